@@ -1,9 +1,17 @@
 #!/usr/bin/env python3
 """bench.py — dpgo edges·iters/sec (+ LC candidates verified/sec) on MI355X.
 
-Contract (see task statement / DESIGN.md §6 "Measurement"):
-  python bench.py --gpus N --steps K --warmup W
+Contract (DESIGN.md §6 "Measurement"):
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1 is launched by torch.distributed.run, one rank per GPU over RCCL).
+
+A plain run does only what the headline figure needs: it builds the graph,
+runs the untimed rounds, times the K rounds, writes the outputs of the last
+timed round when --dump-outputs is given, and prints the result line.
+--full adds everything else, each a run of its own after the timed rounds: the
+evented replay (roofline), the CPU baseline with its parity check, the other
+scaling leg at N > 1, and the LCD / BoW legs (--no-replay, --no-cpu, --no-lcd
+drop single ones of them).
 
 A "step" is one synchronous RBCD round (dpgo_ros UPDATE -> PGOAgent::iterate of
 every robot block, drawio:2058-2066), with GNC-TLS weight updates decided by
@@ -14,8 +22,8 @@ The timed window is a fixed, stated slice of the solve:
   rounds [B, B + W)          untimed: B = --burn-in (default 40) rounds in which
                               tCG stops after 1-5 steps, then the W warmup rounds
   rounds [B + W, B + W + K)  timed (value), K = --steps
-The window is replayed from a snapshot of the solver state (iterate, GNC
-weights and schedule state, statuses) with HIP events around every
+With --full the window is replayed from a snapshot of the solver state (iterate,
+GNC weights and schedule state, statuses) with HIP events around every
 Hessian-vector launch: the roofline describes exactly the timed rounds (the
 replay must reproduce their work counters). The CPU baseline restarts the
 restatement from the same snapshot and times the same rounds.
@@ -55,6 +63,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: evented replay (roofline), CPU baseline "
+                         "+ parity, the other scaling leg (N > 1), LCD and BoW")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed round left (every robot's iterate, the GNC weights, the "
+                         "status words) to DIR/<name>.npy, float64")
     ap.add_argument("--burn-in", type=int, default=40, help="untimed rounds before the warmup (steady-state window)")
     ap.add_argument("--config", default="synth100k", help="synth100k (configs[3]) or synth1m (the cold 1M/5M graph)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong",
@@ -62,9 +76,9 @@ def parse():
     ap.add_argument("--extra-steps", type=int, default=None,
                     help="N > 1: rounds of the other scaling leg (default --steps; 0 = skip)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="bounded CPU-baseline sample per variant")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-lcd", action="store_true")
-    ap.add_argument("--no-replay", action="store_true", help="skip the evented replay (roofline)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-lcd", action="store_true", help="--full without the LCD / BoW legs")
+    ap.add_argument("--no-replay", action="store_true", help="--full without the evented replay (roofline)")
     ap.add_argument("--profile", action="store_true", help="short run for rocprofv3: timed rounds only")
     ap.add_argument("--tile-incidences", type=int, default=0,
                     help="incidences per workgroup tile (kmx_pgo_params.tile_incidences; 0: automatic)")
@@ -115,6 +129,21 @@ def snapshot(drv):
     s = drv.solver
     return {"X": {a: drv.iterate_of(a) for a in drv.robots}, "w": s.get_weights(), "gnc": s.gnc_state(),
             "status": s.status()}
+
+
+def dump_outputs(drv, out_dir, rank, world):
+    """What a caller of the timed path holds after its last round: every local
+    robot's iterate, the GNC weights and the status words (float64), as
+    <out_dir>/<name>.npy. The graph, the lifted start and the schedule are
+    seeded, so the same arguments give the same inputs in every run."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    s = drv.solver
+    tag = f"_rank{rank}" if world > 1 else ""
+    for a in drv.robots:
+        np.save(d / f"iterate_robot{a}.npy", np.asarray(drv.iterate_of(a), np.float64))
+    np.save(d / f"gnc_weights{tag}.npy", np.asarray(s.get_weights(), np.float64))
+    np.save(d / f"status{tag}.npy", np.asarray(s.status(), np.float64))
 
 
 def restore(drv, snap):
@@ -617,10 +646,12 @@ def _gather_each(dist, world, vals):
     return [p.cpu().tolist() for p in parts]
 
 
-def dpgo_leg(g, X0, P, args, rank, world, local_rank, dist, steps, barrier, replay=True, want_snapshot=False):
-    """Burn-in + warmup, snapshot, time `steps` rounds (max over ranks), then
-    replay the same rounds from the snapshot with HIP events around every
-    Hess-vec launch. Returns the team totals."""
+def dpgo_leg(g, X0, P, args, rank, world, local_rank, dist, steps, barrier, replay=True, want_snapshot=False,
+             dump=None):
+    """Burn-in + warmup, snapshot, time `steps` rounds (max over ranks), write
+    the outputs to `dump` if given, then (`replay`) run the same rounds again
+    from the snapshot with HIP events around every Hess-vec launch. Returns
+    the team totals."""
     from kmx.dpgo.driver import RBCDDriver
     drv = RBCDDriver(P, g, rank=rank, world=world, device=local_rank if world > 1 else 0)
     drv.initialize(X0)
@@ -653,6 +684,8 @@ def dpgo_leg(g, X0, P, args, rank, world, local_rank, dist, steps, barrier, repl
         barrier()
         el = time.perf_counter() - t0
         c = drv.solver.read_counters()
+    if dump:  # the state the timed rounds left, before anything else runs on it
+        dump_outputs(drv, dump, rank, world)
     if snap is not None and replay:
         restore(drv, snap)
         sync()
@@ -718,9 +751,10 @@ def main():
     if args.tcg_form == "auto":
         args.tcg_form = "standard"
     P.localOptimizationParams.tCG_form = args.tcg_form
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu and not args.profile
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu and not args.profile
     leg = dpgo_leg(g, X0, P, args, rank, world, local_rank, dist, args.steps, barrier,
-                   replay=not args.no_replay and not args.profile, want_snapshot=want_cpu)
+                   replay=args.full and not args.no_replay and not args.profile, want_snapshot=want_cpu,
+                   dump=args.dump_outputs)
     if args.profile:
         args.steps += args.burn_in + args.warmup  # the profile run counts every round
     el, edges_iters = leg["el"], leg["edges_iters"]
@@ -813,7 +847,7 @@ def main():
             "alg_bytes_rule": "128 B per local edge + 2 x 160 B per pose of every robot in tCG (SURVEY.md §8d)",
         }
     xst = args.steps if args.extra_steps is None else args.extra_steps
-    if world > 1 and xst > 0 and not args.profile:
+    if args.full and world > 1 and xst > 0 and not args.profile:
         other = "weak" if headline == "strong" else "strong"
         del g, X0
         go, X0o = make_workload(args.config, world, other)
@@ -864,7 +898,7 @@ def main():
                 "form": f"{g.n_robots} blocks x {inner} threads inside each block update (oracle "
                         "orc_pgo_round_mt2: edge terms gathered per pose, per-pose loops and dot products "
                         "split; equal to the serial restatement to rounding)"}
-    if not args.no_lcd and not args.profile:
+    if args.full and not args.no_lcd and not args.profile:
         lcd, lcd_cpu = lcd_leg(args, rank, world, barrier)
         n_local, lel = _gather(dist, world, [float(lcd["n_local"] * lcd["steps"]), lcd["elapsed"]], ["sum", "max"])
         lcd["value"] = n_local / lel

@@ -4,9 +4,9 @@
 #   tests        pytest -m gpu (whole suite)          -> TAG/pytest_gpu.log
 #   tests:EXPR   pytest -m gpu -k EXPR (commas = spaces) -> TAG/pytest_k<n>.log
 #   smoke        __graft_entry__.smoke()               -> TAG/smoke.log
-#   bench        python bench.py (defaults)            -> TAG/default.json
-#   bench:ARGS   python bench.py ARGS (commas = spaces)-> TAG/bench_<n>.json
-#   prof         rocprofv3 --kernel-trace --stats of the default bench -> TAG/prof/
+#   bench        python bench.py --full (every leg)    -> TAG/default.json
+#   bench:ARGS   python bench.py ARGS (commas = spaces; --full for more than the headline) -> TAG/bench_<n>.json
+#   prof         rocprofv3 --kernel-trace --stats of bench.py --full -> TAG/prof/
 #   prof:ARGS    the same of bench.py ARGS (commas = spaces) -> TAG/prof_<n>/
 #   py:SCRIPT    python SCRIPT (commas = spaces)       -> TAG/py_<n>.log
 #   env:VAR=VAL:ARGS  bench.py ARGS under VAR=VAL       -> TAG/bench_<n>.json
@@ -34,7 +34,7 @@ for step in "$@"; do
         || { echo "smoke failed"; tail -20 "$O/smoke.log"; exit 1; }
       tail -1 "$O/smoke.log" ;;
     bench)
-      timeout -k 10 500 python bench.py > "$O/default.json" 2> "$O/default.err" \
+      timeout -k 10 500 python bench.py --full > "$O/default.json" 2> "$O/default.err" \
         || { echo "bench failed"; tail -20 "$O/default.err"; exit 1; }
       python scripts/bench_summary.py "$O/default.json" ;;
     bench:*)
@@ -49,7 +49,7 @@ for step in "$@"; do
       echo -n "$kv: "; python scripts/bench_summary.py "$O/bench_$n.json" ;;
     prof)
       mkdir -p "$O/prof"
-      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run --output-format csv -- python3 bench.py \
+      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run --output-format csv -- python3 bench.py --full \
         > "$O/prof/bench.json" 2> "$O/prof/rocprof.err" || { echo "prof failed"; tail -20 "$O/prof/rocprof.err"; exit 1; }
       find "$O/prof" -name '*kernel_stats.csv' | head -1 | xargs -I{} cp {} "$O/kernel_stats.csv"
       head -12 "$O/kernel_stats.csv" | cut -c1-160 ;;

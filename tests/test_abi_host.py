@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
+GOLDEN_PARAMS = ROOT / "tests" / "golden" / "params_D455"
 
 
 def test_library_exports_every_header_symbol():
@@ -64,10 +65,9 @@ def test_params_to_c_and_yaml(tmp_path):
 def test_reference_lcdparams_yaml_if_present():
     """The reference config loads unmodified (refine_pose: 1 included) and
     maps onto the verification parameters, Stewenius and EPnP included; the
-    refinement with PnP recovery is the one combination not built."""
-    f = Path("/root/reference/params/D455/LcdParams.yaml")
-    if not f.exists():
-        pytest.skip("reference not mounted")
+    refinement with PnP recovery is the one combination not built. The file
+    is kept, unmodified, under tests/golden/params_D455/."""
+    f = GOLDEN_PARAMS / "LcdParams.yaml"
     from kmx.lcd import LcdParams
     p = LcdParams.from_yaml(str(f))
     assert p.refine_pose == 1 and p.to_c().refine_pose == 1
@@ -98,9 +98,8 @@ def test_focal_length_from_camera_file(tmp_path):
     bad.write_text("%YAML:1.0\ncamera_id: x\n")
     with pytest.raises(ValueError, match="intrinsics"):
         camera_focal_length(str(bad))
-    ref = Path("/root/reference/params/D455/LeftCameraParams.yaml")
-    if ref.exists():
-        assert camera_focal_length(str(ref)) == LcdParams().focal_length
+    ref = GOLDEN_PARAMS / "LeftCameraParams.yaml"  # the reference's D455 left camera file, unmodified
+    assert camera_focal_length(str(ref)) == LcdParams().focal_length
 
 
 @pytest.mark.parametrize("line,msg", [
