@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define KMX_ABI_VERSION 8
+#define KMX_ABI_VERSION 9
 
 /* error codes */
 #define KMX_OK 0
@@ -560,6 +560,71 @@ int kmx_bow_score_pairs(kmx_bow* h, int32_t n, const int64_t* aptr,
                         const uint32_t* aw, const double* av,
                         const int64_t* bptr, const uint32_t* bw,
                         const double* bv, double* out);
+
+/* ------------------------------------------------------------------------- */
+/* DBoW2 vocabulary transform: ORB descriptors -> BowVectors                  */
+/* ------------------------------------------------------------------------- */
+/* Replaces DBoW2 TemplatedVocabulary<FORB>::transform(features, BowVector&)
+ * for the ORB vocabulary named at launch/kimera_vio_jackal.launch:40 [U: DBoW2
+ * is not vendored; restated from the published algorithm, parity unpinned].
+ * A descriptor (256 bits) descends from the root: among a node's children in
+ * stored order it takes the one of least Hamming distance (the first of equal
+ * children) until it reaches a node without children; that leaf's word id and
+ * weight are its result. A frame's vector is, per weighting,
+ *   TF_IDF / TF:   v[word] += weight, one addition per occurrence;
+ *   IDF / BINARY:  v[word]  = weight;
+ * over the features whose leaf weight is > 0, then divided by its L1 norm
+ * (summed in increasing word id). The output is the CSR row kmx_bow_* reads:
+ * words strictly increasing, weights double. */
+#define KMX_VOC_TF_IDF 0
+#define KMX_VOC_TF 1
+#define KMX_VOC_IDF 2
+#define KMX_VOC_BINARY 3
+
+typedef struct kmx_voc kmx_voc;
+/* The tree in DBoW2's node ids: node 0 is the root (parent[0] is not read), a
+ * node's children are the nodes naming it as parent, in increasing node id
+ * (DBoW2's load order). descriptor: n_nodes x 32 bytes; weight: per node (read
+ * at leaves); word_node[w]: the leaf of word w. Checked before any device
+ * call: KMX_EINVAL for n_nodes < 2, a parent out of range, a cycle or a depth
+ * over 64, a word that maps to an inner node, a leaf that is no word or two
+ * words; KMX_EUNSUP for an unknown weighting. */
+int kmx_voc_create(int device, int32_t n_nodes, const int32_t* parent,
+                   const uint8_t* descriptor, const double* weight, int32_t n_words,
+                   const int32_t* word_node, int weighting, kmx_voc** out);
+int kmx_voc_destroy(kmx_voc* h);
+int kmx_voc_set_stream(kmx_voc* h, void* hip_stream);
+/* Shape of the resident tree (any pointer may be NULL): the largest child
+ * count, the deepest leaf, the nodes of the tree's top kept in LDS, and the
+ * workgroups of the descent kernel (those resident at once on the device). */
+int kmx_voc_info(kmx_voc* h, int32_t* n_nodes, int32_t* n_words, int32_t* max_children,
+                 int32_t* max_depth, int32_t* lds_nodes, int32_t* descend_grid);
+/* Transform n_frames frames of host descriptors desc[n_frames][max_feats][32]
+ * (1 <= max_feats <= 1024; frame f has n_feats[f] features; bytes beyond them
+ * are never read into the result). out_nnz[n_frames]; frame f's vector is
+ * out_words / out_weights [f * max_feats .. f * max_feats + out_nnz[f]). */
+int kmx_voc_transform(kmx_voc* h, int32_t n_frames, int32_t max_feats, const int32_t* n_feats,
+                      const uint8_t* desc, int32_t* out_nnz, uint32_t* out_words,
+                      double* out_weights);
+/* The same on frames resident in a detector's device pool (kmx_lcd_set_frames
+ * / kmx_lcd_add_frames): nothing is uploaded again. frame_ids[n] may repeat
+ * and come in any order; the stride of the outputs is the pool's max_feats.
+ * Ordered after the work enqueued on the detector's stream. KMX_EINVAL for an
+ * id outside the pool or a pool on another device. */
+int kmx_voc_transform_pool(kmx_voc* h, kmx_lcd* pool, int32_t n, const int32_t* frame_ids,
+                           int32_t* out_nnz, uint32_t* out_words, double* out_weights);
+/* Enqueue only (benchmark path); kmx_voc_sync waits. The results stay on the
+ * device. A pool transform in flight reads the pool's buffers: wait for it
+ * before the pool grows or is replaced. */
+int kmx_voc_transform_async(kmx_voc* h, int32_t n_frames, int32_t max_feats,
+                            const int32_t* n_feats, const uint8_t* desc);
+int kmx_voc_transform_pool_async(kmx_voc* h, kmx_lcd* pool, int32_t n, const int32_t* frame_ids);
+int kmx_voc_sync(kmx_voc* h);
+/* Instrumentation: when enabled, every transform brackets its descent and its
+ * per-frame reduction with HIP events; read_timing synchronises and returns
+ * the device times (ms) of the last transform. */
+int kmx_voc_enable_timing(kmx_voc* h, int enable);
+int kmx_voc_read_timing(kmx_voc* h, double* descend_ms, double* reduce_ms);
 
 #ifdef __cplusplus
 }

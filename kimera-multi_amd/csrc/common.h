@@ -10,6 +10,19 @@
 namespace kmx {
 void set_error(const std::string& msg);
 int fail(int code, const std::string& msg);
+
+// The detector's resident frame pool as other parts of the library read it
+// (voc.hip transforms pool frames without a second upload): device pointers
+// that stay valid until the pool next grows or is replaced, and the stream
+// the detector's frame uploads are enqueued on. Reads the handle only.
+struct LcdPoolView {
+  int device = 0;
+  int n_frames = 0, max_feats = 0;
+  const uint32_t* desc = nullptr;  // [n_frames][max_feats][8]
+  const int* n_feats = nullptr;    // [n_frames]
+  hipStream_t stream = nullptr;
+};
+int lcd_pool_view(kmx_lcd* h, LcdPoolView* out);  // lcd.hip
 }  // namespace kmx
 
 #define KMX_HIP(call)                                                        \

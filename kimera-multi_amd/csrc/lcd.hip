@@ -4384,6 +4384,17 @@ extern "C" int kmx_lcd_pool_info(kmx_lcd* h, int32_t* n_frames, int32_t* capacit
   return KMX_OK;
 }
 
+int kmx::lcd_pool_view(kmx_lcd* h, kmx::LcdPoolView* out) {
+  KMX_CHECK(h && out, KMX_EINVAL, "null handle");
+  out->device = h->device;
+  out->n_frames = h->F;
+  out->max_feats = h->N;
+  out->desc = h->d_desc;
+  out->n_feats = h->d_nfeat;
+  out->stream = h->stream;
+  return KMX_OK;
+}
+
 static int check_cands(kmx_lcd* h, int32_t n, const int32_t* cq, const int32_t* cm) {
   KMX_CHECK(h && h->d_desc && h->F > 0, KMX_ESTATE, "no frames: set_frames or add_frames first");
   KMX_CHECK(n >= 0 && (n == 0 || (cq && cm)), KMX_EINVAL, "bad candidate arrays");

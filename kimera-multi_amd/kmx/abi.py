@@ -18,7 +18,7 @@ _LIB_PATH = Path(__file__).resolve().parent / "libkmx.so"
 
 KMX_OK = 0
 KMX_ETIMEOUT = -6
-ABI_VERSION = 8  # include/kmx_abi.h KMX_ABI_VERSION this binding is written for
+ABI_VERSION = 9  # include/kmx_abi.h KMX_ABI_VERSION this binding is written for
 KMX_COST_L2 = 0
 KMX_COMM_ID_BYTES = 128  # include/kmx_abi.h (ncclUniqueId)
 KMX_COST_GNC_TLS = 1
@@ -36,6 +36,12 @@ KMX_RNG_GCC9 = 0
 KMX_RNG_GCC11 = 1
 KMX_LCD_STAGE_2D2D = 1
 KMX_LCD_STAGE_RECOVER = 2
+KMX_EINVAL = -1
+KMX_EUNSUP = -5
+KMX_VOC_TF_IDF = 0
+KMX_VOC_TF = 1
+KMX_VOC_IDF = 2
+KMX_VOC_BINARY = 3
 
 TCG_STOP_NAMES = {0: "none", 1: "negative_curvature", 2: "exceeded_trust_region",
                   3: "linear", 4: "superlinear", 5: "max_iterations", 6: "skipped"}
@@ -209,6 +215,17 @@ def lib() -> C.CDLL:
         "kmx_bow_query_async": ([P, i32, pi64, pu32, pf64, pi32, i32], C.c_int),
         "kmx_bow_sync": ([P], C.c_int),
         "kmx_bow_score_pairs": ([P, i32, pi64, pu32, pf64, pi64, pu32, pf64, pf64], C.c_int),
+        "kmx_voc_create": ([C.c_int, i32, pi32, pu8, pf64, i32, pi32, C.c_int, C.POINTER(P)], C.c_int),
+        "kmx_voc_destroy": ([P], C.c_int),
+        "kmx_voc_set_stream": ([P, P], C.c_int),
+        "kmx_voc_info": ([P, pi32, pi32, pi32, pi32, pi32, pi32], C.c_int),
+        "kmx_voc_transform": ([P, i32, i32, pi32, pu8, pi32, pu32, pf64], C.c_int),
+        "kmx_voc_transform_pool": ([P, P, i32, pi32, pi32, pu32, pf64], C.c_int),
+        "kmx_voc_transform_async": ([P, i32, i32, pi32, pu8], C.c_int),
+        "kmx_voc_transform_pool_async": ([P, P, i32, pi32], C.c_int),
+        "kmx_voc_sync": ([P], C.c_int),
+        "kmx_voc_enable_timing": ([P, C.c_int], C.c_int),
+        "kmx_voc_read_timing": ([P, pf64, pf64], C.c_int),
     })
     for name, (argt, rest) in sig.items():
         if not hasattr(L, name):

@@ -167,11 +167,28 @@ class TemporalConstraint:
 class BowDetector:
     """Loop-candidate detection on BowVectors (one database per robot)."""
 
-    def __init__(self, params: LcdParams | None = None, n_words: int = 1_000_000, device: int = 0):
+    def __init__(self, params: LcdParams | None = None, n_words: int = 1_000_000, device: int = 0,
+                 vocabulary=None):
+        """vocabulary: a kmx.lcd.vocabulary.Vocabulary. When given, n_words is
+        the vocabulary's and `transform` turns ORB descriptors into the
+        BowVectors the detection calls take; None (the default) leaves the
+        detector on caller-made BowVectors over `n_words` words."""
         self.p = params or LcdParams()
-        self.n_words = n_words
+        self.n_words = n_words if vocabulary is None else vocabulary.n_words
         self.device = device
         self.db: dict[int, BowDatabase] = {}
+        self.vocabulary = vocabulary
+        self._gpu_voc = None
+
+    def transform(self, n_feats, desc):
+        """DBoW2 transform of frames (desc uint8 [F, N, 32], n_feats [F]) with
+        the detector's vocabulary: CSR (vptr, words, weights)."""
+        if self.vocabulary is None:
+            raise ValueError("BowDetector.transform needs a vocabulary (BowDetector(..., vocabulary=...))")
+        if self._gpu_voc is None:
+            from .vocabulary import GpuVocabulary
+            self._gpu_voc = GpuVocabulary(self.vocabulary, self.device)
+        return self._gpu_voc.transform(n_feats, desc)
 
     def set_robot_database(self, robot: int, vptr, words, weights):
         db = self.db.get(robot) or BowDatabase(self.n_words, self.device)

@@ -320,6 +320,12 @@ class LoopClosureDetector:
         check(self.L.kmx_lcd_pool_info(self.h, C.byref(f), C.byref(cap), C.byref(n)), "kmx_lcd_pool_info")
         return {"n_frames": f.value, "capacity": cap.value, "max_feats": n.value}
 
+    def bow_vectors(self, gpu_vocabulary, frame_ids):
+        """BowVectors (CSR vptr, words, weights) of resident frames, made on
+        the device from the pool's descriptors by a
+        kmx.lcd.vocabulary.GpuVocabulary (no second upload)."""
+        return gpu_vocabulary.transform_pool(self, frame_ids)
+
     def addVLCFrame(self, frame: VLCFrame) -> int:
         """LoopClosureDetector::addVLCFrame (drawio:2601): the frame joins the
         device pool (padded to the pool's feature stride, `nfeatures` of
