@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define KMX_ABI_VERSION 9
+#define KMX_ABI_VERSION 10
 
 /* error codes */
 #define KMX_OK 0
@@ -560,6 +560,64 @@ int kmx_bow_score_pairs(kmx_bow* h, int32_t n, const int64_t* aptr,
                         const uint32_t* aw, const double* av,
                         const int64_t* bptr, const uint32_t* bw,
                         const double* bv, double* out);
+
+/* ---- Streaming database: DBoW2 Database::add, one keyframe or batch at a
+ * time. Every entry's vector stays resident on the device (a forward store);
+ * entries [0, n_sealed) are in the inverted file, the tail [n_sealed,
+ * n_entries) is scored per query from the forward store and merged in. After
+ * any sequence of set_database / add calls every query returns bit for bit
+ * what kmx_bow_set_database of the same vectors returns. Query vectors must be
+ * BowVectors (words strictly increasing). kmx_bow_set_database keeps its
+ * behaviour: it replaces everything and leaves all entries sealed. */
+struct kmx_voc; /* below */
+/* An empty database over n_words words (= set_database with 0 entries). Reads
+ * KMX_BOW_LDS, KMX_BOW_CHUNK and KMX_BOW_TAIL, as kmx_bow_set_database does. */
+int kmx_bow_reset(kmx_bow* h, int32_t n_words);
+/* Database::add of n host vectors in order; the first gets id n_entries
+ * (*first_id_out, may be NULL). Checked on the host before any device call,
+ * the database unchanged on failure: KMX_EINVAL for a non-monotone vptr, words
+ * not strictly increasing, a word >= n_words, or totals >= INT32_MAX;
+ * KMX_ESTATE without a database. An empty vector is a legal entry. */
+int kmx_bow_add_entries(kmx_bow* h, int32_t n, const int64_t* vptr,
+                        const uint32_t* words, const double* weights,
+                        int32_t* first_id_out);
+/* Append the vectors voc's last kmx_voc_transform*[_async] left on the device,
+ * ordered after voc's stream; no word or weight passes through the host.
+ * KMX_EINVAL when voc's word count differs from the database's; KMX_ESTATE
+ * when voc holds no batch. */
+int kmx_bow_add_from_voc(kmx_bow* h, struct kmx_voc* voc, int32_t* first_id_out, int32_t* n_out);
+/* Move the tail into the inverted file now (on the device). An add seals by
+ * itself when the tail holds more than tail_cap entries. */
+int kmx_bow_seal(kmx_bow* h);
+/* tail_cap in [0, 1024] (the tail's sort capacity); default 64. The
+ * environment variable KMX_BOW_TAIL, read at set_database / reset, overrides. */
+int kmx_bow_set_tail_cap(kmx_bow* h, int32_t cap);
+/* Any pointer may be NULL. device_bytes: inverted file, scratch and forward store. */
+int kmx_bow_info(kmx_bow* h, int32_t* n_words, int32_t* n_entries, int32_t* n_sealed,
+                 int32_t* tail_cap, int64_t* n_postings, int64_t* device_bytes);
+/* Read stored vectors [first, first + n) back as CSR: vptr_out[n + 1] from 0.
+ * words_out == NULL fills only vptr_out (to size the arrays); otherwise
+ * words_out / weights_out hold `cap` >= vptr_out[n] elements. */
+int kmx_bow_get_entries(kmx_bow* h, int32_t first, int32_t n, int64_t* vptr_out,
+                        uint32_t* words_out, double* weights_out, int64_t cap);
+/* kmx_bow_query with query q = stored entry entry_ids[q] of src (src may be h
+ * or another database on the same device); ordered after src's stream; no
+ * query words are uploaded. src's forward store must not grow while a query
+ * that reads it is in flight. */
+int kmx_bow_query_entries(kmx_bow* h, kmx_bow* src, int32_t nq, const int32_t* entry_ids,
+                          const int32_t* max_id, int32_t max_results, int32_t* out_n,
+                          int32_t* out_ids, double* out_scores);
+int kmx_bow_query_entries_async(kmx_bow* h, kmx_bow* src, int32_t nq,
+                                const int32_t* entry_ids, const int32_t* max_id,
+                                int32_t max_results);
+/* Wait for the last kmx_bow_query_async / kmx_bow_query_entries_async (same nq
+ * and max_results) and copy its results out, as the synchronous forms do. */
+int kmx_bow_fetch(kmx_bow* h, int32_t nq, int32_t max_results, int32_t* out_n,
+                  int32_t* out_ids, double* out_scores);
+/* L1Scoring::score of stored entries (a_ids[i], b_ids[i]) of src; an id of -1
+ * (no entry) or an empty vector scores 0. */
+int kmx_bow_score_entries(kmx_bow* src, int32_t n, const int32_t* a_ids,
+                          const int32_t* b_ids, double* out);
 
 /* ------------------------------------------------------------------------- */
 /* DBoW2 vocabulary transform: ORB descriptors -> BowVectors                  */

@@ -17,6 +17,13 @@
 //     which are sorted in LDS (bitonic) — no pass over all n_entries.
 //   * k_bow_pair_score: one thread per pair, the sorted-list merge of
 //     L1Scoring::score (nss factor against the previous keyframe).
+//   * Database::add (kmx_bow_add_entries / kmx_bow_add_from_voc): every
+//     entry's vector stays in a device-resident forward store; the newest
+//     entries (the tail) are scored per query by k_bow_tail and merged with
+//     the inverted file's results, and are sealed into the inverted file on
+//     the device (k_bow_seal_*, k_bow_cptr) every tail_cap adds. Queries and
+//     nss factors by entry id (k_bow_gather, k_bow_entry_score) read the
+//     forward store, so a keyframe's vector never leaves the GPU.
 // Compiled with -ffp-contract=off (no FMA to contract here anyway).
 #include <hip/hip_runtime.h>
 
@@ -25,6 +32,7 @@
 #include <string>
 #include <vector>
 
+#include "bow_host.h"
 #include "common.h"
 
 namespace {
@@ -531,6 +539,317 @@ __global__ void k_bow_pair_score(int n, const long long* aptr, const unsigned* a
   out[t] = -s / 2.0;
 }
 
+// ---------------------------------------------------------------------------
+// The streaming database (Database::add): a forward store of every entry's
+// vector, entry-major, a sealed base [0, n_sealed) that the two query kernels
+// above serve unchanged, and an unsealed tail [n_sealed, n_entries) that
+// exists only in the forward store.
+struct BowFwd {
+  const long long* fptr;  // [n_entries + 1]
+  const unsigned* fw;     // words, strictly increasing per entry
+  const double* fv;       // weights
+};
+
+constexpr int TAIL_MAX = 1024;      // the largest tail_cap: what k_bow_tail's LDS sort holds beside MAX_RESULTS
+constexpr int TAIL_DEFAULT = 64;    // measured: DESIGN.md section 12
+constexpr int TL_WAVES = 16;
+constexpr int TL_BLOCK = 64 * TL_WAVES;
+constexpr int TL_QW = 2048;         // query words staged in LDS (longer queries are searched in HBM)
+constexpr int TL_SORT = 2048;       // >= TAIL_MAX + MAX_RESULTS, a power of two
+static_assert(TAIL_MAX + MAX_RESULTS <= TL_SORT && (TL_SORT & (TL_SORT - 1)) == 0, "tail sort capacity");
+
+// Same as L1Scoring::score of stored entries a_ids[t], b_ids[t]; an id of -1
+// scores 0 and reads nothing.
+__global__ void k_bow_entry_score(int n, BowFwd f, const int* a_ids, const int* b_ids, double* out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const int a = a_ids[t], b = b_ids[t];
+  double s = 0.0;
+  if (a >= 0 && b >= 0) {
+    long long i = f.fptr[a], j = f.fptr[b];
+    const long long ie = f.fptr[a + 1], je = f.fptr[b + 1];
+    while (i < ie && j < je) {
+      const unsigned x = f.fw[i], y = f.fw[j];
+      if (x == y) {
+        s += fabs(f.fv[i] - f.fv[j]) - fabs(f.fv[i]) - fabs(f.fv[j]);
+        ++i;
+        ++j;
+      } else if (x < y) {
+        ++i;
+      } else {
+        ++j;
+      }
+    }
+  }
+  out[t] = -s / 2.0;
+}
+
+// Inclusive scan of one value per thread over a block of TL_BLOCK threads
+// (every thread calls it); *total = the block's sum. s_w holds TL_WAVES values.
+__device__ __forceinline__ long long block_scan_incl(long long x, long long* s_w, long long* total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  long long incl = x;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const long long t = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += t;
+  }
+  if (lane == 63) s_w[w] = incl;
+  __syncthreads();
+  long long base = 0, tot = 0;
+  for (int k = 0; k < TL_WAVES; ++k) {
+    if (k < w) base += s_w[k];
+    tot += s_w[k];
+  }
+  __syncthreads();  // s_w may be written again
+  *total = tot;
+  return base + incl;
+}
+
+// One block. SRC 0: out[i + 1] = out[0] + sum of nnz[0..i] (appending a
+// vocabulary batch: out = fptr + n_entries). SRC 1: out[0] = 0, out[i + 1] =
+// the summed lengths of entries ids[0..i] (queries by entry id).
+template <int SRC>
+__global__ __launch_bounds__(TL_BLOCK) void k_bow_scan_len(int n, const int* nnz_or_ids, const long long* fptr,
+                                                           long long* out) {
+  __shared__ long long s_w[TL_WAVES];
+  long long carry = SRC == 0 ? out[0] : 0;
+  if (SRC == 1 && threadIdx.x == 0) out[0] = 0;
+  for (int t0 = 0; t0 < n; t0 += TL_BLOCK) {
+    const int i = t0 + (int)threadIdx.x;
+    long long len = 0;
+    if (i < n) {
+      const int v = nnz_or_ids[i];
+      len = SRC == 0 ? v : fptr[v + 1] - fptr[v];
+    }
+    long long tot;
+    const long long incl = block_scan_incl(len, s_w, &tot);
+    if (i < n) out[i + 1] = carry + incl;
+    carry += tot;
+  }
+}
+
+// Frame b of a vocabulary batch (nnz[b] words at stride) -> its place in the forward store.
+__global__ void k_bow_voc_compact(const int* nnz, const unsigned* words, const double* weights, int stride,
+                                  const long long* fptr_new, unsigned* fw, double* fv) {
+  const int b = blockIdx.x;
+  const int n = min(nnz[b], stride);
+  const long long dst = fptr_new[b];
+  for (int k = threadIdx.x; k < n; k += blockDim.x) {
+    fw[dst + k] = words[(size_t)b * stride + k];
+    fv[dst + k] = weights[(size_t)b * stride + k];
+  }
+}
+
+// Query q := entry ids[q] of `src`, copied to the query buffers (qptr from k_bow_scan_len<1>).
+__global__ void k_bow_gather(BowFwd src, const int* ids, const long long* qptr, unsigned* qw, double* qv) {
+  const int q = blockIdx.x;
+  const long long s0 = src.fptr[ids[q]], d0 = qptr[q];
+  const int n = (int)(qptr[q + 1] - d0);
+  for (int k = threadIdx.x; k < n; k += blockDim.x) {
+    qw[d0 + k] = src.fw[s0 + k];
+    qv[d0 + k] = src.fv[s0 + k];
+  }
+}
+
+// k_bow_tail: after a base query kernel, score the unsealed entries against
+// each query and merge them into its results in place. One workgroup per
+// query (grid-stride). A wave per tail entry: the lanes read 64 consecutive
+// words of the entry, each looks its word up in the query (staged in LDS,
+// sorted: a binary search), and the matches are added lane by lane in ballot
+// order, so the sum is one chain over the common words in increasing word id
+// starting from 0.0 — the chain k_bow_query / k_bow_query_lds build for a
+// sealed entry, bit for bit. Query words >= n_words cannot match: stored
+// words are < n_words. A tail entry is a result iff its sum is non-zero and
+// (id < max_id or max_id == -1). The candidates (<= TAIL_MAX) and the base's
+// results (<= MAX_RESULTS) are sorted in LDS by (score descending, id
+// ascending); score = -acc / 2 is exact, so this is the (acc, id) order.
+__global__ __launch_bounds__(TL_BLOCK) void k_bow_tail(BowFwd f, int n_sealed, int n_entries, int nq,
+                                                       const long long* qptr, const unsigned* qw, const double* qv,
+                                                       const int* max_id, int K, int* out_n, int* out_id,
+                                                       double* out_score) {
+  __shared__ double c_val[TL_SORT];
+  __shared__ double s_qv[TL_QW];
+  __shared__ int c_id[TL_SORT];
+  __shared__ unsigned s_qw[TL_QW];
+  __shared__ int s_nc;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  for (int q = blockIdx.x; q < nq; q += gridDim.x) {
+    const long long q0 = qptr[q];
+    const int nw = (int)min(qptr[q + 1] - q0, (long long)INT32_MAX);
+    const bool staged = nw <= TL_QW;
+    __syncthreads();  // the previous query's readers of LDS are done
+    if (staged)
+      for (int i = tid; i < nw; i += TL_BLOCK) {
+        s_qw[i] = qw[q0 + i];
+        s_qv[i] = qv[q0 + i];
+      }
+    if (tid == 0) s_nc = 0;
+    __syncthreads();
+    const unsigned* sw = staged ? s_qw : qw + q0;
+    const double* sv = staged ? s_qv : qv + q0;
+    const int mid = max_id ? max_id[q] : -1;
+    const int hi = (mid == -1) ? n_entries : min(mid, n_entries);  // entries < hi are eligible
+    for (int e = n_sealed + wv; e < hi; e += TL_WAVES) {
+      const long long p0 = f.fptr[e], p1 = f.fptr[e + 1];
+      double s = 0.0;
+      for (long long pb = p0; pb < p1; pb += 64) {
+        const long long p = pb + lane;
+        const bool ok = p < p1;
+        const unsigned w = ok ? f.fw[p] : 0u;
+        int lo = 0, up = nw;
+        while (lo < up) {
+          const int m = (lo + up) >> 1;
+          if (sw[m] < w) lo = m + 1;
+          else up = m;
+        }
+        const bool hit = ok && lo < nw && sw[lo] == w;
+        double v = 0.0;
+        if (hit) {
+          const double qval = sv[lo], d = f.fv[p];
+          v = fabs(qval - d) - fabs(qval) - fabs(d);
+        }
+        unsigned long long mask = __ballot(hit);
+        while (mask) {  // ordered: lane order is word order
+          const int l = __ffsll((long long)mask) - 1;
+          s += __shfl(v, l, 64);
+          mask &= mask - 1;
+        }
+      }
+      if (lane == 0 && s != 0.0) {
+        const int slot = atomicAdd(&s_nc, 1);  // <= tail size <= TAIL_MAX
+        if (slot < TAIL_MAX) { c_val[slot] = -s / 2.0; c_id[slot] = e; }
+      }
+    }
+    __syncthreads();
+    const int nc = min(s_nc, TAIL_MAX);
+    if (nc == 0) continue;  // the base's results stand
+    const int nb = min(out_n[q], K);
+    for (int i = tid; i < nb; i += TL_BLOCK) {
+      c_val[nc + i] = out_score[(size_t)q * K + i];
+      c_id[nc + i] = out_id[(size_t)q * K + i];
+    }
+    const int nt = nc + nb;
+    int n2 = 1;
+    while (n2 < nt) n2 <<= 1;
+    for (int i = nt + tid; i < n2; i += TL_BLOCK) { c_val[i] = -1.0; c_id[i] = 0x7fffffff; }
+    __syncthreads();
+    for (int k = 2; k <= n2; k <<= 1) {
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int i = tid; i < n2; i += TL_BLOCK) {
+          const int l = i ^ j;
+          if (l > i) {
+            const bool up = (i & k) == 0;
+            // key_less on (-score, id): larger scores first, then smaller ids
+            const bool sw2 = up ? key_less(-c_val[l], c_id[l], -c_val[i], c_id[i])
+                                : key_less(-c_val[i], c_id[i], -c_val[l], c_id[l]);
+            if (sw2) {
+              const double tv = c_val[i]; c_val[i] = c_val[l]; c_val[l] = tv;
+              const int ti = c_id[i]; c_id[i] = c_id[l]; c_id[l] = ti;
+            }
+          }
+        }
+        __syncthreads();
+      }
+    }
+    const int nout = min(K, nt);
+    for (int i = tid; i < nout; i += TL_BLOCK) {
+      out_id[(size_t)q * K + i] = c_id[i];
+      out_score[(size_t)q * K + i] = c_val[i];
+    }
+    if (tid == 0) out_n[q] = nout;
+  }
+}
+
+// ---- sealing the tail into the base, on the device
+// cnt[w + 1] += 1 for every tail posting of word w (cnt zeroed, n_words + 1 ints).
+__global__ void k_bow_seal_count(const unsigned* fw, long long p0, long long p1, int n_words, int* cnt) {
+  for (long long p = p0 + blockIdx.x * (long long)blockDim.x + threadIdx.x; p < p1;
+       p += (long long)gridDim.x * blockDim.x) {
+    const unsigned w = fw[p];
+    if (w < (unsigned)n_words) atomicAdd(&cnt[w + 1], 1);
+  }
+}
+
+// One block: new_ptr[i] = old_ptr[i] + (tail postings of words < i), i in [0, n_words].
+__global__ __launch_bounds__(TL_BLOCK) void k_bow_seal_ptr(int n_words, const int* old_ptr, const int* cnt,
+                                                           int* new_ptr) {
+  __shared__ long long s_w[TL_WAVES];
+  long long carry = 0;
+  for (int t0 = 0; t0 <= n_words; t0 += TL_BLOCK) {
+    const int i = t0 + (int)threadIdx.x;
+    long long tot;
+    const long long incl = block_scan_incl(i <= n_words ? cnt[i] : 0, s_w, &tot);
+    if (i <= n_words) new_ptr[i] = old_ptr[i] + (int)(carry + incl);
+    carry += tot;
+  }
+}
+
+// Tail postings, a wave per tail entry, dropped into their word's segment of
+// tmp in arrival order (cursor zeroed, n_words ints); k_bow_seal_place orders
+// each segment by entry id. A word's segment starts at new_ptr[w] - old_ptr[w].
+__global__ void k_bow_seal_fill(BowFwd f, int e0, int e1, int n_words, const int* old_ptr, const int* new_ptr,
+                                int* cursor, int* tmp_e, double* tmp_v, int n_tmp) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwave = (gridDim.x * blockDim.x) >> 6;
+  for (int e = e0 + wave; e < e1; e += nwave) {
+    const long long p1 = f.fptr[e + 1];
+    for (long long p = f.fptr[e] + lane; p < p1; p += 64) {
+      const unsigned w = f.fw[p];
+      if (w >= (unsigned)n_words) continue;
+      const int slot = new_ptr[w] - old_ptr[w] + atomicAdd(&cursor[w], 1);
+      if (slot >= 0 && slot < n_tmp) { tmp_e[slot] = e; tmp_v[slot] = f.fv[p]; }
+    }
+  }
+}
+
+// A wave per word: the old list moves to its shifted place, and the word's
+// tail segment follows it ordered by entry id (rank by counting: an entry
+// occurs once per word, so the ranks are a permutation). Lists stay ascending.
+__global__ void k_bow_seal_place(int n_words, const int* old_ptr, const int* new_ptr, const int* old_ent,
+                                 const double* old_wt, const int* tmp_e, const double* tmp_v, int* new_ent,
+                                 double* new_wt) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwave = (gridDim.x * blockDim.x) >> 6;
+  for (int w = wave; w < n_words; w += nwave) {
+    const int o0 = old_ptr[w], o1 = old_ptr[w + 1], d0 = new_ptr[w], d1 = new_ptr[w + 1];
+    const int n_old = o1 - o0;
+    for (int k = lane; k < n_old; k += 64) {
+      new_ent[d0 + k] = old_ent[o0 + k];
+      new_wt[d0 + k] = old_wt[o0 + k];
+    }
+    const int t0 = d0 - o0, L = (d1 - d0) - n_old, dst = d0 + n_old;
+    for (int i = lane; i < L; i += 64) {
+      const int e = tmp_e[t0 + i];
+      int rank = 0;
+      for (int k = 0; k < L; ++k) rank += tmp_e[t0 + k] < e ? 1 : 0;
+      new_ent[dst + rank] = e;
+      new_wt[dst + rank] = tmp_v[t0 + i];
+    }
+  }
+}
+
+// cptr[w][c] = first posting of word w with entry >= c * sch (c < nsub), and
+// the list's end at c == nsub: what kmx_bow_set_database builds on the host.
+__global__ void k_bow_cptr(int n_words, int nsub, int sch, const int* ptr, const int* ent, int* cptr) {
+  const size_t total = (size_t)n_words * (nsub + 1);
+  for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+    const int w = (int)(t / (nsub + 1)), c = (int)(t - (size_t)w * (nsub + 1));
+    int lo = ptr[w], up = ptr[w + 1];
+    if (c < nsub) {
+      const long long bound = (long long)c * sch;
+      while (lo < up) {
+        const int m = lo + ((up - lo) >> 1);
+        if (ent[m] < bound) lo = m + 1;
+        else up = m;
+      }
+    } else {
+      lo = up;
+    }
+    cptr[t] = lo;
+  }
+}
+
 template <typename T>
 int bow_alloc(T** p, size_t n) {
   *p = nullptr;
@@ -570,6 +889,26 @@ struct kmx_bow {
   long long *d_aptr = nullptr, *d_bptr = nullptr;
   unsigned *d_aw = nullptr, *d_bw = nullptr;
   double *d_av = nullptr, *d_bv = nullptr, *d_pout = nullptr;
+  // streaming database: entries [0, n_sealed) are in the inverted file above,
+  // [n_sealed, n_entries) only in the forward store (every entry's vector)
+  int n_sealed = 0;
+  int tail_cap = TAIL_DEFAULT, tail_cap_set = TAIL_DEFAULT;
+  size_t fe_cap = 0, fp_cap = 0;  // forward store capacity: entries, postings
+  long long* d_fptr = nullptr;
+  unsigned* d_fw = nullptr;
+  double* d_fv = nullptr;
+  std::vector<int64_t> h_fptr{0};  // host mirror of d_fptr (8 bytes per entry; no words or weights)
+  size_t base_cap = 0;             // ints at d_ent / doubles at d_wt
+  size_t cptr_cap = 0, scratch_cap = 0;
+  hipEvent_t ev = nullptr;         // orders this handle after another handle's stream
+  // seal scratch (grow-only) and entry-id scratch
+  int* d_cnt = nullptr;
+  size_t tmp_cap = 0;
+  int* d_tmp_e = nullptr;
+  double* d_tmp_v = nullptr;
+  size_t ecap = 0;
+  int* d_eid = nullptr;
+  double* d_eout = nullptr;
 };
 
 namespace {
@@ -582,6 +921,22 @@ void bow_free_db(kmx_bow* h) {
   h->d_acc = nullptr;
   h->d_touched = nullptr;
   h->n_wg = 0;
+  h->base_cap = h->cptr_cap = h->scratch_cap = 0;
+}
+void bow_free_fwd(kmx_bow* h) {
+  for (void* p : {(void*)h->d_fptr, (void*)h->d_fw, (void*)h->d_fv, (void*)h->d_cnt, (void*)h->d_tmp_e,
+                  (void*)h->d_tmp_v})
+    if (p) (void)hipFree(p);
+  h->d_fptr = nullptr; h->d_fw = nullptr; h->d_fv = nullptr;
+  h->d_cnt = h->d_tmp_e = nullptr; h->d_tmp_v = nullptr;
+  h->fe_cap = h->fp_cap = h->tmp_cap = 0;
+  h->h_fptr.assign(1, 0);
+}
+void bow_free_e(kmx_bow* h) {
+  if (h->d_eid) (void)hipFree(h->d_eid);
+  if (h->d_eout) (void)hipFree(h->d_eout);
+  h->d_eid = nullptr; h->d_eout = nullptr;
+  h->ecap = 0;
 }
 void bow_free_q(kmx_bow* h) {
   for (void* p : {(void*)h->d_qptr, (void*)h->d_qw, (void*)h->d_qv, (void*)h->d_maxid, (void*)h->d_n,
@@ -599,6 +954,141 @@ void bow_free_p(kmx_bow* h) {
   h->d_av = h->d_bv = h->d_pout = nullptr;
   h->pcap = h->pwcap = 0;
 }
+
+// Room in the forward store for ne entries and np postings: capacity
+// doubling, one device-to-device copy of what is held per doubling.
+int bow_fwd_reserve(kmx_bow* h, size_t ne, size_t np) {
+  const bool grow_e = !h->d_fptr || ne > h->fe_cap, grow_p = !h->d_fw || np > h->fp_cap;
+  if (!grow_e && !grow_p) return 0;
+  const size_t held_e = (size_t)h->n_entries + 1, held_p = (size_t)h->h_fptr.back();
+  long long* nf = nullptr;
+  unsigned* nw = nullptr;
+  double* nv = nullptr;
+  int rc = 0;
+  const size_t ec = std::max<size_t>({ne, 2 * h->fe_cap, 1024}), pc = std::max<size_t>({np, 2 * h->fp_cap, 65536});
+  if (grow_e) rc = bow_alloc(&nf, ec + 1);
+  if (!rc && grow_p) rc = bow_alloc(&nw, pc);
+  if (!rc && grow_p) rc = bow_alloc(&nv, pc);
+  hipError_t e = hipSuccess;
+  if (!rc && grow_e)
+    e = h->d_fptr ? hipMemcpyAsync(nf, h->d_fptr, sizeof(long long) * held_e, hipMemcpyDeviceToDevice, h->stream)
+                  : hipMemsetAsync(nf, 0, sizeof(long long), h->stream);
+  if (!rc && grow_p && h->d_fw && held_p) {
+    if (e == hipSuccess) e = hipMemcpyAsync(nw, h->d_fw, sizeof(unsigned) * held_p, hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(nv, h->d_fv, sizeof(double) * held_p, hipMemcpyDeviceToDevice, h->stream);
+  }
+  if (!rc && e == hipSuccess) e = hipStreamSynchronize(h->stream);  // queries in flight read the old store
+  if (rc || e != hipSuccess) {
+    for (void* p : {(void*)nf, (void*)nw, (void*)nv})
+      if (p) (void)hipFree(p);
+    return rc ? rc : kmx::fail(KMX_EHIP, std::string("forward store: ") + hipGetErrorString(e));
+  }
+  if (grow_e) {
+    if (h->d_fptr) (void)hipFree(h->d_fptr);
+    h->d_fptr = nf;
+    h->fe_cap = ec;
+  }
+  if (grow_p) {
+    if (h->d_fw) (void)hipFree(h->d_fw);
+    if (h->d_fv) (void)hipFree(h->d_fv);
+    h->d_fw = nw;
+    h->d_fv = nv;
+    h->fp_cap = pc;
+  }
+  return 0;
+}
+
+// Seal the tail: the inverted file over [0, n_entries), built on the device
+// from the old one and the tail's vectors in the forward store. Afterwards
+// d_ptr / d_ent / d_wt / d_cptr are what kmx_bow_set_database builds from the
+// same entries. No posting crosses to the host (its totals are in h_fptr).
+int bow_seal(kmx_bow* h) {
+  const int n = h->n_entries, e0 = h->n_sealed, nw = h->n_words;
+  if (n == e0) return KMX_OK;
+  KMX_HIP(hipSetDevice(h->device));
+  const long long p0 = h->h_fptr[e0], p1 = h->h_fptr[n];
+  const size_t n_tail = (size_t)(p1 - p0), n_new = (size_t)p1;
+  int rc = 0;
+  if (!h->d_cnt && (rc = bow_alloc(&h->d_cnt, (size_t)nw + 1))) return rc;
+  if (n_tail > h->tmp_cap || !h->d_tmp_e) {
+    if (h->d_tmp_e) (void)hipFree(h->d_tmp_e);
+    if (h->d_tmp_v) (void)hipFree(h->d_tmp_v);
+    h->d_tmp_e = nullptr;
+    h->d_tmp_v = nullptr;
+    h->tmp_cap = 0;
+    const size_t cap = std::max<size_t>(n_tail, 65536);
+    if ((rc = bow_alloc(&h->d_tmp_e, cap)) || (rc = bow_alloc(&h->d_tmp_v, cap))) return rc;
+    h->tmp_cap = cap;
+  }
+  const int nch = std::max(1, (n + h->ch - 1) / h->ch), nsub = nch * LW_WAVES, sch = h->ch / LW_WAVES;
+  const size_t cneed = h->lds ? (size_t)nw * (nsub + 1) : 0;
+  const size_t sneed = h->lds ? 1 : (size_t)h->n_wg * std::max(n, 1);
+  int *new_ptr = nullptr, *new_ent = nullptr, *new_cptr = nullptr, *new_touched = nullptr;
+  double *new_wt = nullptr, *new_acc = nullptr;
+  auto drop = [&]() {
+    for (void* p : {(void*)new_ptr, (void*)new_ent, (void*)new_wt, (void*)new_cptr, (void*)new_acc,
+                    (void*)new_touched})
+      if (p) (void)hipFree(p);
+  };
+  if ((rc = bow_alloc(&new_ptr, (size_t)nw + 1)) || (rc = bow_alloc(&new_ent, n_new)) ||
+      (rc = bow_alloc(&new_wt, n_new)) || (cneed > h->cptr_cap && (rc = bow_alloc(&new_cptr, cneed))) ||
+      (sneed > h->scratch_cap && ((rc = bow_alloc(&new_acc, sneed)) || (rc = bow_alloc(&new_touched, sneed))))) {
+    drop();
+    return rc;
+  }
+  BowFwd f{h->d_fptr, h->d_fw, h->d_fv};
+  hipError_t e = hipMemsetAsync(h->d_cnt, 0, sizeof(int) * ((size_t)nw + 1), h->stream);
+  if (e == hipSuccess && n_tail) {
+    const int grid = (int)std::min<size_t>((n_tail + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_bow_seal_count, dim3(grid), dim3(256), 0, h->stream, (const unsigned*)h->d_fw, p0, p1, nw,
+                       h->d_cnt);
+  }
+  if (e == hipSuccess)
+    hipLaunchKernelGGL(k_bow_seal_ptr, dim3(1), dim3(TL_BLOCK), 0, h->stream, nw, (const int*)h->d_ptr,
+                       (const int*)h->d_cnt, new_ptr);
+  if (e == hipSuccess) e = hipMemsetAsync(h->d_cnt, 0, sizeof(int) * ((size_t)nw + 1), h->stream);
+  if (e == hipSuccess && n_tail)
+    hipLaunchKernelGGL(k_bow_seal_fill, dim3(std::min((n - e0 + 3) / 4, 2048)), dim3(256), 0, h->stream, f, e0, n, nw,
+                       (const int*)h->d_ptr, (const int*)new_ptr, h->d_cnt, h->d_tmp_e, h->d_tmp_v, (int)n_tail);
+  if (e == hipSuccess)
+    hipLaunchKernelGGL(k_bow_seal_place, dim3(std::min((nw + 3) / 4, 4096)), dim3(256), 0, h->stream, nw,
+                       (const int*)h->d_ptr, (const int*)new_ptr, (const int*)h->d_ent, (const double*)h->d_wt,
+                       (const int*)h->d_tmp_e, (const double*)h->d_tmp_v, new_ent, new_wt);
+  if (e == hipSuccess && h->lds) {  // in place when the table keeps its shape: only earlier queries read it
+    const int grid = (int)std::min<size_t>((cneed + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_bow_cptr, dim3(grid), dim3(256), 0, h->stream, nw, nsub, sch, (const int*)new_ptr,
+                       (const int*)new_ent, new_cptr ? new_cptr : h->d_cptr);
+  }
+  if (e == hipSuccess && new_acc) e = hipMemsetAsync(new_acc, 0, sizeof(double) * sneed, h->stream);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // the old arrays are read until here
+  if (e != hipSuccess) {
+    drop();
+    return kmx::fail(KMX_EHIP, std::string("kmx_bow_seal: ") + hipGetErrorString(e));
+  }
+  (void)hipFree(h->d_ptr);
+  (void)hipFree(h->d_ent);
+  (void)hipFree(h->d_wt);
+  h->d_ptr = new_ptr;
+  h->d_ent = new_ent;
+  h->d_wt = new_wt;
+  h->base_cap = std::max<size_t>(n_new, 1);
+  if (new_cptr) {
+    if (h->d_cptr) (void)hipFree(h->d_cptr);
+    h->d_cptr = new_cptr;
+    h->cptr_cap = cneed;
+  }
+  if (new_acc) {
+    (void)hipFree(h->d_acc);
+    (void)hipFree(h->d_touched);
+    h->d_acc = new_acc;
+    h->d_touched = new_touched;
+    h->scratch_cap = sneed;
+  }
+  h->nch = nch;
+  h->n_sealed = n;
+  return KMX_OK;
+}
 }  // namespace
 
 extern "C" int kmx_bow_create(int device, kmx_bow** out) {
@@ -615,7 +1105,9 @@ extern "C" int kmx_bow_create(int device, kmx_bow** out) {
     return kmx::fail(KMX_EHIP, "hipStreamCreate failed");
   }
   h->own_stream = true;
-  if (hipMalloc(reinterpret_cast<void**>(&h->d_err), 2 * sizeof(int)) != hipSuccess) {
+  if (hipMalloc(reinterpret_cast<void**>(&h->d_err), 2 * sizeof(int)) != hipSuccess ||
+      hipEventCreateWithFlags(&h->ev, hipEventDisableTiming) != hipSuccess) {
+    if (h->d_err) (void)hipFree(h->d_err);
     (void)hipStreamDestroy(h->stream);
     delete h;
     return kmx::fail(KMX_ENOMEM, "hipMalloc failed");
@@ -632,6 +1124,9 @@ extern "C" int kmx_bow_destroy(kmx_bow* h) {
   bow_free_db(h);
   bow_free_q(h);
   bow_free_p(h);
+  bow_free_fwd(h);
+  bow_free_e(h);
+  if (h->ev) (void)hipEventDestroy(h->ev);
   if (h->d_err) (void)hipFree(h->d_err);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -718,19 +1213,181 @@ extern "C" int kmx_bow_set_database(kmx_bow* h, int32_t n_words, int32_t n_entri
   KMX_HIP(hipMemcpy(h->d_ent, ent.data(), sizeof(int) * ent.size(), hipMemcpyHostToDevice));
   KMX_HIP(hipMemcpy(h->d_wt, wt.data(), sizeof(double) * wt.size(), hipMemcpyHostToDevice));
   KMX_HIP(hipMemset(h->d_acc, 0, sizeof(double) * scratch));
+  h->base_cap = ent.size();
+  h->cptr_cap = h->lds ? cptr.size() : 0;
+  h->scratch_cap = scratch;
+  // the forward store: the same vectors entry-major (one more upload of the
+  // CSR), all of them sealed. KMX_BOW_TAIL overrides kmx_bow_set_tail_cap.
+  h->n_entries = 0;  // until the forward store holds them
+  h->n_sealed = 0;
+  bow_free_fwd(h);
+  h->tail_cap = h->tail_cap_set;
+  if (const char* v = std::getenv("KMX_BOW_TAIL")) h->tail_cap = std::max(0, std::min(TAIL_MAX, std::atoi(v)));
+  const int64_t held = vptr[n_entries] - vptr[0];
+  if (int rc2 = bow_fwd_reserve(h, (size_t)n_entries, (size_t)held)) {
+    bow_free_db(h);
+    return rc2;
+  }
+  std::vector<int64_t> fp((size_t)n_entries + 1);
+  for (int e = 0; e <= n_entries; ++e) fp[e] = vptr[e] - vptr[0];
+  KMX_HIP(hipMemcpy(h->d_fptr, fp.data(), sizeof(long long) * fp.size(), hipMemcpyHostToDevice));
+  if (held) {
+    KMX_HIP(hipMemcpy(h->d_fw, words + vptr[0], sizeof(unsigned) * (size_t)held, hipMemcpyHostToDevice));
+    KMX_HIP(hipMemcpy(h->d_fv, weights + vptr[0], sizeof(double) * (size_t)held, hipMemcpyHostToDevice));
+  }
+  h->h_fptr.swap(fp);
+  h->n_entries = h->n_sealed = n_entries;
+  return KMX_OK;
+  KMX_GUARD_END
+}
+
+extern "C" int kmx_bow_reset(kmx_bow* h, int32_t n_words) {
+  const int64_t zero = 0;
+  return kmx_bow_set_database(h, n_words, 0, &zero, nullptr, nullptr);
+}
+
+extern "C" int kmx_bow_set_tail_cap(kmx_bow* h, int32_t cap) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(h, KMX_EINVAL, "null handle");
+  KMX_CHECK(cap >= 0 && cap <= TAIL_MAX, KMX_EINVAL, "tail_cap must be in [0, 1024]");
+  h->tail_cap_set = cap;
+  if (!std::getenv("KMX_BOW_TAIL")) h->tail_cap = cap;
+  if (h->d_ptr && h->n_entries - h->n_sealed > h->tail_cap) return bow_seal(h);
+  return KMX_OK;
+  KMX_GUARD_END
+}
+
+extern "C" int kmx_bow_seal(kmx_bow* h) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(h && h->d_ptr, KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
+  return bow_seal(h);
+  KMX_GUARD_END
+}
+
+extern "C" int kmx_bow_info(kmx_bow* h, int32_t* n_words, int32_t* n_entries, int32_t* n_sealed, int32_t* tail_cap,
+                            int64_t* n_postings, int64_t* device_bytes) {
+  KMX_CHECK(h, KMX_EINVAL, "null handle");
+  if (n_words) *n_words = h->n_words;
+  if (n_entries) *n_entries = h->n_entries;
+  if (n_sealed) *n_sealed = h->n_sealed;
+  if (tail_cap) *tail_cap = h->tail_cap;
+  if (n_postings) *n_postings = h->h_fptr.back();
+  if (device_bytes) {
+    size_t b = 0;
+    if (h->d_ptr)
+      b = sizeof(int) * ((size_t)h->n_words + 1) + (sizeof(int) + sizeof(double)) * h->base_cap +
+          sizeof(int) * h->cptr_cap + (sizeof(int) + sizeof(double)) * h->scratch_cap +
+          sizeof(long long) * (h->fe_cap + 1) + (sizeof(unsigned) + sizeof(double)) * h->fp_cap;
+    *device_bytes = (int64_t)b;
+  }
+  return KMX_OK;
+}
+
+extern "C" int kmx_bow_add_entries(kmx_bow* h, int32_t n, const int64_t* vptr, const uint32_t* words,
+                                   const double* weights, int32_t* first_id_out) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(h, KMX_EINVAL, "null handle");
+  KMX_CHECK(h->d_ptr, KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
+  std::string err;
+  if (int rc = kmx::bow_check_csr(h->n_words, h->n_entries, h->h_fptr.back(), n, vptr, words, &err))
+    return kmx::fail(rc, err);
+  if (first_id_out) *first_id_out = h->n_entries;
+  if (n == 0) return KMX_OK;
+  const int64_t total = vptr[n] - vptr[0], base = h->h_fptr.back();
+  KMX_CHECK(total == 0 || weights, KMX_EINVAL, "null weights");
+  KMX_HIP(hipSetDevice(h->device));
+  if (int rc = bow_fwd_reserve(h, (size_t)h->n_entries + n, (size_t)(base + total))) return rc;
+  const size_t m0 = h->h_fptr.size();  // n_entries + 1
+  for (int e = 1; e <= n; ++e) h->h_fptr.push_back(base + (vptr[e] - vptr[0]));
+  hipError_t e1 = hipMemcpyAsync(h->d_fptr + m0, h->h_fptr.data() + m0, sizeof(long long) * n,
+                                 hipMemcpyHostToDevice, h->stream);
+  if (e1 == hipSuccess && total)
+    e1 = hipMemcpyAsync(h->d_fw + base, words + vptr[0], sizeof(unsigned) * total, hipMemcpyHostToDevice, h->stream);
+  if (e1 == hipSuccess && total)
+    e1 = hipMemcpyAsync(h->d_fv + base, weights + vptr[0], sizeof(double) * total, hipMemcpyHostToDevice, h->stream);
+  if (e1 == hipSuccess) e1 = hipStreamSynchronize(h->stream);  // the caller's arrays are free again
+  if (e1 != hipSuccess) {
+    h->h_fptr.resize(m0);  // the entries were not added
+    return kmx::fail(KMX_EHIP, std::string("kmx_bow_add_entries: ") + hipGetErrorString(e1));
+  }
+  h->n_entries += n;
+  if (h->n_entries - h->n_sealed > h->tail_cap) return bow_seal(h);
+  return KMX_OK;
+  KMX_GUARD_END
+}
+
+extern "C" int kmx_bow_add_from_voc(kmx_bow* h, kmx_voc* voc, int32_t* first_id_out, int32_t* n_out) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(h && voc, KMX_EINVAL, "null handle");
+  KMX_CHECK(h->d_ptr, KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
+  kmx::VocBatchView vb;
+  if (int rc = kmx::voc_batch_view(voc, &vb)) return rc;
+  KMX_CHECK(vb.device == h->device, KMX_EINVAL, "the vocabulary is on another device");
+  KMX_CHECK(vb.n_words == h->n_words, KMX_EINVAL, "the vocabulary's word count differs from the database's");
+  KMX_CHECK(vb.n_frames > 0 && vb.stride > 0 && vb.nnz && vb.words && vb.weights, KMX_ESTATE,
+            "the vocabulary holds no transformed batch");
+  const int n = vb.n_frames;
+  const int64_t base = h->h_fptr.back(), most = (int64_t)n * vb.stride;  // a frame has <= stride words
+  KMX_CHECK(n < INT32_MAX - h->n_entries, KMX_EINVAL, "database too large (entries must fit int32)");
+  KMX_CHECK(most < (int64_t)INT32_MAX - base, KMX_EINVAL, "database too large (postings must fit int32)");
+  KMX_HIP(hipSetDevice(h->device));
+  if (int rc = bow_fwd_reserve(h, (size_t)h->n_entries + n, (size_t)(base + most))) return rc;
+  // after the transform, which runs on the vocabulary's stream
+  KMX_HIP(hipEventRecord(h->ev, vb.stream));
+  KMX_HIP(hipStreamWaitEvent(h->stream, h->ev, 0));
+  long long* fnew = h->d_fptr + h->n_entries;
+  hipLaunchKernelGGL(k_bow_scan_len<0>, dim3(1), dim3(TL_BLOCK), 0, h->stream, n, vb.nnz,
+                     (const long long*)nullptr, fnew);
+  KMX_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_bow_voc_compact, dim3(n), dim3(256), 0, h->stream, vb.nnz, (const unsigned*)vb.words,
+                     vb.weights, vb.stride, (const long long*)fnew, h->d_fw, h->d_fv);
+  KMX_HIP(hipGetLastError());
+  // the new entries' offsets come back to the host mirror: 8 bytes per entry, no words or weights
+  const size_t m0 = h->h_fptr.size();
+  h->h_fptr.resize(m0 + n);
+  hipError_t e1 = hipMemcpyAsync(h->h_fptr.data() + m0, fnew + 1, sizeof(long long) * n, hipMemcpyDeviceToHost,
+                                 h->stream);
+  if (e1 == hipSuccess) e1 = hipStreamSynchronize(h->stream);
+  if (e1 != hipSuccess) {
+    h->h_fptr.resize(m0);
+    return kmx::fail(KMX_EHIP, std::string("kmx_bow_add_from_voc: ") + hipGetErrorString(e1));
+  }
+  if (first_id_out) *first_id_out = h->n_entries;
+  if (n_out) *n_out = n;
+  h->n_entries += n;
+  if (h->n_entries - h->n_sealed > h->tail_cap) return bow_seal(h);
+  return KMX_OK;
+  KMX_GUARD_END
+}
+
+extern "C" int kmx_bow_get_entries(kmx_bow* h, int32_t first, int32_t n, int64_t* vptr_out, uint32_t* words_out,
+                                   double* weights_out, int64_t cap) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(h && vptr_out, KMX_EINVAL, "null argument");
+  KMX_CHECK(h->d_ptr, KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
+  KMX_CHECK(first >= 0 && n >= 0 && (int64_t)first + n <= h->n_entries, KMX_EINVAL, "entry range outside the database");
+  const int64_t p0 = h->h_fptr[first], total = h->h_fptr[(size_t)first + n] - p0;
+  for (int i = 0; i <= n; ++i) vptr_out[i] = h->h_fptr[(size_t)first + i] - p0;
+  if (!words_out) return KMX_OK;  // sizes only
+  KMX_CHECK(weights_out && cap >= total, KMX_EINVAL, "output arrays too small (vptr_out[n] words)");
+  if (total == 0) return KMX_OK;
+  KMX_HIP(hipSetDevice(h->device));
+  KMX_HIP(hipMemcpyAsync(words_out, h->d_fw + p0, sizeof(unsigned) * total, hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(weights_out, h->d_fv + p0, sizeof(double) * total, hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipStreamSynchronize(h->stream));
   return KMX_OK;
   KMX_GUARD_END
 }
 
 namespace {
-int bow_upload_queries(kmx_bow* h, int32_t nq, const int64_t* qptr, const uint32_t* words, const double* weights,
-                       const int32_t* max_id, int32_t K) {
-  const size_t nw = (size_t)qptr[nq];
-  if ((size_t)nq + 1 > h->qcap || nw > h->wcap || (size_t)nq * K > h->rcap) {
+// Room for nq queries of nw words in all and their K results each.
+int bow_reserve_queries(kmx_bow* h, size_t nq, size_t nw, int32_t K) {
+  if (nq + 1 > h->qcap || nw > h->wcap || nq * K > h->rcap) {
+    KMX_HIP(hipStreamSynchronize(h->stream));  // a query in flight uses the old buffers
     bow_free_q(h);
     h->qcap = std::max<size_t>(nq + 1, 1024);
     h->wcap = std::max<size_t>(nw, 1);
-    h->rcap = std::max<size_t>((size_t)nq * K, 1);
+    h->rcap = std::max<size_t>(nq * K, 1);
     int rc;
     if ((rc = bow_alloc(&h->d_qptr, h->qcap)) || (rc = bow_alloc(&h->d_qw, h->wcap)) ||
         (rc = bow_alloc(&h->d_qv, h->wcap)) || (rc = bow_alloc(&h->d_maxid, h->qcap)) ||
@@ -740,12 +1397,77 @@ int bow_upload_queries(kmx_bow* h, int32_t nq, const int64_t* qptr, const uint32
       return rc;
     }
   }
+  return KMX_OK;
+}
+
+int bow_upload_queries(kmx_bow* h, int32_t nq, const int64_t* qptr, const uint32_t* words, const double* weights,
+                       const int32_t* max_id, int32_t K) {
+  const size_t nw = (size_t)qptr[nq];
+  if (int rc = bow_reserve_queries(h, (size_t)nq, nw, K)) return rc;
   KMX_HIP(hipMemcpyAsync(h->d_qptr, qptr, sizeof(long long) * (nq + 1), hipMemcpyHostToDevice, h->stream));
   if (nw) {
     KMX_HIP(hipMemcpyAsync(h->d_qw, words, sizeof(unsigned) * nw, hipMemcpyHostToDevice, h->stream));
     KMX_HIP(hipMemcpyAsync(h->d_qv, weights, sizeof(double) * nw, hipMemcpyHostToDevice, h->stream));
   }
   if (max_id) KMX_HIP(hipMemcpyAsync(h->d_maxid, max_id, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
+  return KMX_OK;
+}
+
+// The query kernels over the queries in d_qptr / d_qw / d_qv: the base's
+// kernel, then, only when there are unsealed entries, k_bow_tail.
+int bow_launch_query(kmx_bow* h, int32_t nq, bool has_max_id, int32_t max_results) {
+  // only after an add whose seal failed: k_bow_tail holds TAIL_MAX candidates, so seal first
+  if (h->n_entries - h->n_sealed > TAIL_MAX)
+    if (int rc = bow_seal(h)) return rc;
+  KMX_HIP(hipMemsetAsync(h->d_err, 0, 2 * sizeof(int), h->stream));  // error flag, query counter
+  BowDb db{h->d_ptr, h->d_ent, h->d_wt, h->n_words, h->n_sealed};
+  const int grid = std::min(nq, h->n_wg);
+  const int* mid = has_max_id ? (const int*)h->d_maxid : nullptr;
+  if (h->lds) {
+    hipLaunchKernelGGL(k_bow_query_lds, dim3(grid), dim3(LW_BLOCK), LDS_BOW, h->stream, db,
+                       (const int*)h->d_cptr, h->nch, h->ch, nq, (const long long*)h->d_qptr,
+                       (const unsigned*)h->d_qw, (const double*)h->d_qv, mid, max_results, h->d_n, h->d_id,
+                       h->d_score, h->d_err, h->d_err + 1);
+  } else {
+    hipLaunchKernelGGL(k_bow_query, dim3(grid), dim3(BOW_BLOCK), 0, h->stream, db, nq,
+                       (const long long*)h->d_qptr, (const unsigned*)h->d_qw, (const double*)h->d_qv, mid,
+                       max_results, h->d_acc, h->d_touched, h->d_n, h->d_id, h->d_score, h->d_err, h->d_err + 1);
+  }
+  KMX_HIP(hipGetLastError());
+  if (h->n_entries > h->n_sealed) {
+    BowFwd f{h->d_fptr, h->d_fw, h->d_fv};
+    hipLaunchKernelGGL(k_bow_tail, dim3(std::min(nq, 4096)), dim3(TL_BLOCK), 0, h->stream, f, h->n_sealed,
+                       h->n_entries, nq, (const long long*)h->d_qptr, (const unsigned*)h->d_qw,
+                       (const double*)h->d_qv, mid, max_results, h->d_n, h->d_id, h->d_score);
+    KMX_HIP(hipGetLastError());
+  }
+  return KMX_OK;
+}
+
+int bow_fetch_results(kmx_bow* h, int32_t nq, int32_t max_results, int32_t* out_n, int32_t* out_ids,
+                      double* out_scores) {
+  int err = 0;
+  KMX_HIP(hipMemcpyAsync(out_n, h->d_n, sizeof(int) * nq, hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(out_ids, h->d_id, sizeof(int) * (size_t)nq * max_results, hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(out_scores, h->d_score, sizeof(double) * (size_t)nq * max_results, hipMemcpyDeviceToHost,
+                         h->stream));
+  KMX_HIP(hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipStreamSynchronize(h->stream));
+  KMX_CHECK(!err, KMX_EUNSUP, "too many exactly tied scores at the max_results cut");
+  return KMX_OK;
+}
+
+int bow_reserve_ids(kmx_bow* h, size_t n) {
+  if (n <= h->ecap) return KMX_OK;
+  KMX_HIP(hipStreamSynchronize(h->stream));
+  bow_free_e(h);
+  const size_t cap = std::max<size_t>(n, 1024);
+  int rc;
+  if ((rc = bow_alloc(&h->d_eid, 2 * cap)) || (rc = bow_alloc(&h->d_eout, cap))) {
+    bow_free_e(h);
+    return rc;
+  }
+  h->ecap = cap;
   return KMX_OK;
 }
 }  // namespace
@@ -760,24 +1482,7 @@ extern "C" int kmx_bow_query_async(kmx_bow* h, int32_t nq, const int64_t* qptr, 
   for (int q = 0; q < nq; ++q) KMX_CHECK(qptr[q + 1] >= qptr[q], KMX_EINVAL, "qptr not monotone");
   if (int rc = bow_upload_queries(h, nq, qptr, words, weights, max_id, max_results)) return rc;
   if (nq == 0) return KMX_OK;
-  KMX_HIP(hipMemsetAsync(h->d_err, 0, 2 * sizeof(int), h->stream));  // error flag, query counter
-  BowDb db{h->d_ptr, h->d_ent, h->d_wt, h->n_words, h->n_entries};
-  const int grid = std::min(nq, h->n_wg);
-  if (h->lds) {
-    hipLaunchKernelGGL(k_bow_query_lds, dim3(grid), dim3(LW_BLOCK), LDS_BOW, h->stream, db,
-                       (const int*)h->d_cptr, h->nch, h->ch, nq, (const long long*)h->d_qptr,
-                       (const unsigned*)h->d_qw, (const double*)h->d_qv,
-                       max_id ? (const int*)h->d_maxid : nullptr, max_results, h->d_n, h->d_id, h->d_score,
-                       h->d_err, h->d_err + 1);
-    KMX_HIP(hipGetLastError());
-    return KMX_OK;
-  }
-  hipLaunchKernelGGL(k_bow_query, dim3(grid), dim3(BOW_BLOCK), 0, h->stream, db, nq,
-                     (const long long*)h->d_qptr, (const unsigned*)h->d_qw, (const double*)h->d_qv,
-                     max_id ? (const int*)h->d_maxid : nullptr, max_results, h->d_acc, h->d_touched, h->d_n,
-                     h->d_id, h->d_score, h->d_err, h->d_err + 1);
-  KMX_HIP(hipGetLastError());
-  return KMX_OK;
+  return bow_launch_query(h, nq, max_id != nullptr, max_results);
   KMX_GUARD_END
 }
 
@@ -788,14 +1493,85 @@ extern "C" int kmx_bow_query(kmx_bow* h, int32_t nq, const int64_t* qptr, const 
   KMX_CHECK(out_n && out_ids && out_scores, KMX_EINVAL, "null output");
   if (int rc = kmx_bow_query_async(h, nq, qptr, words, weights, max_id, max_results)) return rc;
   if (nq == 0) return KMX_OK;
-  int err = 0;
-  KMX_HIP(hipMemcpyAsync(out_n, h->d_n, sizeof(int) * nq, hipMemcpyDeviceToHost, h->stream));
-  KMX_HIP(hipMemcpyAsync(out_ids, h->d_id, sizeof(int) * (size_t)nq * max_results, hipMemcpyDeviceToHost, h->stream));
-  KMX_HIP(hipMemcpyAsync(out_scores, h->d_score, sizeof(double) * (size_t)nq * max_results, hipMemcpyDeviceToHost,
-                         h->stream));
-  KMX_HIP(hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  KMX_HIP(hipStreamSynchronize(h->stream));
-  KMX_CHECK(!err, KMX_EUNSUP, "too many exactly tied scores at the max_results cut");
+  return bow_fetch_results(h, nq, max_results, out_n, out_ids, out_scores);
+  KMX_GUARD_END
+}
+
+extern "C" int kmx_bow_query_entries_async(kmx_bow* h, kmx_bow* src, int32_t nq, const int32_t* entry_ids,
+                                           const int32_t* max_id, int32_t max_results) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(h && h->d_ptr && src && src->d_ptr, KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
+  KMX_CHECK(nq >= 0 && (nq == 0 || entry_ids) && max_results > 0 && max_results <= MAX_RESULTS, KMX_EINVAL,
+            "bad argument (max_results in [1, 256])");
+  KMX_CHECK(src->device == h->device, KMX_EINVAL, "the source database is on another device");
+  size_t nw = 0;
+  for (int q = 0; q < nq; ++q) {
+    KMX_CHECK(entry_ids[q] >= 0 && entry_ids[q] < src->n_entries, KMX_EINVAL, "entry id outside the source database");
+    nw += (size_t)(src->h_fptr[(size_t)entry_ids[q] + 1] - src->h_fptr[entry_ids[q]]);
+  }
+  if (nq == 0) return KMX_OK;
+  KMX_HIP(hipSetDevice(h->device));
+  int rc;
+  if ((rc = bow_reserve_queries(h, (size_t)nq, nw, max_results)) || (rc = bow_reserve_ids(h, (size_t)nq))) return rc;
+  if (src != h && src->stream != h->stream) {  // after the adds enqueued on the source's stream
+    KMX_HIP(hipEventRecord(h->ev, src->stream));
+    KMX_HIP(hipStreamWaitEvent(h->stream, h->ev, 0));
+  }
+  KMX_HIP(hipMemcpyAsync(h->d_eid, entry_ids, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
+  if (max_id) KMX_HIP(hipMemcpyAsync(h->d_maxid, max_id, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
+  BowFwd f{src->d_fptr, src->d_fw, src->d_fv};
+  hipLaunchKernelGGL(k_bow_scan_len<1>, dim3(1), dim3(TL_BLOCK), 0, h->stream, nq, (const int*)h->d_eid, f.fptr,
+                     h->d_qptr);
+  KMX_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_bow_gather, dim3(nq), dim3(256), 0, h->stream, f, (const int*)h->d_eid,
+                     (const long long*)h->d_qptr, h->d_qw, h->d_qv);
+  KMX_HIP(hipGetLastError());
+  return bow_launch_query(h, nq, max_id != nullptr, max_results);
+  KMX_GUARD_END
+}
+
+extern "C" int kmx_bow_query_entries(kmx_bow* h, kmx_bow* src, int32_t nq, const int32_t* entry_ids,
+                                     const int32_t* max_id, int32_t max_results, int32_t* out_n, int32_t* out_ids,
+                                     double* out_scores) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(out_n && out_ids && out_scores, KMX_EINVAL, "null output");
+  if (int rc = kmx_bow_query_entries_async(h, src, nq, entry_ids, max_id, max_results)) return rc;
+  if (nq == 0) return KMX_OK;
+  return bow_fetch_results(h, nq, max_results, out_n, out_ids, out_scores);
+  KMX_GUARD_END
+}
+
+extern "C" int kmx_bow_fetch(kmx_bow* h, int32_t nq, int32_t max_results, int32_t* out_n, int32_t* out_ids,
+                             double* out_scores) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(h && out_n && out_ids && out_scores, KMX_EINVAL, "null argument");
+  KMX_CHECK(nq >= 0 && max_results > 0 && (size_t)nq + 1 <= h->qcap && (size_t)nq * max_results <= h->rcap,
+            KMX_EINVAL, "no enqueued query of this shape");
+  if (nq == 0) return KMX_OK;
+  KMX_HIP(hipSetDevice(h->device));
+  return bow_fetch_results(h, nq, max_results, out_n, out_ids, out_scores);
+  KMX_GUARD_END
+}
+
+extern "C" int kmx_bow_score_entries(kmx_bow* src, int32_t n, const int32_t* a_ids, const int32_t* b_ids,
+                                     double* out) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(src && n >= 0 && (n == 0 || (a_ids && b_ids && out)), KMX_EINVAL, "bad argument");
+  KMX_CHECK(src->d_ptr, KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
+  for (int i = 0; i < n; ++i)
+    KMX_CHECK(a_ids[i] >= -1 && a_ids[i] < src->n_entries && b_ids[i] >= -1 && b_ids[i] < src->n_entries,
+              KMX_EINVAL, "entry id outside the database (-1: no entry)");
+  if (n == 0) return KMX_OK;
+  KMX_HIP(hipSetDevice(src->device));
+  if (int rc = bow_reserve_ids(src, (size_t)n)) return rc;
+  KMX_HIP(hipMemcpyAsync(src->d_eid, a_ids, sizeof(int) * n, hipMemcpyHostToDevice, src->stream));
+  KMX_HIP(hipMemcpyAsync(src->d_eid + src->ecap, b_ids, sizeof(int) * n, hipMemcpyHostToDevice, src->stream));
+  BowFwd f{src->d_fptr, src->d_fw, src->d_fv};
+  hipLaunchKernelGGL(k_bow_entry_score, dim3((n + 255) / 256), dim3(256), 0, src->stream, n, f,
+                     (const int*)src->d_eid, (const int*)(src->d_eid + src->ecap), src->d_eout);
+  KMX_HIP(hipGetLastError());
+  KMX_HIP(hipMemcpyAsync(out, src->d_eout, sizeof(double) * n, hipMemcpyDeviceToHost, src->stream));
+  KMX_HIP(hipStreamSynchronize(src->stream));
   return KMX_OK;
   KMX_GUARD_END
 }

@@ -1,0 +1,87 @@
+// bow_check.cpp — bow.hip's host code (bow_host.h: the CSR validation of
+// kmx_bow_add_entries) as a stand-alone program, built by `make bow_check`
+// with the host address and undefined-behaviour sanitizers. It feeds
+// kmx::bow_check_csr the inputs kmx_bow_add_entries must reject, in arrays of
+// exactly the stated size so that a read past either is a report. CPU only.
+#include <climits>
+#include <cstdio>
+#include <random>
+#include <string>
+#include <vector>
+
+#include "bow_host.h"
+
+namespace {
+
+int g_fail = 0;
+
+void expect_code(int32_t n_words, int64_t n_now, int64_t post_now, const std::vector<int64_t>& vptr,
+                 const std::vector<uint32_t>& words, int code, const char* what) {
+  // exact-size copies, so a read past either array is a sanitizer report
+  std::vector<int64_t> vp(vptr);
+  std::vector<uint32_t> w(words);
+  std::string err;
+  const int64_t n = vp.empty() ? 0 : (int64_t)vp.size() - 1;
+  const int rc = kmx::bow_check_csr(n_words, n_now, post_now, n, vp.empty() ? nullptr : vp.data(),
+                                    w.empty() ? nullptr : w.data(), &err);
+  if (rc != code || (code != KMX_OK && err.find(what) == std::string::npos)) {
+    std::fprintf(stderr, "expected %d (%s), got %d (%s)\n", code, what, rc, err.c_str());
+    ++g_fail;
+  }
+}
+
+}  // namespace
+
+int main() {
+  // empty input: no vectors, one empty vector, empty vectors between full ones
+  expect_code(10, 0, 0, {}, {}, KMX_OK, "");
+  expect_code(10, 0, 0, {0}, {}, KMX_OK, "");
+  expect_code(10, 5, 7, {0, 0}, {}, KMX_OK, "");
+  expect_code(10, 0, 0, {0, 2, 2, 5, 5}, {1, 9, 0, 4, 8}, KMX_OK, "");
+  expect_code(10, 0, 0, {3, 5}, {7, 7, 7, 2, 3}, KMX_OK, "");  // vptr need not start at 0
+  // a non-monotone vptr
+  expect_code(10, 0, 0, {0, 3, 2}, {1, 2, 3}, KMX_EINVAL, "vptr not monotone");
+  expect_code(10, 0, 0, {-1, 2}, {1, 2}, KMX_EINVAL, "vptr not monotone");
+  // a repeated word, a decreasing word
+  expect_code(10, 0, 0, {0, 3}, {1, 4, 4}, KMX_EINVAL, "strictly increasing");
+  expect_code(10, 0, 0, {0, 2, 4}, {1, 4, 5, 2}, KMX_EINVAL, "strictly increasing");
+  // a word equal to n_words, and beyond
+  expect_code(10, 0, 0, {0, 3}, {1, 4, 10}, KMX_EINVAL, "word id >= n_words");
+  expect_code(10, 0, 0, {0, 1}, {0xffffffffu}, KMX_EINVAL, "word id >= n_words");
+  // int32 overflow of the total: refused before a word is read (there are none)
+  expect_code(10, 0, 0, {0, (int64_t)INT32_MAX}, {}, KMX_EINVAL, "postings must fit int32");
+  expect_code(10, 0, (int64_t)INT32_MAX - 3, {0, 3}, {1, 2, 3}, KMX_EINVAL, "postings must fit int32");
+  expect_code(10, 0, (int64_t)INT32_MAX - 4, {0, 3}, {1, 2, 3}, KMX_OK, "");
+  expect_code(10, 0, 0, {0, INT64_MAX}, {}, KMX_EINVAL, "postings must fit int32");
+  expect_code(10, (int64_t)INT32_MAX - 1, 0, {0, 0}, {}, KMX_EINVAL, "entries must fit int32");
+  expect_code(0, 0, 0, {0, 0}, {}, KMX_EINVAL, "bad argument");
+  // random valid batches, and each with one word broken
+  std::mt19937 rng(4321);
+  int batches = 0;
+  for (int rep = 0; rep < 300; ++rep) {
+    const int32_t n_words = 1 + (int32_t)(rng() % 50);
+    const int n = (int)(rng() % 6);
+    std::vector<int64_t> vptr{(int64_t)(rng() % 3)};
+    std::vector<uint32_t> words(vptr[0], 0xdeadbeefu);  // never read: before vptr[0]
+    for (int e = 0; e < n; ++e) {
+      for (int32_t w = 0; w < n_words; ++w)
+        if (rng() % 3 == 0) words.push_back((uint32_t)w);
+      vptr.push_back((int64_t)words.size());
+    }
+    expect_code(n_words, rep, rep * 7, vptr, words, KMX_OK, "");
+    ++batches;
+    const size_t first = (size_t)vptr[0];
+    if (words.size() > first) {
+      std::vector<uint32_t> broken(words);
+      const size_t k = first + rng() % (words.size() - first);
+      broken[k] = (uint32_t)n_words + (uint32_t)(rng() % 3);
+      expect_code(n_words, rep, rep * 7, vptr, broken, KMX_EINVAL, "word id >= n_words");
+    }
+  }
+  if (g_fail) {
+    std::fprintf(stderr, "bow_check: %d failure(s)\n", g_fail);
+    return 1;
+  }
+  std::printf("bow_check ok: %d random batches, malformed batches rejected\n", batches);
+  return 0;
+}

@@ -23,6 +23,21 @@ struct LcdPoolView {
   hipStream_t stream = nullptr;
 };
 int lcd_pool_view(kmx_lcd* h, LcdPoolView* out);  // lcd.hip
+
+// The BowVectors a vocabulary's last transform left on the device, as bow.hip
+// reads them (kmx_bow_add_from_voc appends them without a host copy): frame f
+// holds nnz[f] words at words / weights [f * stride ..). The pointers stay
+// valid until the vocabulary's next transform; `stream` is the one the
+// transform was enqueued on. n_frames == 0: no batch. Reads the handle only.
+struct VocBatchView {
+  int device = 0;
+  int n_words = 0, n_frames = 0, stride = 0;
+  const int* nnz = nullptr;         // [n_frames]
+  const uint32_t* words = nullptr;  // [n_frames][stride]
+  const double* weights = nullptr;  // [n_frames][stride]
+  hipStream_t stream = nullptr;
+};
+int voc_batch_view(kmx_voc* h, VocBatchView* out);  // voc.hip
 }  // namespace kmx
 
 #define KMX_HIP(call)                                                        \

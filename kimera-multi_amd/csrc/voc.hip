@@ -322,6 +322,19 @@ int voc_fetch(kmx_voc* h, int32_t* out_nnz, uint32_t* out_words, double* out_wei
 
 }  // namespace
 
+int kmx::voc_batch_view(kmx_voc* h, kmx::VocBatchView* out) {
+  KMX_CHECK(h && out, KMX_EINVAL, "null argument");
+  out->device = h->device;
+  out->n_words = h->n_words;
+  out->n_frames = h->last_frames;
+  out->stride = h->last_N;
+  out->nnz = h->d_nnz;
+  out->words = h->d_words;
+  out->weights = h->d_weights;
+  out->stream = h->stream;
+  return KMX_OK;
+}
+
 extern "C" int kmx_voc_create(int device, int32_t n_nodes, const int32_t* parent, const uint8_t* descriptor,
                               const double* weight, int32_t n_words, const int32_t* word_node, int weighting,
                               kmx_voc** out) {

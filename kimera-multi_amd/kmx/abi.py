@@ -18,7 +18,7 @@ _LIB_PATH = Path(__file__).resolve().parent / "libkmx.so"
 
 KMX_OK = 0
 KMX_ETIMEOUT = -6
-ABI_VERSION = 9  # include/kmx_abi.h KMX_ABI_VERSION this binding is written for
+ABI_VERSION = 10  # include/kmx_abi.h KMX_ABI_VERSION this binding is written for
 KMX_COST_L2 = 0
 KMX_COMM_ID_BYTES = 128  # include/kmx_abi.h (ncclUniqueId)
 KMX_COST_GNC_TLS = 1
@@ -37,6 +37,7 @@ KMX_RNG_GCC11 = 1
 KMX_LCD_STAGE_2D2D = 1
 KMX_LCD_STAGE_RECOVER = 2
 KMX_EINVAL = -1
+KMX_ESTATE = -3
 KMX_EUNSUP = -5
 KMX_VOC_TF_IDF = 0
 KMX_VOC_TF = 1
@@ -215,6 +216,17 @@ def lib() -> C.CDLL:
         "kmx_bow_query_async": ([P, i32, pi64, pu32, pf64, pi32, i32], C.c_int),
         "kmx_bow_sync": ([P], C.c_int),
         "kmx_bow_score_pairs": ([P, i32, pi64, pu32, pf64, pi64, pu32, pf64, pf64], C.c_int),
+        "kmx_bow_reset": ([P, i32], C.c_int),
+        "kmx_bow_add_entries": ([P, i32, pi64, pu32, pf64, pi32], C.c_int),
+        "kmx_bow_add_from_voc": ([P, P, pi32, pi32], C.c_int),
+        "kmx_bow_seal": ([P], C.c_int),
+        "kmx_bow_set_tail_cap": ([P, i32], C.c_int),
+        "kmx_bow_info": ([P, pi32, pi32, pi32, pi32, pi64, pi64], C.c_int),
+        "kmx_bow_get_entries": ([P, i32, i32, pi64, pu32, pf64, i64], C.c_int),
+        "kmx_bow_query_entries": ([P, P, i32, pi32, pi32, i32, pi32, pi32, pf64], C.c_int),
+        "kmx_bow_query_entries_async": ([P, P, i32, pi32, pi32, i32], C.c_int),
+        "kmx_bow_fetch": ([P, i32, i32, pi32, pi32, pf64], C.c_int),
+        "kmx_bow_score_entries": ([P, i32, pi32, pi32, pf64], C.c_int),
         "kmx_voc_create": ([C.c_int, i32, pi32, pu8, pf64, i32, pi32, C.c_int, C.POINTER(P)], C.c_int),
         "kmx_voc_destroy": ([P], C.c_int),
         "kmx_voc_set_stream": ([P, P], C.c_int),

@@ -5,9 +5,18 @@ drawio:1565) on top of kmx_bow_* (C ABI, bow.hip):
 
   BowDatabase.query          DBoW2 Database::queryL1 (batched; GPU)
   BowDatabase.score_pairs    L1Scoring::score (the nss factor; GPU)
+  BowDatabase.add / add_transformed   DBoW2 Database::add, one keyframe or
+                             batch at a time: the vectors stay resident on
+                             the device (from host CSR, or straight from a
+                             GpuVocabulary's last transform)
+  BowDatabase.query_entries / score_entries   the same query / score with the
+                             vectors named by entry id (nothing uploaded)
   BowDetector.detectLoopWithRobot   nss vs the previous keyframe of the query
                              robot, min_nss_factor gate, max_db_results query,
                              alpha * nss cut, best result (batched)
+  BowDetector.add_vectors / add_frames / detectLoopResident /
+  detectLoopWithRobotResident   the streaming forms: keyframes are added as
+                             they arrive and detection runs by entry id
   BowDetector.detectLoop     single-robot stream: query with
                              max_id = frame - recent_frames_window, nss / alpha
                              cut, computeIslands, checkTemporalConstraint
@@ -62,6 +71,97 @@ class BowDatabase:
         self.n = vptr.shape[0] - 1
         check(self.L.kmx_bow_set_database(self.h, self.n_words, self.n, i64ptr(vptr), u32ptr(words),
                                           fptr(weights)), "kmx_bow_set_database")
+
+    # ---- streaming: Database::add, the vectors resident on the device
+    def reset(self):
+        """An empty database (the state set_entries of no vectors leaves)."""
+        check(self.L.kmx_bow_reset(self.h, self.n_words), "kmx_bow_reset")
+        self.n = 0
+
+    def add(self, vptr, words, weights) -> int:
+        """Database::add of each vector, in order -> the first new entry id."""
+        vptr, words, weights = _csr(vptr, words, weights)
+        first = C.c_int32(-1)
+        check(self.L.kmx_bow_add_entries(self.h, vptr.shape[0] - 1, i64ptr(vptr), u32ptr(words), fptr(weights),
+                                         C.byref(first)), "kmx_bow_add_entries")
+        self.n += vptr.shape[0] - 1
+        return first.value
+
+    def add_transformed(self, gpu_voc):
+        """Append the vectors gpu_voc's last transform / transform_async left on
+        the device (no host copy) -> (first new entry id, count)."""
+        first, n = C.c_int32(-1), C.c_int32(0)
+        check(self.L.kmx_bow_add_from_voc(self.h, gpu_voc.h, C.byref(first), C.byref(n)), "kmx_bow_add_from_voc")
+        self.n += n.value
+        return first.value, n.value
+
+    def seal(self):
+        """Move the unsealed tail into the inverted file now (on the device)."""
+        check(self.L.kmx_bow_seal(self.h), "kmx_bow_seal")
+
+    def set_tail_cap(self, cap: int):
+        check(self.L.kmx_bow_set_tail_cap(self.h, int(cap)), "kmx_bow_set_tail_cap")
+
+    def info(self) -> dict:
+        v = [C.c_int32() for _ in range(4)] + [C.c_int64(), C.c_int64()]
+        check(self.L.kmx_bow_info(self.h, *[C.byref(x) for x in v]), "kmx_bow_info")
+        return dict(zip(("n_words", "n_entries", "n_sealed", "tail_cap", "n_postings", "device_bytes"),
+                        (x.value for x in v)))
+
+    def lengths(self, first: int, n: int):
+        """Word counts of stored vectors [first, first + n) (no device access)."""
+        vptr = np.zeros(n + 1, np.int64)
+        check(self.L.kmx_bow_get_entries(self.h, first, n, i64ptr(vptr), None, None, 0), "kmx_bow_get_entries")
+        return np.diff(vptr)
+
+    def entries(self, first: int, n: int):
+        """Stored vectors [first, first + n) read back as CSR (vptr, words, weights)."""
+        vptr = np.zeros(n + 1, np.int64)
+        check(self.L.kmx_bow_get_entries(self.h, first, n, i64ptr(vptr), None, None, 0), "kmx_bow_get_entries")
+        tot = int(vptr[-1])
+        words, weights = np.zeros(max(tot, 1), np.uint32), np.zeros(max(tot, 1))
+        check(self.L.kmx_bow_get_entries(self.h, first, n, i64ptr(vptr), u32ptr(words), fptr(weights), tot),
+              "kmx_bow_get_entries")
+        return vptr, words[:tot], weights[:tot]
+
+    def query_entries(self, ids, max_results: int = 50, max_id=None, src=None):
+        """query with the query vectors taken from stored entries `ids` of
+        `src` (another BowDatabase on the same device; None: this one)."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        nq = ids.shape[0]
+        mid = None if max_id is None else np.ascontiguousarray(max_id, np.int32)
+        n = np.zeros(nq, np.int32)
+        out = np.full((nq, max_results), -1, np.int32)
+        sc = np.zeros((nq, max_results))
+        check(self.L.kmx_bow_query_entries(self.h, (src or self).h, nq, iptr(ids),
+                                           iptr(mid) if mid is not None else None, max_results, iptr(n), iptr(out),
+                                           fptr(sc)), "kmx_bow_query_entries")
+        return n, out, sc
+
+    def query_entries_async(self, ids, max_results: int = 50, max_id=None, src=None):
+        ids = np.ascontiguousarray(ids, np.int32)
+        mid = None if max_id is None else np.ascontiguousarray(max_id, np.int32)
+        self._keep = (ids, mid)
+        check(self.L.kmx_bow_query_entries_async(self.h, (src or self).h, ids.shape[0], iptr(ids),
+                                                 iptr(mid) if mid is not None else None, max_results),
+              "kmx_bow_query_entries_async")
+
+    def fetch(self, nq: int, max_results: int = 50):
+        """Results of the last query_async / query_entries_async (nq queries, same max_results)."""
+        n = np.zeros(nq, np.int32)
+        ids = np.full((nq, max_results), -1, np.int32)
+        sc = np.zeros((nq, max_results))
+        check(self.L.kmx_bow_fetch(self.h, nq, max_results, iptr(n), iptr(ids), fptr(sc)), "kmx_bow_fetch")
+        return n, ids, sc
+
+    def score_entries(self, a_ids, b_ids):
+        """L1 scores of pairs of stored entries; an id of -1 scores 0."""
+        a, b = np.ascontiguousarray(a_ids, np.int32), np.ascontiguousarray(b_ids, np.int32)
+        if a.shape != b.shape or a.ndim != 1:
+            raise ValueError("a_ids and b_ids must be 1-d and of the same length")
+        out = np.zeros(a.shape[0])
+        check(self.L.kmx_bow_score_entries(self.h, a.shape[0], iptr(a), iptr(b), fptr(out)), "kmx_bow_score_entries")
+        return out
 
     def query(self, qptr, words, weights, max_results: int = 50, max_id=None):
         """queryL1 of each query vector -> (n [nq], ids [nq, K], scores [nq, K])."""
@@ -235,6 +335,12 @@ class BowDetector:
             nss_tail = db.score_pairs(a, b)
         else:
             nss_tail = np.zeros(0)
+        return self._stream_decisions(fids, n, ids, sc, nss_tail)
+
+    def _stream_decisions(self, fids, n, ids, sc, nss_tail):
+        """detectLoop's sequential host control over the batched query results."""
+        p = self.p
+        nq = len(fids)
         tc = TemporalConstraint(p)
         out = []
         for q in range(nq):
@@ -263,3 +369,72 @@ class BowDetector:
                 continue
             out.append((fid, "LOOP_DETECTED", best.best_id, best.best_score))
         return out
+
+    # ---- streaming forms: keyframes are added as they arrive, detection runs by entry id
+    def _robot_db(self, robot: int) -> BowDatabase:
+        db = self.db.get(robot)
+        if db is None:
+            db = self.db[robot] = BowDatabase(self.n_words, self.device)
+            db.reset()
+        return db
+
+    def add_vectors(self, robot: int, vptr, words, weights):
+        """Database::add of BowVectors to `robot`'s database (created empty on
+        first use) -> the new entry ids."""
+        db = self._robot_db(robot)
+        first = db.add(vptr, words, weights)
+        return np.arange(first, db.n, dtype=np.int32)
+
+    def add_frames(self, robot: int, n_feats, desc):
+        """Transform frames (desc uint8 [F, N, 32], n_feats [F]) with the
+        detector's vocabulary and add their vectors to `robot`'s database; the
+        vectors go from the transform to the database on the device -> the
+        new entry ids."""
+        if self.vocabulary is None:
+            raise ValueError("BowDetector.add_frames needs a vocabulary (BowDetector(..., vocabulary=...))")
+        if self._gpu_voc is None:
+            from .vocabulary import GpuVocabulary
+            self._gpu_voc = GpuVocabulary(self.vocabulary, self.device)
+        db = self._robot_db(robot)
+        if len(n_feats) == 0:
+            return np.zeros(0, np.int32)
+        self._gpu_voc.transform_async(n_feats, desc)
+        first, n = db.add_transformed(self._gpu_voc)
+        return np.arange(first, first + n, dtype=np.int32)
+
+    def detectLoopResident(self, robot: int, first_frame: int, n_frames: int):
+        """detectLoop over entries first_frame .. first_frame + n_frames - 1 of
+        `robot`'s database, the queries and the nss factors taken by entry id:
+        the list detectLoop(robot, frames, first_frame) returns for the same
+        vectors."""
+        p = self.p
+        db = self.db[robot]
+        fids = np.arange(first_frame, first_frame + n_frames, dtype=np.int32)
+        max_id = np.maximum(fids - p.recent_frames_window, 0).astype(np.int32)
+        n, ids, sc = db.query_entries(fids, p.max_db_results, max_id)
+        nss_tail = db.score_entries(fids[1:], fids[:-1]) if n_frames > 1 else np.zeros(0)
+        return self._stream_decisions(fids, n, ids, sc, nss_tail)
+
+    def detectLoopWithRobotResident(self, robot: int, query_robot: int, query_ids):
+        """detectLoopWithRobot with the queries = entries `query_ids` of
+        `query_robot`'s database and prev = the entry before each (none for
+        id 0). Returns (match entry id or -1, score, nss)."""
+        p = self.p
+        db, src = self.db[robot], self.db[query_robot]
+        qids = np.ascontiguousarray(query_ids, np.int32)
+        nq = qids.shape[0]
+        prev = qids - 1
+        has_prev = prev >= 0
+        if has_prev.any():
+            lo = int(prev[has_prev].min())
+            ln = src.lengths(lo, int(prev.max()) - lo + 1)
+            has_prev[has_prev] = ln[prev[has_prev] - lo] > 0
+        nss = src.score_entries(qids, prev) if p.use_nss else np.ones(nq)
+        ok = has_prev & (nss >= p.min_nss_factor) if p.use_nss else np.ones(nq, bool)
+        n, ids, sc = db.query_entries(qids, p.max_db_results, src=src)
+        match = np.full(nq, -1, np.int32)
+        score = np.zeros(nq)
+        good = ok & (n > 0) & (sc[:, 0] >= p.alpha * nss)
+        match[good] = ids[good, 0]
+        score[good] = sc[good, 0]
+        return match, score, np.where(has_prev, nss, 0.0)
