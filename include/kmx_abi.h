@@ -151,6 +151,22 @@ int kmx_pgo_set_stream(kmx_pgo* h, void* hip_stream);
  * The environment variable KMX_POLL=0/1 at handle creation forces 0 / 1. */
 int kmx_pgo_set_tcg_poll(kmx_pgo* h, int mode);
 
+/* Robot groups of a round. Between the round-begin launch and the final commit
+ * a robot's block update reads its own rows and the public table only, so the
+ * handle cuts its local robots into contiguous groups of about equal incidence
+ * counts and runs each group's launches on a stream of its own (forked after
+ * the round begin, joined before the commit; the results are bitwise those of
+ * one group). In effect for the launched-reduction form (more than 80k local
+ * poses, or KMX_RED=0) with RTR in the standard tCG form and timing off.
+ * KMX_TCG_GROUPS=1/2/4 at handle creation sets the number asked for (default
+ * 2), clamped to the local robots that have poses.
+ * *groups: the groups the next round runs with (1: a single launch chain).
+ * bounds (may be NULL, else 5 entries): the cut of the current graph, whether
+ * in effect or not: group g holds the local robots [bounds[g], bounds[g + 1])
+ * (indices into the handle's local robots in team order); entries past the
+ * last group repeat the local robot count. */
+int kmx_pgo_get_tcg_groups(kmx_pgo* h, int* groups, int32_t* bounds);
+
 /* Native team exchange over RCCL (replaces the ROS topics public_poses +
  * status of dpgo_ros, drawio:2340-2375, for a team with one process per GPU).
  * Rank 0 calls kmx_comm_unique_id and hands the KMX_COMM_ID_BYTES bytes to

@@ -17,9 +17,11 @@
 //   * tCG in the linearity form: Hz by gather, delta = -z + beta delta_old,
 //     Hdelta = -Hz + beta Hdelta_old; eta = sum coef_k delta_k is folded from
 //     two kept directions every second step and finished in k_retract.
-//   * Edge data: one 72-B compact record per incidence in CSR order (unit
-//     quaternion of R, t, w kappa, +-w tau — the sign bit is the tail flag)
-//     plus its other endpoint in a 4-B array (Dev::rec_o), 76 B per incidence
+//   * Edge data: one 64-B compact record per incidence in CSR order (three
+//     components of R's unit quaternion, t, w kappa, +-w tau — the sign bit is
+//     the tail flag) plus a 4-B word (Dev::rec_o): its other endpoint and, in
+//     bits 29-31, the index of the quaternion's dropped largest component;
+//     68 B per incidence
 //     (struct Rec<10>); or a 128-B record with the full rotation when some
 //     measurement is not a rotation to 1e-12 (Rec<16>). The gathers are
 //     incidence-parallel:
@@ -152,6 +154,9 @@ struct alignas(16) TileDesc {
 
 struct Dev {
   int ntiles, L, nloc, npub;
+  // the tiles of this launch: [gt0, gt0 + gnt), all of them or one robot
+  // group's (kmx_pgo::grp); the grid is gnt workgroups
+  int gt0, gnt;
   const TileDesc* tile;
   const int* rtile0;   // [L+1]
   const int* inc_ptr;  // [nloc+1]
@@ -542,9 +547,9 @@ __device__ __forceinline__ Lane lane_map(const Dev& d) {
   // blocks b and b + 8 share an XCD, so each XCD gets one contiguous range of
   // tiles — about one robot block, whose rows then stay in that XCD's L2.
   {
-    const int nwg = d.ntiles, b = blockIdx.x;
+    const int nwg = d.gnt, b = blockIdx.x;
     const int q = nwg >> 3, rr = nwg & 7, x = b & 7;
-    L.tile = (x < rr ? x * (q + 1) : rr * (q + 1) + (x - rr) * q) + (b >> 3);
+    L.tile = d.gt0 + (x < rr ? x * (q + 1) : rr * (q + 1) + (x - rr) * q) + (b >> 3);
   }
   const TileDesc t = d.tile[L.tile];
   L.l = t.robot;
@@ -1223,14 +1228,14 @@ struct RobotSum {
 // The robot's state (256 B, into LDS) and its tile partials are loaded
 // together at the start, the control logic runs on the LDS copy and 32 lanes
 // write it back: no global round trip is serialised behind another.
-__global__ __launch_bounds__(RBLOCK) void k_reduce(Dev d, int kind, int R_, HostStatus* hs, unsigned long long seq,
-                                                  int slot, const double* src) {
+__global__ __launch_bounds__(RBLOCK) void k_reduce(Dev d, int first, int kind, int R_, HostStatus* hs,
+                                                  unsigned long long seq, int slot, const double* src) {
   constexpr int RW_ = RBLOCK / 64;
   constexpr int CW = sizeof(Ctl) / 8;
   static_assert(CW <= RBLOCK, "Ctl copy");
   __shared__ double lds[NPART * RW_];
   __shared__ Ctl cs;
-  const int l = blockIdx.x;
+  const int l = first + blockIdx.x;  // the launch's robots: [first, first + grid)
   if (threadIdx.x < CW)
     reinterpret_cast<double*>(&cs)[threadIdx.x] = reinterpret_cast<const double*>(d.ctl + l)[threadIdx.x];
   const int t0 = d.rtile0[l], t1 = d.rtile0[l + 1];
@@ -1350,7 +1355,10 @@ __device__ __forceinline__ void pose_precond(const Dev& d, int pose) {
 }
 
 // gated: the first gradient of a round whose begin launch may have re-weighted
-// (the k_precond launch folded in): block 0 commits the GNC state and, when
+// (the k_precond launch folded in): the workgroup of global tile 0 commits the
+// GNC state (of the launches over robot groups' tiles, only the one that holds
+// tile 0 does; no kernel between a round's k_begin and its final k_commit
+// reads d.gnc) and, when
 // the begin fired, every tile rebuilds D_i and the preconditioner of its own
 // poses (only its own incidence records are read) before the phase test, so
 // idle robots are rebuilt too. The writes are read back by the tile's own
@@ -1359,7 +1367,7 @@ template <int R, int RW, int RM>
 __device__ __forceinline__ void body_grad(const Dev& d, int gated, char* smem) {
   const Lane L = lane_map<R>(d);
   if (gated) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) store_gnc(d.gnc, load_gnc(d.gnc_next));
+    if (L.tile == 0 && threadIdx.x == 0) store_gnc(d.gnc, load_gnc(d.gnc_next));
     if (d.gnc_next->fired) {
       const int np = L.np, p0 = L.p0;
       for (int t = threadIdx.x; t < np; t += blockDim.x) pose_precond<RW>(d, p0 + t);
@@ -2809,16 +2817,6 @@ struct kmx_pgo {
   ncclComm_t comm = nullptr;
   int world = 1, rank = 0;
   bool xchg = false, xchg_self_p2p = false;
-  // KMX_XCHG_LAG=1 (a measurement mode, off by default):
-  // the exchange of the rows published after round i-1 runs on xstream while
-  // round i computes, and round i+1 installs them — a one-round-stale public
-  // table (round k >= 2 reads the peers' rows of X^(k-2)). It changes the
-  // iterate sequence and lets the ranks' GNC decisions drift apart (a peer's
-  // status word is a round older too), so it is a timing instrument only.
-  int xchg_lag = 0;
-  bool x_inflight = false;
-  hipStream_t xstream = nullptr;
-  hipEvent_t ev_xg = nullptr, ev_xd = nullptr;
   int *d_xs_slots = nullptr, *d_xr_slots = nullptr, *d_xs_seg = nullptr, *d_xr_seg = nullptr;
   int *d_xs_rseg = nullptr, *d_xr_rseg = nullptr;  // segment index of every row
   double *d_xsbuf = nullptr, *d_xrbuf = nullptr;
@@ -2826,6 +2824,30 @@ struct kmx_pgo {
   std::vector<long long> xs_cnt, xr_cnt, xs_off, xr_off;  // per peer, in doubles (rows * 4r + 1 status)
   int blind_left = 0;
   static constexpr int BLIND_SLACK = 2, BLIND_WINDOW = 8;
+  // Robot groups (KMX_TCG_GROUPS = 1, 2 or 4; default 2): between a round's
+  // k_begin and its final k_commit a robot's launches read only its own rows
+  // and the public table, which changes only in that k_commit (DESIGN.md
+  // section 13), so the local robots are cut into contiguous groups of about
+  // equal incidence counts and each group's launch chain (k_grad, the tCG
+  // steps, k_retract, k_cost and their k_reduce launches, over the group's
+  // tiles and robots) runs on a stream of its own: group 0 on the handle's
+  // stream, group g > 0 on gstream[g - 1], forked by an event after k_begin
+  // and joined by one event per side stream before the final k_commit. One
+  // group's k_reduce launches, ramps and tails then run under another group's
+  // bandwidth-bound kernels. The arithmetic of a robot does not depend on
+  // the grouping (its tiles and the order of its tile partials are the same).
+  // In effect for RM_LAUNCH and RTR only, and not while timing is on (the
+  // evented replay wants launches that do not overlap).
+  static constexpr int MAX_GROUPS = 4;
+  struct Group {
+    int l0 = 0, l1 = 0;  // local robots [l0, l1)
+    int t0 = 0, nt = 0;  // their tiles [t0, t0 + nt)
+    int blind_left = 0;  // the group's own adaptive polling state
+  };
+  int groups_req = 2;
+  std::vector<Group> grp;  // the cut of the current graph (one group: no fork)
+  hipStream_t gstream[MAX_GROUPS - 1] = {nullptr, nullptr, nullptr};
+  hipEvent_t ev_fork = nullptr, ev_join[MAX_GROUPS - 1] = {nullptr, nullptr, nullptr};
   // Gated k_hess launches (KMX_HESS_GATE=0: off): every k_hess launch after a
   // tCG's first tests its robot's phase before its first record chunk is
   // fetched. Ungated, a launch enqueued before the host knows whether any robot
@@ -2923,8 +2945,6 @@ int dalloc(T** p, size_t count) {
 }
 
 void free_xchg(kmx_pgo* h) {
-  if (h->xstream) (void)hipStreamSynchronize(h->xstream);
-  h->x_inflight = false;
   void* ptrs[] = {h->d_xs_slots, h->d_xr_slots, h->d_xs_seg, h->d_xr_seg, h->d_xs_rseg, h->d_xr_rseg,
                   h->d_xsbuf, h->d_xrbuf};
   for (void* q : ptrs)
@@ -3055,12 +3075,22 @@ void enqueue_precond(kmx_pgo* h, int gated) {
 // preconditioner rebuild that commits the GNC state.
 // Returns whether the gated preconditioner rebuild is left to the next k_grad
 // (defer: the round's first gradient follows this launch directly).
-bool enqueue_begin(kmx_pgo* h, const unsigned char* d_active, int mode, bool defer = false) {
+// done: an event that completes with the begin launch itself (the dispatch's
+// own completion signal: no marker packet on the stream behind it).
+bool enqueue_begin(kmx_pgo* h, const unsigned char* d_active, int mode, bool defer = false,
+                   hipEvent_t done = nullptr) {
   const bool may_fire = h->P.robust_cost == KMX_COST_GNC_TLS && (h->gnc_on || (mode & BEGIN_FORCE_GNC));
   if (!may_fire) mode |= BEGIN_SOLO;  // no weight update possible: one block, no preconditioner rebuild
   // a capped grid: when the schedule does not fire, the launch costs its dispatch
   const unsigned grid = may_fire ? 1 + (unsigned)std::min(256, std::max(1, (h->n_gnc + 255) / 256)) : 1;
-  if (h->rw == 10)
+  if (done) {
+    if (h->rw == 10)
+      hipExtLaunchKernelGGL(k_begin<10>, dim3(grid), dim3(256), 0, h->stream, nullptr, done, 0u, h->dv, d_active, mode,
+                            h->P.r);
+    else
+      hipExtLaunchKernelGGL(k_begin<16>, dim3(grid), dim3(256), 0, h->stream, nullptr, done, 0u, h->dv, d_active, mode,
+                            h->P.r);
+  } else if (h->rw == 10)
     hipLaunchKernelGGL(k_begin<10>, dim3(grid), dim3(256), 0, h->stream, h->dv, d_active, mode, h->P.r);
   else
     hipLaunchKernelGGL(k_begin<16>, dim3(grid), dim3(256), 0, h->stream, h->dv, d_active, mode, h->P.r);
@@ -3068,14 +3098,14 @@ bool enqueue_begin(kmx_pgo* h, const unsigned char* d_active, int mode, bool def
   return may_fire && defer;
 }
 
-// Wait until every robot with tiles reported tCG step `seq`; returns whether
-// any robot is still in tCG. A device that stops reporting for 30 s switches
-// the handle to blind enqueueing (every tCG step launched).
-bool wait_running(kmx_pgo* h, unsigned long long seq) {
+// Wait until every robot of [l0, l1) with tiles reported tCG step `seq`;
+// returns whether any of them is still in tCG. A device that stops reporting
+// for 30 s switches the handle to blind enqueueing (every tCG step launched).
+bool wait_running(kmx_pgo* h, unsigned long long seq, int l0, int l1) {
   volatile HostStatus* hs = h->hstat;
   const auto t0 = std::chrono::steady_clock::now();
   bool running = false;
-  for (int l = 0; l < h->dv.L; ++l) {
+  for (int l = l0; l < l1; ++l) {
     if (h->rt0_h[l + 1] == h->rt0_h[l]) continue;  // no tiles: never in tCG
     unsigned long long w;
     while (((w = __atomic_load_n(&hs[l].word, __ATOMIC_ACQUIRE)) >> 1) < seq) {
@@ -3093,7 +3123,39 @@ bool wait_running(kmx_pgo* h, unsigned long long seq) {
 template <int R, int RM>
 void red_t(kmx_pgo* h, int kind, HostStatus* hs = nullptr, unsigned long long seq = 0, int slot = -1,
            const double* src = nullptr) {
-  hipLaunchKernelGGL(k_reduce, dim3(h->dv.L), dim3(RBLOCK), 0, h->stream, h->dv, kind, R, hs, seq, slot, src);
+  hipLaunchKernelGGL(k_reduce, dim3(h->dv.L), dim3(RBLOCK), 0, h->stream, h->dv, 0, kind, R, hs, seq, slot, src);
+}
+
+// Robot groups in effect for the next round (kmx_pgo::grp; 1: today's single
+// launch chain).
+int groups_in_effect(const kmx_pgo* h) {
+  if (h->timing || h->rm != RM_LAUNCH || h->P.method != KMX_METHOD_RTR || onesync(h)) return 1;
+  return std::max<int>(1, (int)h->grp.size());
+}
+
+// One group's view of the round: its stream and a Dev whose launches cover
+// the group's tiles; k_reduce over the group's robots.
+struct GroupLaunch {
+  Dev d;
+  hipStream_t s;
+  int l0, nl;
+};
+GroupLaunch group_launch(kmx_pgo* h, int g) {
+  const kmx_pgo::Group& G = h->grp[g];
+  GroupLaunch q{h->dv, g == 0 ? h->stream : h->gstream[g - 1], G.l0, G.l1 - G.l0};
+  q.d.gt0 = G.t0;
+  q.d.gnt = G.nt;
+  return q;
+}
+template <int R>
+void red_g(const GroupLaunch& q, int kind, HostStatus* hs = nullptr, unsigned long long seq = 0,
+           hipEvent_t done = nullptr) {
+  if (done)  // the event completes with this dispatch
+    hipExtLaunchKernelGGL(k_reduce, dim3(q.nl), dim3(RBLOCK), 0, q.s, nullptr, done, 0u, q.d, q.l0, kind, R, hs, seq, -1,
+                          (const double*)nullptr);
+  else
+    hipLaunchKernelGGL(k_reduce, dim3(q.nl), dim3(RBLOCK), 0, q.s, q.d, q.l0, kind, R, hs, seq, -1,
+                       (const double*)nullptr);
 }
 
 // The parts of a round: gradient, tCG (host-polled steps), trial point and
@@ -3161,7 +3223,7 @@ void enqueue_tcg_t(kmx_pgo* h) {
         else
           hipLaunchKernelGGL((k_step<R, RW>), grid, blk, SmemF<R>::bytes, h->stream, h->dv, cin, cout, j,
                              slot, hs, seq);
-        if (poll && j > 0 && !wait_running(h, seq)) {
+        if (poll && j > 0 && !wait_running(h, seq, 0, h->dv.L)) {
           J = j + 1;
           break;
         }
@@ -3194,7 +3256,7 @@ void enqueue_tcg_t(kmx_pgo* h) {
         hipLaunchKernelGGL((k_hess<R, RW, RM>), grid, blk, SmemH<R>::bytes, h->stream, h->dv, fl, slot,
                            hs, seq);
       hipLaunchKernelGGL((k_update<R, RM>), grid, blk, SmemU::bytes, h->stream, h->dv, nullptr, 0ull, slot);
-      if (poll && j > 0 && !wait_running(h, seq)) {
+      if (poll && j > 0 && !wait_running(h, seq, 0, h->dv.L)) {
         steps = j + 1;
         h->tcg_stopped = true;
         break;
@@ -3210,7 +3272,7 @@ void enqueue_tcg_t(kmx_pgo* h) {
     hipLaunchKernelGGL((k_update<R, RM>), grid, blk, SmemU::bytes, h->stream, h->dv, nullptr, seq, -1);
     red_t<R, RM>(h, RED_UPDATE, hs, seq, -1, nullptr);
     if (poll) {
-      if (j > 0 && !wait_running(h, prev)) {
+      if (j > 0 && !wait_running(h, prev, 0, h->dv.L)) {
         steps = j + 1;
         break;
       }
@@ -3242,8 +3304,99 @@ void enqueue_trial_t(kmx_pgo* h, bool rgd) {
   if (!fold_cost<RM>(h)) red_t<R, RM>(h, RED_COST);
 }
 
+// The round with robot groups (kmx_pgo::grp, RM_LAUNCH and RTR): k_begin on
+// the handle's stream, then every group's chain on its own stream, enqueued
+// launch by launch across the groups so no stream runs dry while the host
+// serves another, and the final k_commit of all robots behind the join (it
+// writes the public rows the other groups' k_grad / k_cost read). The tCG
+// loop polls per group: a group whose robots have all left tCG is no longer
+// enqueued while the others go on.
+template <int R, int RW>
+void enqueue_round_groups_t(kmx_pgo* h, const unsigned char* d_active) {
+  constexpr int RM = RM_LAUNCH;
+  const int G = (int)h->grp.size();
+  const dim3 blk(BLOCK);
+  // fork: the begin launch's own completion is the event the side streams wait
+  // for, and join: each side stream's last launch (the trial cost's k_reduce)
+  // carries the event the final commit waits for. Neither puts a marker on the
+  // stream it is recorded on, so group 0's k_grad follows k_begin directly.
+  const bool pend = enqueue_begin(h, d_active, BEGIN_ROUND, true, h->ev_fork);
+  GroupLaunch q[kmx_pgo::MAX_GROUPS];
+  for (int g = 0; g < G; ++g) q[g] = group_launch(h, g);
+  // (an event call's error is left to the caller's hipGetLastError, as a launch's)
+  for (int g = 1; g < G; ++g) (void)hipStreamWaitEvent(q[g].s, h->ev_fork, 0);
+  const int iters = h->P.rtr_iterations, tmax = h->P.tcg_max_iterations;
+  for (int it = 0; it < iters; ++it) {
+    for (int g = 0; g < G; ++g) {
+      hipLaunchKernelGGL((k_grad<R, RW, RM>), dim3(q[g].d.gnt), blk, SmemHG<R>::bytes, q[g].s, q[g].d,
+                         it == 0 && pend ? 1 : 0);
+      red_g<R>(q[g], RED_GRAD);
+    }
+    // tCG, as enqueue_tcg_t's RM_LAUNCH loop, with each group's own polling state
+    bool poll[kmx_pgo::MAX_GROUPS], live[kmx_pgo::MAX_GROUPS];
+    unsigned long long prev[kmx_pgo::MAX_GROUPS], seq[kmx_pgo::MAX_GROUPS];
+    int steps[kmx_pgo::MAX_GROUPS];
+    for (int g = 0; g < G; ++g) {
+      poll[g] = h->poll && h->hstat;
+      if (poll[g] && h->poll_auto && h->grp[g].blind_left > 0) {
+        --h->grp[g].blind_left;
+        poll[g] = false;
+      }
+      live[g] = true;
+      prev[g] = seq[g] = 0;
+      steps[g] = tmax;
+    }
+    for (int j = 0; j < tmax; ++j) {
+      bool any = false;
+      for (int g = 0; g < G; ++g) {
+        if (!live[g]) continue;
+        any = true;
+        poll[g] = poll[g] && h->poll;  // a poll timeout inside wait_running switches to blind
+        seq[g] = poll[g] ? ++h->seq : 0;
+        HostStatus* hs = poll[g] ? h->hstat : nullptr;
+        const int fl = (j == 0 ? 1 : 0) | (j > 0 && h->hess_gate ? 2 : 0);
+        const dim3 grid(q[g].d.gnt);
+        hipLaunchKernelGGL((k_hess<R, RW, RM>), grid, blk, SmemH<R>::bytes, q[g].s, q[g].d, fl, -1,
+                           (HostStatus*)nullptr, 0ull);
+        red_g<R>(q[g], RED_HESS);
+        hipLaunchKernelGGL((k_update<R, RM>), grid, blk, SmemU::bytes, q[g].s, q[g].d, (HostStatus*)nullptr,
+                           seq[g], -1);
+        red_g<R>(q[g], RED_UPDATE, hs, seq[g]);
+      }
+      if (!any) break;
+      for (int g = 0; g < G; ++g) {
+        if (!live[g] || !poll[g]) continue;
+        if (j > 0 && !wait_running(h, prev[g], h->grp[g].l0, h->grp[g].l1)) {
+          steps[g] = j + 1;
+          live[g] = false;
+        }
+        prev[g] = seq[g];
+      }
+    }
+    for (int g = 0; g < G; ++g)
+      if (poll[g] && h->poll_auto && steps[g] + kmx_pgo::BLIND_SLACK >= tmax)
+        h->grp[g].blind_left = kmx_pgo::BLIND_WINDOW;
+    for (int g = 0; g < G; ++g) {
+      const dim3 grid(q[g].d.gnt);
+      hipLaunchKernelGGL((k_retract<R>), grid, blk, SmemU::bytes, q[g].s, q[g].d, 0, (const Ctl*)h->d_ctl);
+      hipLaunchKernelGGL((k_cost<R, RW, RM>), grid, blk, SmemC<R>::bytes, q[g].s, q[g].d, (const Ctl*)h->d_ctl);
+      red_g<R>(q[g], RED_COST, nullptr, 0, g > 0 && it + 1 == iters ? h->ev_join[g - 1] : nullptr);
+      if (it + 1 < iters)  // the next RTR iteration starts from the accepted point: the robot's own X only
+        hipLaunchKernelGGL((k_commit<R>), grid, blk, 0, q[g].s, q[g].d, 0, 0);
+    }
+  }
+  for (int g = 1; g < G; ++g) (void)hipStreamWaitEvent(h->stream, h->ev_join[g - 1], 0);
+  hipLaunchKernelGGL((k_commit<R>), dim3(h->ntiles), blk, 0, h->stream, h->dv, 0, 1);
+}
+
 template <int R, int RW, int RM>
 void enqueue_round_t(kmx_pgo* h, const unsigned char* d_active) {
+  if constexpr (RM == RM_LAUNCH) {
+    if (groups_in_effect(h) > 1) {
+      enqueue_round_groups_t<R, RW>(h, d_active);
+      return;
+    }
+  }
   // no tiles: nothing would run the deferred rebuild
   const bool pend = enqueue_begin(h, d_active, BEGIN_ROUND, h->ntiles > 0);
   const bool rgd = h->P.method == KMX_METHOD_RGD;
@@ -3374,6 +3527,20 @@ extern "C" int kmx_pgo_create(const kmx_pgo_params* params, int device, kmx_pgo*
     h->rm_forced = m == 0 ? RM_LAUNCH : m == 2 ? RM_CONSUMER : -1;  // 1 and 3 (tickets, half) were removed
   }
   if (const char* v = std::getenv("KMX_HESS_GATE")) h->hess_gate = std::atoi(v) != 0;
+  if (const char* v = std::getenv("KMX_TCG_GROUPS")) {
+    const int g = std::atoi(v);
+    h->groups_req = g >= 4 ? 4 : g >= 2 ? 2 : 1;
+  }
+  // the side streams of the robot groups (group 0 runs on the handle's stream)
+  for (int g = 1; g < h->groups_req && e == hipSuccess; ++g) {
+    e = hipStreamCreateWithFlags(&h->gstream[g - 1], hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreate(&h->ev_join[g - 1]);
+  }
+  if (e == hipSuccess && h->groups_req > 1) e = hipEventCreate(&h->ev_fork);
+  if (e != hipSuccess) {
+    (void)kmx_pgo_destroy(h);
+    return kmx::fail(KMX_EHIP, std::string("robot group streams: ") + hipGetErrorString(e));
+  }
   *out = h;
   return KMX_OK;
   KMX_GUARD_END
@@ -3383,17 +3550,19 @@ extern "C" int kmx_pgo_destroy(kmx_pgo* h) {
   if (!h) return KMX_OK;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
+  for (hipStream_t s : h->gstream)
+    if (s) (void)hipStreamSynchronize(s);
   free_dev(h);
   free_xchg(h);
   if (h->comm) (void)ncclCommAbort(h->comm);  // non-blocking communicator: no finalize handshake at teardown
   for (auto e : h->ev_pool) (void)hipEventDestroy(e);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   if (h->hstat) (void)hipHostFree(h->hstat);
-  if (h->xstream) {
-    (void)hipStreamDestroy(h->xstream);
-    (void)hipEventDestroy(h->ev_xg);
-    (void)hipEventDestroy(h->ev_xd);
-  }
+  for (hipStream_t s : h->gstream)
+    if (s) (void)hipStreamDestroy(s);
+  for (hipEvent_t ev : h->ev_join)
+    if (ev) (void)hipEventDestroy(ev);
+  if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   delete h;
   return KMX_OK;
 }
@@ -3416,6 +3585,18 @@ extern "C" int kmx_pgo_set_tcg_poll(kmx_pgo* h, int mode) {
   h->poll = mode != 0;
   h->poll_auto = mode == -1;
   h->blind_left = 0;
+  for (auto& g : h->grp) g.blind_left = 0;
+  return KMX_OK;
+}
+
+extern "C" int kmx_pgo_get_tcg_groups(kmx_pgo* h, int* groups, int32_t* bounds) {
+  KMX_CHECK(h && groups, KMX_EINVAL, "null argument");
+  *groups = ready(h) ? groups_in_effect(h) : 1;
+  if (bounds) {  // the cut of the current graph, also while it is not in effect
+    const int G = ready(h) ? (int)h->grp.size() : 0;
+    for (int g = 0; g <= kmx_pgo::MAX_GROUPS; ++g)
+      bounds[g] = g < G ? h->grp[g].l0 : G > 0 ? h->grp[G - 1].l1 : 0;
+  }
   return KMX_OK;
 }
 
@@ -3667,6 +3848,40 @@ extern "C" int kmx_pgo_set_graph(kmx_pgo* h, int n_robots, const int32_t* n_pose
   h->rt0_h = rt0;
   h->ntiles = (int)tr.size();
   KMX_CHECK(h->ntiles > 0, KMX_EINVAL, "no local poses");
+  {
+    // robot groups: contiguous robot ranges, at most as many as robots have
+    // tiles, cut where the incidence prefix is nearest to g / G of the total
+    // (every group keeps a robot with tiles); a robot without tiles belongs to
+    // the group its index falls in and launches nothing
+    std::vector<int64_t> pre(L + 1, 0);
+    std::vector<int> tiled(L + 1, 0);  // robots with tiles before l
+    for (int l = 0; l < L; ++l) {
+      const int n = n_poses[h->robots[l]], base = h->loff[l];
+      pre[l + 1] = pre[l] + ((int64_t)inc_ptr[base + n] - inc_ptr[base]);
+      tiled[l + 1] = tiled[l] + (rt0[l + 1] > rt0[l] ? 1 : 0);
+    }
+    const int G = std::max(1, std::min(h->groups_req, tiled[L]));
+    std::vector<int> start(G + 1, 0);
+    start[G] = L;
+    for (int g = 1; g < G; ++g) {
+      int best = -1;
+      for (int c = start[g - 1] + 1; c < L; ++c) {
+        // a tiled robot in [start[g - 1], c), and G - g of them left in [c, L)
+        if (tiled[c] == tiled[start[g - 1]] || tiled[L] - tiled[c] < G - g) continue;
+        const int64_t dc = std::llabs(G * pre[c] - g * pre[L]);
+        if (best < 0 || dc < std::llabs(G * pre[best] - g * pre[L])) best = c;
+      }
+      start[g] = best;
+    }
+    h->grp.assign(G, kmx_pgo::Group{});
+    for (int g = 0; g < G; ++g) {
+      kmx_pgo::Group& q = h->grp[g];
+      q.l0 = start[g];
+      q.l1 = start[g + 1];
+      q.t0 = rt0[q.l0];
+      q.nt = rt0[q.l1] - rt0[q.l0];
+    }
+  }
   std::vector<int> own_src(std::max<int64_t>(h->n_owned, 1), 0);
   for (int64_t k = 0; k < h->n_owned; ++k) own_src[k] = pub_src[h->first_owned + k];
   std::vector<int> nrob(L);
@@ -3778,6 +3993,7 @@ extern "C" int kmx_pgo_set_graph(kmx_pgo* h, int n_robots, const int32_t* n_pose
   Dev& d = h->dv;
   d = Dev{};
   d.ntiles = h->ntiles; d.L = L; d.nloc = nloc; d.npub = (int)h->npub;
+  d.gt0 = 0; d.gnt = h->ntiles;
   d.tile = h->d_tile; d.rtile0 = h->d_rtile0;
   d.inc_ptr = h->d_inc_ptr; d.rec = h->d_rec; d.rec_o = h->d_rec_o;
   d.ekappa = h->d_ekappa; d.etau = h->d_etau; d.ew = h->d_ew; d.eipos = h->d_eipos;
@@ -3944,10 +4160,8 @@ int nccl_settle(kmx_pgo* h, ncclResult_t r, const char* what) {
 // one group on the handle's stream, then the received rows land in the public
 // table and the peers' status words in ext. Segment layout as
 // kmx_pgo_exchange_pack / _unpack.
-int enqueue_exchange_lag(kmx_pgo* h);
 int enqueue_exchange(kmx_pgo* h) {
   if (!h->xchg) return KMX_OK;
-  if (h->xchg_lag) return enqueue_exchange_lag(h);
   const int ps = 4 * h->P.r, W = h->world;
   const long long ts = h->xn_send * ps + W, tr = h->xn_recv * ps + W;
   hipLaunchKernelGGL(k_xgather, dim3((unsigned)((ts + 255) / 256)), dim3(256), 0, h->stream, h->d_vec,
@@ -3967,59 +4181,6 @@ int enqueue_exchange(kmx_pgo* h) {
                            sizeof(double) * h->xs_cnt[h->rank], hipMemcpyDeviceToDevice, h->stream));
   hipLaunchKernelGGL(k_xscatter, dim3((unsigned)((tr + 255) / 256)), dim3(256), 0, h->stream, h->d_pub,
                      h->d_xr_slots, h->d_xr_rseg, h->xn_recv, (const double*)h->d_xrbuf, ps, h->d_xr_seg, W, h->d_ext);
-  if (h->n_ext != W) {
-    h->n_ext = W;
-    sync_params(h);
-  }
-  KMX_HIP(hipGetLastError());
-  return KMX_OK;
-}
-
-// KMX_XCHG_LAG: the previous round's exchange (done on xstream while that
-// round computed) is installed, then this round's rows are gathered and sent
-// on xstream behind an event, and the round runs without waiting for them.
-// The first round of a sequence waits (round 1 reads X^0 as in the in-round
-// form). The send / receive buffers need no second copy: the scatter of
-// exchange i-1 and the gather of exchange i both wait for exchange i-1 to
-// finish, and exchange i starts after both.
-int enqueue_exchange_lag(kmx_pgo* h) {
-  const int ps = 4 * h->P.r, W = h->world;
-  const long long ts = h->xn_send * ps + W, tr = h->xn_recv * ps + W;
-  if (!h->xstream) {
-    KMX_HIP(hipStreamCreateWithFlags(&h->xstream, hipStreamNonBlocking));
-    KMX_HIP(hipEventCreateWithFlags(&h->ev_xg, hipEventDisableTiming));
-    KMX_HIP(hipEventCreateWithFlags(&h->ev_xd, hipEventDisableTiming));
-  }
-  auto scatter = [&]() {
-    hipLaunchKernelGGL(k_xscatter, dim3((unsigned)((tr + 255) / 256)), dim3(256), 0, h->stream, h->d_pub,
-                       h->d_xr_slots, h->d_xr_rseg, h->xn_recv, (const double*)h->d_xrbuf, ps, h->d_xr_seg, W,
-                       h->d_ext);
-  };
-  if (h->x_inflight) {
-    KMX_HIP(hipStreamWaitEvent(h->stream, h->ev_xd, 0));
-    scatter();
-  }
-  hipLaunchKernelGGL(k_xgather, dim3((unsigned)((ts + 255) / 256)), dim3(256), 0, h->stream, h->d_vec,
-                     h->d_pub_src, h->d_xs_slots, h->d_xs_rseg, h->xn_send, h->d_xsbuf, ps, h->d_xs_seg, W,
-                     (const double*)h->d_relc, h->dv.L);
-  KMX_HIP(hipEventRecord(h->ev_xg, h->stream));
-  KMX_HIP(hipStreamWaitEvent(h->xstream, h->ev_xg, 0));
-  KMX_NCCL(ncclGroupStart());
-  for (int q = 0; q < W; ++q) {
-    if (q == h->rank && !h->xchg_self_p2p) continue;
-    KMX_NCCL(ncclSend(h->d_xsbuf + h->xs_off[q], (size_t)h->xs_cnt[q], ncclDouble, q, h->comm, h->xstream));
-    KMX_NCCL(ncclRecv(h->d_xrbuf + h->xr_off[q], (size_t)h->xr_cnt[q], ncclDouble, q, h->comm, h->xstream));
-  }
-  if (int rc = nccl_settle(h, ncclGroupEnd(), "ncclGroupEnd")) return rc;
-  if (!h->xchg_self_p2p)
-    KMX_HIP(hipMemcpyAsync(h->d_xrbuf + h->xr_off[h->rank], h->d_xsbuf + h->xs_off[h->rank],
-                           sizeof(double) * h->xs_cnt[h->rank], hipMemcpyDeviceToDevice, h->xstream));
-  KMX_HIP(hipEventRecord(h->ev_xd, h->xstream));
-  if (!h->x_inflight) {  // the first round: its own exchange's rows
-    KMX_HIP(hipStreamWaitEvent(h->stream, h->ev_xd, 0));
-    scatter();
-  }
-  h->x_inflight = true;
   if (h->n_ext != W) {
     h->n_ext = W;
     sync_params(h);
@@ -4094,7 +4255,6 @@ extern "C" int kmx_pgo_comm_init(kmx_pgo* h, const void* unique_id, int world, i
   h->world = world;
   h->rank = rank;
   if (const char* v = std::getenv("KMX_XCHG_SELF_P2P")) h->xchg_self_p2p = std::atoi(v) != 0;
-  if (const char* v = std::getenv("KMX_XCHG_LAG")) h->xchg_lag = std::atoi(v) != 0;
   return KMX_OK;
   KMX_GUARD_END
 }
@@ -4129,7 +4289,6 @@ extern "C" int kmx_pgo_sync_timeout(kmx_pgo* h, double timeout_s) {
   const auto t0 = std::chrono::steady_clock::now();
   for (;;) {
     hipError_t e = hipStreamQuery(h->stream);
-    if (e == hipSuccess && h->xstream) e = hipStreamQuery(h->xstream);  // a lagged exchange in flight
     if (e == hipSuccess) return KMX_OK;
     if (e != hipErrorNotReady) return kmx::fail(KMX_EHIP, std::string("hipStreamQuery: ") + hipGetErrorString(e));
     if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > timeout_s)
@@ -4326,7 +4485,6 @@ extern "C" int kmx_pgo_sync(kmx_pgo* h) {
   KMX_CHECK(h, KMX_EINVAL, "null handle");
   KMX_HIP(hipSetDevice(h->device));
   KMX_HIP(hipStreamSynchronize(h->stream));
-  if (h->xstream) KMX_HIP(hipStreamSynchronize(h->xstream));
   return KMX_OK;
 }
 

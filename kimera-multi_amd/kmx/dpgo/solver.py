@@ -58,6 +58,24 @@ class BlockSolver:
         (kmx_pgo_set_tcg_poll; identical results in every mode)."""
         check(self.L.kmx_pgo_set_tcg_poll(self.h, int(mode)), "kmx_pgo_set_tcg_poll")
 
+    def tcg_groups(self) -> int:
+        """Robot groups the next round runs with (kmx_pgo_get_tcg_groups; 1: a
+        single launch chain)."""
+        g = C.c_int()
+        check(self.L.kmx_pgo_get_tcg_groups(self.h, C.byref(g), None), "kmx_pgo_get_tcg_groups")
+        return g.value
+
+    def tcg_group_bounds(self) -> list[int]:
+        """The cut of the local robots into groups: group g holds the local
+        robots [b[g], b[g + 1])."""
+        g = C.c_int()
+        b = (C.c_int32 * 5)()
+        check(self.L.kmx_pgo_get_tcg_groups(self.h, C.byref(g), b), "kmx_pgo_get_tcg_groups")
+        out = list(b)
+        while len(out) > 2 and out[-1] == out[-2]:
+            out.pop()
+        return out
+
     # ------------------------------------------------- native exchange ---
     native_exchange = True  # kmx_pgo_comm_init / kmx_pgo_set_exchange (RCCL inside the round)
 

@@ -84,13 +84,10 @@ print(f"N={N}: rank 0 holds robots {lo}..{hi - 1}, {int(g.n_poses[lo:hi].sum())}
       f"sends {n_send} rows, receives {n_recv} rows ({n_recv * ps * 8 / 1e6:.2f} MB) per round; "
       f"adaptive tCG enqueueing, {P.localOptimizationParams.tCG_form} tCG", flush=True)
 
-modes = ("batch", "seam", "native", "lagged") if os.environ.get("KMX_SEAM_LAG") else ("batch", "seam", "native")
-for mode in modes:
+for mode in ("batch", "seam", "native"):
     s = make()
-    if mode in ("native", "lagged"):
+    if mode == "native":
         os.environ["KMX_XCHG_SELF_P2P"] = "1"
-        # lagged: the one-round-stale exchange (KMX_XCHG_LAG, pgo.hip enqueue_exchange_lag) on its own stream
-        os.environ["KMX_XCHG_LAG"] = "1" if mode == "lagged" else "0"
         k = min(n_send, n_recv)
         s.comm_init(s.comm_unique_id(), 1, 0)
         s.set_exchange(ss[:k], [k], rs[:k], [k])
@@ -108,7 +105,7 @@ for mode in modes:
     s.read_counters()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    if mode in ("batch", "native", "lagged"):
+    if mode in ("batch", "native"):
         s.iterate_async(n_rounds, refresh_local=False)
     else:
         for _ in range(n_rounds):
