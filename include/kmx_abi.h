@@ -700,6 +700,70 @@ int kmx_voc_sync(kmx_voc* h);
 int kmx_voc_enable_timing(kmx_voc* h, int enable);
 int kmx_voc_read_timing(kmx_voc* h, double* descend_ms, double* reduce_ms);
 
+/* ------------------------------------------------------------------------- */
+/* Chordal initialisation of a batch of pose graphs (dpgo's local
+ * initialisation method Chordal [U: dpgo is not vendored; restated from the
+ * SE-Sync chordal relaxation]; the problem kmx.dpgo.init.chordal_initialization
+ * solves on the host). Additive to ABI 10, like kmx_pgo_get_tcg_groups.
+ * Poses 0..n-1 are cut into n_blocks contiguous blocks (a robot each; one block
+ * over everything is a centralised solve). An edge (i, j, R_ij, t_ij, kappa,
+ * tau, w) means R_j = R_i R_ij, t_j = t_i + R_i t_ij; both ends lie in one
+ * block. Anchors are held at R = I, t = 0.
+ *   1. minimise sum w kappa |X_j - X_i R_ij|_F^2 over unconstrained 3x3 blocks;
+ *   2. project every free block to SO(3) (SVD, determinant fix on the smallest
+ *      singular direction);
+ *   3. minimise sum w tau |t_j - t_i - R_i t_ij|^2 with those rotations.
+ * Steps 1 and 3 are Jacobi-preconditioned conjugate gradients, one per block
+ * and per right-hand side (the three rows of X, the three components of t):
+ * the stop test |r| <= rtol |b| and the iteration count are per (block, row),
+ * so a block's result does not depend on the other blocks of the batch. Two
+ * solves of the same graph give the same bits, whatever check_every is. */
+typedef struct kmx_chordal kmx_chordal;
+typedef struct {
+  double rtol;            /* 0: 1e-10 */
+  int32_t max_iterations; /* per stage; 0: 20000 */
+  int32_t check_every;    /* iterations enqueued between two host reads of the
+                             device's done word; 0: 50. No effect on the result. */
+} kmx_chordal_params;
+typedef struct {          /* per block */
+  int32_t iterations_rot, iterations_trans; /* the largest count among the block's three CGs */
+  int32_t converged;      /* 1: all six met the stop test; 0: max_iterations cut one short */
+  double relres_rot[3], relres_trans[3]; /* |r| / |b| at the end (0 where |b| = 0) */
+} kmx_chordal_block_info;
+int kmx_chordal_create(int device, kmx_chordal** out);
+int kmx_chordal_destroy(kmx_chordal* h);
+int kmx_chordal_set_stream(kmx_chordal* h, void* hip_stream);
+/* Checked on the host before any device call; on failure the handle keeps its
+ * previous graph: KMX_EINVAL for an index out of range, src == dst, an edge
+ * across blocks, a value that is not finite, kappa or tau <= 0, w < 0, a
+ * block_ptr that is not monotone from 0 to n_poses, an anchor out of range or
+ * listed twice, and a connected component over the edges of w > 0 without an
+ * anchor (a free pose without such an edge is one): that system is singular.
+ * Edges of w == 0 contribute nothing. Parallel edges and empty blocks are
+ * legal. R is [n_edges][9] row-major, t [n_edges][3]; weight NULL: 1. */
+int kmx_chordal_set_graph(kmx_chordal* h, int32_t n_poses, int32_t n_blocks, const int32_t* block_ptr,
+                          int64_t n_edges, const int32_t* src, const int32_t* dst,
+                          const double* R, const double* t,
+                          const double* kappa, const double* tau, const double* weight,
+                          int32_t n_anchors, const int32_t* anchors);
+/* New weights for the same edges ([n_edges]; NULL: 1): only the weights are
+ * uploaded again. Checked like set_graph's; on KMX_EINVAL the previous weights
+ * stay in force. */
+int kmx_chordal_set_weights(kmx_chordal* h, const double* weight);
+/* R_init [n][9] / t_init [n][3]: the start vectors (NULL: zero; values at
+ * anchors are ignored). R_out [n][9], t_out [n][3]; info [n_blocks] or NULL.
+ * p NULL or a field 0: the default. Reaching max_iterations is no error: that
+ * block reports converged = 0 and the output is its last iterate, projected.
+ * A (block, row) whose right-hand side is zero is converged at once and keeps
+ * its start vector. KMX_ESTATE without a graph. */
+int kmx_chordal_solve(kmx_chordal* h, const kmx_chordal_params* p,
+                      const double* R_init, const double* t_init,
+                      double* R_out, double* t_out, kmx_chordal_block_info* info);
+/* Device times (ms, HIP events) of the last solve: the upload of the start
+ * vectors, the rotation stage with the projection, the translation stage, the
+ * download. KMX_ESTATE before the first solve. */
+int kmx_chordal_get_timing(kmx_chordal* h, double* ms /* [4] */);
+
 #ifdef __cplusplus
 }
 #endif

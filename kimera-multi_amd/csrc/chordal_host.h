@@ -1,0 +1,187 @@
+// chordal_host.h — host-side half of chordal.hip that needs no device: the
+// checks kmx_chordal_set_graph / kmx_chordal_set_weights run before any device
+// call, and the per-pose incidence CSR and tile list they upload. Plain C++, so
+// `make chordal_check` can build it with the host sanitizers
+// (chordal_check.cpp).
+#pragma once
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdint>
+#include <numeric>
+#include <string>
+#include <vector>
+
+#include "kmx_abi.h"
+
+namespace kmx {
+
+constexpr int CH_TILE = 64;                 // poses per tile = lanes per workgroup (one wave)
+constexpr uint32_t CH_DIR_OUT = 1u << 31;   // record bit: this pose is the edge's source (p == i)
+
+// What kmx_chordal_set_graph keeps: the incidence CSR (sorted by pose, in edge
+// order within a pose) and the tiles. A tile is at most CH_TILE consecutive
+// poses of ONE block, so a block's partial sums do not depend on which other
+// blocks are in the batch.
+struct ChordalGraph {
+  int32_t n = 0, nb = 0;
+  int64_t m = 0;
+  std::vector<int32_t> inc_ptr;     // [n + 1]
+  std::vector<uint32_t> inc_other;  // [2m] other endpoint | CH_DIR_OUT
+  std::vector<int32_t> inc_edge;    // [2m] the caller's edge index (weights are per edge)
+  std::vector<double> inc_M;        // [2m][9] R_e when the pose is the target, R_e^T when it is the source
+  std::vector<double> inc_t;        // [2m][3] t_ij
+  std::vector<uint8_t> is_free;     // [n] 0: anchor
+  std::vector<int32_t> tile_p0, tile_p1, tile_block;  // [n_tiles]
+  std::vector<int32_t> tile_ptr;    // [nb + 1] a block's tiles
+  std::vector<double> kappa, tau;   // [m]
+  std::vector<int32_t> src, dst;    // [m] (kept for the connectivity check of set_weights)
+};
+
+namespace chordal_detail {
+inline int32_t uf_find(std::vector<int32_t>& parent, int32_t a) {
+  while (parent[a] != a) {
+    parent[a] = parent[parent[a]];
+    a = parent[a];
+  }
+  return a;
+}
+}  // namespace chordal_detail
+
+// Every connected component over the edges with weight > 0 (weight NULL: all)
+// must hold an anchor; a free pose without a kept edge is such a component.
+// The weights are checked here too (finite, >= 0). src / dst must already be
+// in range. KMX_OK, or KMX_EINVAL with *err set.
+inline int chordal_check_weights(int32_t n, int64_t m, const int32_t* src, const int32_t* dst, const double* weight,
+                                 const uint8_t* is_free, std::string* err) {
+  auto bad = [&](const std::string& s) {
+    if (err) *err = s;
+    return KMX_EINVAL;
+  };
+  if (weight)
+    for (int64_t e = 0; e < m; ++e)
+      if (!std::isfinite(weight[e]) || weight[e] < 0) return bad("weight must be finite and >= 0 (edge " + std::to_string(e) + ")");
+  std::vector<int32_t> parent((size_t)n);
+  std::iota(parent.begin(), parent.end(), 0);
+  for (int64_t e = 0; e < m; ++e) {
+    if (weight && weight[e] == 0) continue;
+    const int32_t a = chordal_detail::uf_find(parent, src[e]), b = chordal_detail::uf_find(parent, dst[e]);
+    if (a != b) parent[a] = b;
+  }
+  std::vector<uint8_t> anchored((size_t)n, 0);
+  for (int32_t p = 0; p < n; ++p)
+    if (!is_free[p]) anchored[chordal_detail::uf_find(parent, p)] = 1;
+  for (int32_t p = 0; p < n; ++p)
+    if (!anchored[chordal_detail::uf_find(parent, p)])
+      return bad("pose " + std::to_string(p) + " is not connected to an anchor over the edges of weight > 0 (singular system)");
+  return KMX_OK;
+}
+
+// Checks the arguments of kmx_chordal_set_graph and, when they pass, builds
+// *out (untouched on failure). KMX_OK, or KMX_EINVAL with *err set.
+inline int chordal_build(int32_t n, int32_t nb, const int32_t* block_ptr, int64_t m, const int32_t* src,
+                         const int32_t* dst, const double* R, const double* t, const double* kappa, const double* tau,
+                         const double* weight, int32_t n_anchors, const int32_t* anchors, ChordalGraph* out,
+                         std::string* err) {
+  auto bad = [&](const std::string& s) {
+    if (err) *err = s;
+    return KMX_EINVAL;
+  };
+  if (!out) return bad("null argument");
+  if (n < 1 || nb < 1 || m < 0 || n_anchors < 0) return bad("bad argument (n_poses, n_blocks >= 1; n_edges, n_anchors >= 0)");
+  if (!block_ptr) return bad("null block_ptr");
+  if (m > 0 && (!src || !dst || !R || !t || !kappa || !tau)) return bad("null edge array");
+  if (n_anchors > 0 && !anchors) return bad("null anchors");
+  if (m >= (int64_t)INT32_MAX / 2) return bad("too many edges (2 * n_edges must fit int32)");
+  if (block_ptr[0] != 0) return bad("block_ptr must start at 0");
+  for (int32_t b = 0; b < nb; ++b)
+    if (block_ptr[b + 1] < block_ptr[b] || block_ptr[b + 1] > n) return bad("block_ptr not monotone");
+  if (block_ptr[nb] != n) return bad("block_ptr must cover [0, n_poses)");
+  std::vector<int32_t> pose_block((size_t)n);
+  for (int32_t b = 0; b < nb; ++b)
+    for (int32_t p = block_ptr[b]; p < block_ptr[b + 1]; ++p) pose_block[p] = b;
+  std::vector<uint8_t> is_free((size_t)n, 1);
+  for (int32_t a = 0; a < n_anchors; ++a) {
+    if (anchors[a] < 0 || anchors[a] >= n) return bad("anchor out of range");
+    if (!is_free[anchors[a]]) return bad("anchor listed twice");
+    is_free[anchors[a]] = 0;
+  }
+  for (int64_t e = 0; e < m; ++e) {
+    const std::string at = " (edge " + std::to_string(e) + ")";
+    if (src[e] < 0 || src[e] >= n || dst[e] < 0 || dst[e] >= n) return bad("edge endpoint out of range" + at);
+    if (src[e] == dst[e]) return bad("edge from a pose to itself" + at);
+    if (pose_block[src[e]] != pose_block[dst[e]]) return bad("edge across blocks" + at);
+    for (int k = 0; k < 9; ++k)
+      if (!std::isfinite(R[9 * e + k])) return bad("R not finite" + at);
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(t[3 * e + k])) return bad("t not finite" + at);
+    if (!std::isfinite(kappa[e]) || !(kappa[e] > 0)) return bad("kappa must be finite and > 0" + at);
+    if (!std::isfinite(tau[e]) || !(tau[e] > 0)) return bad("tau must be finite and > 0" + at);
+  }
+  std::string werr;
+  if (chordal_check_weights(n, m, src, dst, weight, is_free.data(), &werr) != KMX_OK) return bad(werr);
+
+  ChordalGraph g;
+  g.n = n;
+  g.nb = nb;
+  g.m = m;
+  g.is_free = std::move(is_free);
+  g.kappa.assign(kappa, kappa + m);
+  g.tau.assign(tau, tau + m);
+  g.src.assign(src, src + m);
+  g.dst.assign(dst, dst + m);
+  // incidence CSR by counting sort: a pose's records come in edge order, and
+  // an edge's two records are distinct (src != dst)
+  g.inc_ptr.assign((size_t)n + 1, 0);
+  for (int64_t e = 0; e < m; ++e) {
+    g.inc_ptr[src[e] + 1]++;
+    g.inc_ptr[dst[e] + 1]++;
+  }
+  for (int32_t p = 0; p < n; ++p) g.inc_ptr[p + 1] += g.inc_ptr[p];
+  const size_t nrec = (size_t)2 * (size_t)m;
+  g.inc_other.resize(nrec);
+  g.inc_edge.resize(nrec);
+  g.inc_M.resize(9 * nrec);
+  g.inc_t.resize(3 * nrec);
+  std::vector<int32_t> fill(g.inc_ptr.begin(), g.inc_ptr.end() - 1);
+  for (int64_t e = 0; e < m; ++e) {
+    const double* Re = R + 9 * e;
+    const size_t ks = (size_t)fill[src[e]]++;  // the source's record: X_j R_e^T
+    g.inc_other[ks] = (uint32_t)dst[e] | CH_DIR_OUT;
+    g.inc_edge[ks] = (int32_t)e;
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) g.inc_M[9 * ks + 3 * r + c] = Re[3 * c + r];
+    const size_t kd = (size_t)fill[dst[e]]++;  // the target's record: X_i R_e
+    g.inc_other[kd] = (uint32_t)src[e];
+    g.inc_edge[kd] = (int32_t)e;
+    for (int k = 0; k < 9; ++k) g.inc_M[9 * kd + k] = Re[k];
+    for (int k = 0; k < 3; ++k) g.inc_t[3 * ks + k] = g.inc_t[3 * kd + k] = t[3 * e + k];
+  }
+  g.tile_ptr.assign((size_t)nb + 1, 0);
+  for (int32_t b = 0; b < nb; ++b) {
+    for (int32_t p = block_ptr[b]; p < block_ptr[b + 1]; p += CH_TILE) {
+      g.tile_p0.push_back(p);
+      g.tile_p1.push_back(std::min<int32_t>(p + CH_TILE, block_ptr[b + 1]));
+      g.tile_block.push_back(b);
+    }
+    g.tile_ptr[b + 1] = (int32_t)g.tile_p0.size();
+  }
+  *out = std::move(g);
+  return KMX_OK;
+}
+
+// The per-record weights w*kappa and w*tau the kernels read (weight NULL: 1).
+inline void chordal_record_weights(const ChordalGraph& g, const double* weight, std::vector<double>* wk,
+                                   std::vector<double>* wt) {
+  const size_t nrec = g.inc_edge.size();
+  wk->resize(nrec);
+  wt->resize(nrec);
+  for (size_t k = 0; k < nrec; ++k) {
+    const int32_t e = g.inc_edge[k];
+    const double w = weight ? weight[e] : 1.0;
+    (*wk)[k] = w * g.kappa[e];
+    (*wt)[k] = w * g.tau[e];
+  }
+}
+
+}  // namespace kmx

@@ -122,6 +122,17 @@ class LcdResult(C.Structure):
     ]
 
 
+class ChordalParams(C.Structure):
+    """kmx_chordal_params (0 in a field: the library's default)."""
+    _fields_ = [("rtol", C.c_double), ("max_iterations", C.c_int32), ("check_every", C.c_int32)]
+
+
+class ChordalBlockInfo(C.Structure):
+    """kmx_chordal_block_info: one per block of a kmx_chordal_solve."""
+    _fields_ = [("iterations_rot", C.c_int32), ("iterations_trans", C.c_int32), ("converged", C.c_int32),
+                ("relres_rot", C.c_double * 3), ("relres_trans", C.c_double * 3)]
+
+
 _lib = None
 
 
@@ -239,6 +250,15 @@ def lib() -> C.CDLL:
         "kmx_voc_sync": ([P], C.c_int),
         "kmx_voc_enable_timing": ([P, C.c_int], C.c_int),
         "kmx_voc_read_timing": ([P, pf64, pf64], C.c_int),
+        "kmx_chordal_create": ([C.c_int, C.POINTER(P)], C.c_int),
+        "kmx_chordal_destroy": ([P], C.c_int),
+        "kmx_chordal_set_stream": ([P, P], C.c_int),
+        "kmx_chordal_set_graph": ([P, i32, i32, pi32, i64, pi32, pi32, pf64, pf64, pf64, pf64, pf64, i32, pi32],
+                                  C.c_int),
+        "kmx_chordal_set_weights": ([P, pf64], C.c_int),
+        "kmx_chordal_solve": ([P, C.POINTER(ChordalParams), pf64, pf64, pf64, pf64, C.POINTER(ChordalBlockInfo)],
+                              C.c_int),
+        "kmx_chordal_get_timing": ([P, pf64], C.c_int),
     })
     for name, (argt, rest) in sig.items():
         if not hasattr(L, name):

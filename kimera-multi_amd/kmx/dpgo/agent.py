@@ -156,7 +156,10 @@ class PGOAgent:
         """INITIALIZE: build the local problem and the initial lifted iterate.
         TInit: dpgo PoseArray (d x (d+1)n) or [n, 3, 4]; default: the odometry
         chain or, with localInitializationMethod "chordal", the chordal
-        relaxation over the robot's own measurements (kmx.dpgo.init).
+        relaxation over the robot's own measurements (kmx.dpgo.init);
+        "chordal_gpu" solves the same relaxation on the device, started from
+        the odometry chain (an L2 method either way: outlier loop closures at
+        weight 1 can make it worse than the odometry chain).
         neighbor_global_poses: {(robot, pose): (R, t)} of neighbours already in
         the global frame -> the local trajectory is aligned to it by robust
         single-pose averaging over the shared loop closures (kmx.dpgo.init;
@@ -199,6 +202,14 @@ class PGOAgent:
                 from .init import chordal_initialization
                 own = self.odometry + self.private_lcs
                 Rs, ts = chordal_initialization(self.n, [(m.p1, m.p2, m.R, m.t, m.kappa, m.tau, m.weight) for m in own])
+            elif self.params.localInitializationMethod == "chordal_gpu":
+                # the same problem on the device (kmx_chordal_*), started from the odometry chain
+                from .init import chordal_initialization_gpu
+                own = self.odometry + self.private_lcs
+                R0, t0 = self._odometry_chain()
+                Rs, ts = chordal_initialization_gpu(
+                    self.n, [(m.p1, m.p2, m.R, m.t, m.kappa, m.tau, m.weight) for m in own], R_init=R0, t_init=t0,
+                    device=self._device)
             elif self.params.localInitializationMethod == "odometry":
                 Rs, ts = self._odometry_chain()
             else:

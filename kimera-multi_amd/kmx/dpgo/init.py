@@ -193,3 +193,74 @@ def chordal_initialization(n: int, edges, anchor: int = 0):
     ts = np.zeros((n, 3))
     ts[free] = np.asarray(x).reshape(n - 1, 3)
     return Rs, ts
+
+
+def _edge_arrays(edges):
+    E = list(edges)
+    m = len(E)
+    src = np.array([e[0] for e in E], np.int64).reshape(m)
+    dst = np.array([e[1] for e in E], np.int64).reshape(m)
+    R = np.array([np.asarray(e[2], np.float64) for e in E], np.float64).reshape(m, 3, 3)
+    t = np.array([np.asarray(e[3], np.float64) for e in E], np.float64).reshape(m, 3)
+    kap = np.array([e[4] for e in E], np.float64).reshape(m)
+    tau = np.array([e[5] for e in E], np.float64).reshape(m)
+    w = np.array([e[6] for e in E], np.float64).reshape(m)
+    return src, dst, R, t, kap, tau, w
+
+
+def chordal_initialization_gpu(n: int, edges, anchor: int = 0, R_init=None, t_init=None, *, device: int = 0,
+                               return_info: bool = False, **solver_kw):
+    """chordal_initialization on the device (kmx.dpgo.chordal.ChordalSolver,
+    DESIGN.md §14): the same arguments, the same problem and the same return
+    values, the two linear systems solved by preconditioned conjugate
+    gradients to solver_kw's rtol (default 1e-10) instead of a sparse
+    factorisation. R_init / t_init: the start vectors ([n,3,3], [n,3]; None:
+    zero), e.g. the odometry chain. There is no CPU fallback.
+
+    Like the host function this is an L2 method: loop closures that are
+    outliers pull at full weight, and the result can then be worse than the
+    odometry chain."""
+    from .chordal import ChordalSolver
+    src, dst, R, t, kap, tau, w = _edge_arrays(edges)
+    s = ChordalSolver(device)
+    try:
+        s.set_graph(n, [0, n], src, dst, R, t, kap, tau, w, anchors=[anchor])
+        Rs, ts, info = s.solve(R_init, t_init, **solver_kw)
+    finally:
+        s.close()
+    return (Rs, ts, info) if return_info else (Rs, ts)
+
+
+def chordal_initialization_team(g, weights=None, *, device: int = 0, return_info: bool = False, **solver_kw):
+    """Chordal initialisation of every robot of the team graph g
+    (kmx.synth.PoseGraphData) in one batch on the device: each robot's private
+    measurements (r1 == r2) form one block, pose 0 of each robot is its anchor
+    (every robot in its own frame), and the start vector is the robot's
+    odometry chain g.init_R / g.init_t relative to its pose 0. weights: per
+    edge of g ([g.m]; None: g.weight). Returns (list of R [n_a,3,3], list of
+    t [n_a,3]) per robot, and the per-robot solver info with return_info.
+    An L2 method: see chordal_initialization_gpu."""
+    from .chordal import ChordalSolver
+    n_poses = np.asarray(g.n_poses, np.int64)
+    ptr = np.concatenate([[0], np.cumsum(n_poses)])
+    own = np.nonzero(g.r1 == g.r2)[0]
+    w = np.asarray(g.weight if weights is None else weights, np.float64)
+    if w.shape != (g.m,):
+        raise ValueError(f"weights: expected shape ({g.m},), got {w.shape}")
+    off = ptr[g.r1[own]]
+    R0, t0 = [], []
+    for a in range(g.n_robots):
+        Ra, ta = np.asarray(g.init_R[a], np.float64), np.asarray(g.init_t[a], np.float64)
+        R0.append(np.einsum("ij,njk->nik", Ra[0].T, Ra))
+        t0.append((ta - ta[0]) @ Ra[0])
+    n = int(ptr[-1])
+    s = ChordalSolver(device)
+    try:
+        s.set_graph(n, ptr, off + g.p1[own], off + g.p2[own], g.R[own], g.t[own], g.kappa[own], g.tau[own], w[own],
+                    anchors=ptr[:-1][n_poses > 0])
+        Rs, ts, info = s.solve(np.concatenate(R0).reshape(n, 3, 3), np.concatenate(t0).reshape(n, 3), **solver_kw)
+    finally:
+        s.close()
+    Rl = [Rs[ptr[a]:ptr[a + 1]] for a in range(g.n_robots)]
+    tl = [ts[ptr[a]:ptr[a + 1]] for a in range(g.n_robots)]
+    return (Rl, tl, info) if return_info else (Rl, tl)

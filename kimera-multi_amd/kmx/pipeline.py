@@ -248,13 +248,18 @@ def ate_rmse(g: PoseGraphData, traj: dict, *, anchor_robot: int = 0) -> float:
 
 def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, rank: int = 0, world: int = 1,
                  device: int = 0, rounds: int = 100, verifier=None, solver=None, exchange_device=None,
-                 return_trajectory: bool = False) -> dict:
+                 return_trajectory: bool = False, local_init: str = "odometry") -> dict:
     """One team run: LCD verification of this rank's candidates (query robot
     in the rank's robot range) -> all_gather of the accepted loop closures ->
     team graph -> global initialisation -> `rounds` concurrent RBCD rounds
     with GNC. `verifier(cand_query, cand_match) -> result dicts` and `solver`
     replace the HIP LoopClosureDetector / BlockSolver (the CPU tests inject
-    the restatement). Returns stage timings and metrics (identical on every
+    the restatement). local_init: how every robot is initialised in its own
+    frame before the global alignment: "odometry" (its odometry chain, the
+    default) or "chordal_gpu" (kmx.dpgo.init.chordal_initialization_team: the
+    chordal relaxation over its private measurements, one batch on the device;
+    an L2 method, so outlier loop closures at weight 1 can make it worse than
+    the odometry chain). Returns stage timings and metrics (identical on every
     rank)."""
     import time
 
@@ -293,8 +298,16 @@ def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, ran
     t0 = time.perf_counter()
     rc = lcd_params
     g = team_graph(g0, acc, getattr(rc, "kappa", 1e4), getattr(rc, "tau", 1e2))
-    traj0, frames = global_init(g, odometry_init(g))
-    out["init"] = {"seconds": time.perf_counter() - t0, "ate_m": ate_rmse(g, traj0),
+    if local_init == "odometry":
+        own0 = odometry_init(g)
+    elif local_init == "chordal_gpu":
+        from .dpgo.init import chordal_initialization_team
+        Rl, tl = chordal_initialization_team(g, device=device)
+        own0 = {a: (Rl[a], tl[a]) for a in range(g.n_robots)}
+    else:
+        raise ValueError(f"unknown local_init {local_init!r}")
+    traj0, frames = global_init(g, own0)
+    out["init"] = {"seconds": time.perf_counter() - t0, "ate_m": ate_rmse(g, traj0), "local_init": local_init,
                    "edges": g.m, "shared_loop_closures": int((g.r1 != g.r2).sum())}
     # 3. RBCD + GNC rounds
     Y = lifting_matrix(params.r, seed=1)

@@ -28,6 +28,9 @@ def main():
     ap.add_argument("--sigma-r", type=float, default=0.002, help="odometry rotation noise per keyframe (rad)")
     ap.add_argument("--sigma-t", type=float, default=0.02, help="odometry translation noise per keyframe (m)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--local-init", choices=("odometry", "chordal_gpu"), default="odometry",
+                    help="each robot's initialisation in its own frame: its odometry chain, or the chordal "
+                         "relaxation on the device (L2: the intra-robot outliers pull at full weight)")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -48,7 +51,7 @@ def main():
     stream = PL.make_lc_stream(g0, a.robots * a.true_per_robot, a.robots * a.false_per_robot, seed=a.seed + 1)
     gen = time.perf_counter() - t0
     out = PL.run_pipeline(g0, stream, bench.params(), LcdParams(), rank=rank, world=world, device=local_rank,
-                          rounds=a.rounds)
+                          rounds=a.rounds, local_init=a.local_init)
     out["config"] = {"workload": f"configs[4]: {a.robots} robots x {a.poses} poses, {g0.m} base edges "
                                  f"(intra-robot loop closures, 20% intra outliers, odometry noise "
                                  f"{a.sigma_r} rad / {a.sigma_t} m), LC stream "
