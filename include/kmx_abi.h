@@ -167,6 +167,16 @@ int kmx_pgo_set_tcg_poll(kmx_pgo* h, int mode);
  * last group repeat the local robot count. */
 int kmx_pgo_get_tcg_groups(kmx_pgo* h, int* groups, int32_t* bounds);
 
+/* The reduction form of the next round's launch chains (additive to ABI 10):
+ * 0 launched (a k_reduce launch after every producing kernel), 2 consumer (the
+ * next kernel of the chain reduces its robot's partials itself; no k_reduce in
+ * a round). Where robot groups are in effect this is the grouped round's form:
+ * KMX_GROUP_RED=0/2 at handle creation, by default 2 while no local robot has
+ * more than 384 tiles and 0 above that; otherwise the single chain's form
+ * (KMX_RED, or by the local pose count). The results are bitwise the same in
+ * either form. */
+int kmx_pgo_get_group_reduction(kmx_pgo* h, int* form);
+
 /* Native team exchange over RCCL (replaces the ROS topics public_poses +
  * status of dpgo_ros, drawio:2340-2375, for a team with one process per GPU).
  * Rank 0 calls kmx_comm_unique_id and hands the KMX_COMM_ID_BYTES bytes to

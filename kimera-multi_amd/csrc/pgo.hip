@@ -2846,6 +2846,23 @@ struct kmx_pgo {
   };
   int groups_req = 2;
   std::vector<Group> grp;  // the cut of the current graph (one group: no fork)
+  // The grouped round's reduction form (KMX_GROUP_RED = 0 launched, 2
+  // consumer): which of the two forms below the groups' chains take; `rm`
+  // still decides whether groups are in effect and the single chain's form.
+  // On one chain the consumer form only ties at 100k poses (above); on two
+  // chains it drops 22 of a chain's 45 launches and the other group's
+  // workgroups fill part of the waits for the robot sums: configs[3]
+  // 0.603-0.619 ms per round against 0.622-0.633 for the launched form
+  // (profiles/r08/group_consumer/). Every workgroup of
+  // the consumer kernels reads all tile partials of its robot, so its cost
+  // grows with the robot's tile count: with 8 robots in 2 groups it wins 3-5 %
+  // at 275-288 tiles per robot (12.5k poses), 1-2 % at 310-324 and ~1 % at
+  // 354-368, loses 1.4 % at 400-421, 7 % at ~500 and 20 % at ~2600 (the
+  // 1M-pose config). It is the default while no local robot has more than
+  // GROUP_CONSUMER_MAX_TILES tiles.
+  int grm = 2;
+  int grm_forced = -1;
+  static constexpr int GROUP_CONSUMER_MAX_TILES = 384;
   hipStream_t gstream[MAX_GROUPS - 1] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_fork = nullptr, ev_join[MAX_GROUPS - 1] = {nullptr, nullptr, nullptr};
   // Gated k_hess launches (KMX_HESS_GATE=0: off): every k_hess launch after a
@@ -3304,36 +3321,45 @@ void enqueue_trial_t(kmx_pgo* h, bool rgd) {
   if (!fold_cost<RM>(h)) red_t<R, RM>(h, RED_COST);
 }
 
-// The round with robot groups (kmx_pgo::grp, RM_LAUNCH and RTR): k_begin on
+// The round with robot groups (kmx_pgo::grp, RTR): k_begin on
 // the handle's stream, then every group's chain on its own stream, enqueued
 // launch by launch across the groups so no stream runs dry while the host
 // serves another, and the final k_commit of all robots behind the join (it
 // writes the public rows the other groups' k_grad / k_cost read). The tCG
 // loop polls per group: a group whose robots have all left tCG is no longer
 // enqueued while the others go on.
-template <int R, int RW>
+// RM: the grouped round's reduction form (kmx_pgo::grm). RM_LAUNCH: every
+// group's chain carries its k_reduce launches. RM_CONSUMER: no k_reduce in a
+// chain, as the single-chain consumer form (enqueue_tcg_t, enqueue_trial_t):
+// the gradient's sums go into the group's first k_hess, k_update and k_hess
+// reduce each other's partials, k_retract (fold 2) takes the last update's
+// and the final all-robot k_commit the trial cost's (one RTR iteration; with
+// more, each group keeps its RED_COST k_reduce and its own non-final commit).
+template <int R, int RW, int RM>
 void enqueue_round_groups_t(kmx_pgo* h, const unsigned char* d_active) {
-  constexpr int RM = RM_LAUNCH;
+  constexpr bool cons = RM == RM_CONSUMER;
   const int G = (int)h->grp.size();
   const dim3 blk(BLOCK);
   // fork: the begin launch's own completion is the event the side streams wait
-  // for, and join: each side stream's last launch (the trial cost's k_reduce)
-  // carries the event the final commit waits for. Neither puts a marker on the
-  // stream it is recorded on, so group 0's k_grad follows k_begin directly.
+  // for, and join: each side stream's last launch (the trial cost's k_reduce,
+  // or k_cost itself where the final commit takes its sums) carries the event
+  // the final commit waits for. Neither puts a marker on the stream it is
+  // recorded on, so group 0's k_grad follows k_begin directly.
   const bool pend = enqueue_begin(h, d_active, BEGIN_ROUND, true, h->ev_fork);
   GroupLaunch q[kmx_pgo::MAX_GROUPS];
   for (int g = 0; g < G; ++g) q[g] = group_launch(h, g);
   // (an event call's error is left to the caller's hipGetLastError, as a launch's)
   for (int g = 1; g < G; ++g) (void)hipStreamWaitEvent(q[g].s, h->ev_fork, 0);
   const int iters = h->P.rtr_iterations, tmax = h->P.tcg_max_iterations;
+  const bool fcost = fold_cost<RM>(h);
   for (int it = 0; it < iters; ++it) {
     for (int g = 0; g < G; ++g) {
       hipLaunchKernelGGL((k_grad<R, RW, RM>), dim3(q[g].d.gnt), blk, SmemHG<R>::bytes, q[g].s, q[g].d,
                          it == 0 && pend ? 1 : 0);
-      red_g<R>(q[g], RED_GRAD);
+      if (!fold_grad<RM>(h)) red_g<R>(q[g], RED_GRAD);
     }
-    // tCG, as enqueue_tcg_t's RM_LAUNCH loop, with each group's own polling state
-    bool poll[kmx_pgo::MAX_GROUPS], live[kmx_pgo::MAX_GROUPS];
+    // tCG, as enqueue_tcg_t's loop of the same form, with each group's own polling state
+    bool poll[kmx_pgo::MAX_GROUPS], live[kmx_pgo::MAX_GROUPS], stopped[kmx_pgo::MAX_GROUPS];
     unsigned long long prev[kmx_pgo::MAX_GROUPS], seq[kmx_pgo::MAX_GROUPS];
     int steps[kmx_pgo::MAX_GROUPS];
     for (int g = 0; g < G; ++g) {
@@ -3343,6 +3369,7 @@ void enqueue_round_groups_t(kmx_pgo* h, const unsigned char* d_active) {
         poll[g] = false;
       }
       live[g] = true;
+      stopped[g] = false;
       prev[g] = seq[g] = 0;
       steps[g] = tmax;
     }
@@ -3356,19 +3383,30 @@ void enqueue_round_groups_t(kmx_pgo* h, const unsigned char* d_active) {
         HostStatus* hs = poll[g] ? h->hstat : nullptr;
         const int fl = (j == 0 ? 1 : 0) | (j > 0 && h->hess_gate ? 2 : 0);
         const dim3 grid(q[g].d.gnt);
-        hipLaunchKernelGGL((k_hess<R, RW, RM>), grid, blk, SmemH<R>::bytes, q[g].s, q[g].d, fl, -1,
-                           (HostStatus*)nullptr, 0ull);
-        red_g<R>(q[g], RED_HESS);
-        hipLaunchKernelGGL((k_update<R, RM>), grid, blk, SmemU::bytes, q[g].s, q[g].d, (HostStatus*)nullptr,
-                           seq[g], -1);
-        red_g<R>(q[g], RED_UPDATE, hs, seq[g]);
+        if constexpr (cons) {
+          // k_hess reports the stop test of the previous step's update
+          hipLaunchKernelGGL((k_hess<R, RW, RM>), grid, blk, SmemH<R>::bytes, q[g].s, q[g].d, fl, -1, hs, seq[g]);
+          hipLaunchKernelGGL((k_update<R, RM>), grid, blk, SmemU::bytes, q[g].s, q[g].d, (HostStatus*)nullptr, 0ull,
+                             -1);
+        } else {
+          hipLaunchKernelGGL((k_hess<R, RW, RM>), grid, blk, SmemH<R>::bytes, q[g].s, q[g].d, fl, -1,
+                             (HostStatus*)nullptr, 0ull);
+          red_g<R>(q[g], RED_HESS);
+          hipLaunchKernelGGL((k_update<R, RM>), grid, blk, SmemU::bytes, q[g].s, q[g].d, (HostStatus*)nullptr,
+                             seq[g], -1);
+          red_g<R>(q[g], RED_UPDATE, hs, seq[g]);
+        }
       }
       if (!any) break;
       for (int g = 0; g < G; ++g) {
         if (!live[g] || !poll[g]) continue;
-        if (j > 0 && !wait_running(h, prev[g], h->grp[g].l0, h->grp[g].l1)) {
+        // consumer: this step's k_hess reports (its k_update is queued behind
+        // it); launched: one step stays queued beyond the last one known to
+        // be needed
+        if (j > 0 && !wait_running(h, cons ? seq[g] : prev[g], h->grp[g].l0, h->grp[g].l1)) {
           steps[g] = j + 1;
           live[g] = false;
+          stopped[g] = true;  // consumer: each robot was retracted by the k_update after its last k_hess
         }
         prev[g] = seq[g];
       }
@@ -3378,22 +3416,33 @@ void enqueue_round_groups_t(kmx_pgo* h, const unsigned char* d_active) {
         h->grp[g].blind_left = kmx_pgo::BLIND_WINDOW;
     for (int g = 0; g < G; ++g) {
       const dim3 grid(q[g].d.gnt);
-      hipLaunchKernelGGL((k_retract<R>), grid, blk, SmemU::bytes, q[g].s, q[g].d, 0, (const Ctl*)h->d_ctl);
-      hipLaunchKernelGGL((k_cost<R, RW, RM>), grid, blk, SmemC<R>::bytes, q[g].s, q[g].d, (const Ctl*)h->d_ctl);
-      red_g<R>(q[g], RED_COST, nullptr, 0, g > 0 && it + 1 == iters ? h->ev_join[g - 1] : nullptr);
-      if (it + 1 < iters)  // the next RTR iteration starts from the accepted point: the robot's own X only
+      const bool last = it + 1 == iters;
+      hipEvent_t join = g > 0 && last ? h->ev_join[g - 1] : nullptr;
+      // consumer: k_retract (fold 2) decides and retracts the robots still in
+      // tCG at the cap; not needed when the polled loop saw the group's robots stop
+      if (!(cons && stopped[g]))
+        hipLaunchKernelGGL((k_retract<R>), grid, blk, SmemU::bytes, q[g].s, q[g].d, cons ? 2 : 0,
+                           (const Ctl*)h->d_ctl);
+      if (fcost && join)  // the side stream's last dispatch: the join event completes with it
+        hipExtLaunchKernelGGL((k_cost<R, RW, RM>), grid, blk, SmemC<R>::bytes, q[g].s, nullptr, join, 0u, q[g].d,
+                              (const Ctl*)h->d_ctl);
+      else
+        hipLaunchKernelGGL((k_cost<R, RW, RM>), grid, blk, SmemC<R>::bytes, q[g].s, q[g].d, (const Ctl*)h->d_ctl);
+      if (!fcost) red_g<R>(q[g], RED_COST, nullptr, 0, join);
+      if (!last)  // the next RTR iteration starts from the accepted point: the robot's own X only
         hipLaunchKernelGGL((k_commit<R>), grid, blk, 0, q[g].s, q[g].d, 0, 0);
     }
   }
   for (int g = 1; g < G; ++g) (void)hipStreamWaitEvent(h->stream, h->ev_join[g - 1], 0);
-  hipLaunchKernelGGL((k_commit<R>), dim3(h->ntiles), blk, 0, h->stream, h->dv, 0, 1);
+  hipLaunchKernelGGL((k_commit<R>), dim3(h->ntiles), blk, 0, h->stream, h->dv, fcost ? 1 : 0, 1);
 }
 
 template <int R, int RW, int RM>
 void enqueue_round_t(kmx_pgo* h, const unsigned char* d_active) {
   if constexpr (RM == RM_LAUNCH) {
     if (groups_in_effect(h) > 1) {
-      enqueue_round_groups_t<R, RW>(h, d_active);
+      if (h->grm == RM_CONSUMER) enqueue_round_groups_t<R, RW, RM_CONSUMER>(h, d_active);
+      else enqueue_round_groups_t<R, RW, RM_LAUNCH>(h, d_active);
       return;
     }
   }
@@ -3531,6 +3580,7 @@ extern "C" int kmx_pgo_create(const kmx_pgo_params* params, int device, kmx_pgo*
     const int g = std::atoi(v);
     h->groups_req = g >= 4 ? 4 : g >= 2 ? 2 : 1;
   }
+  if (const char* v = std::getenv("KMX_GROUP_RED")) h->grm_forced = std::atoi(v) == 2 ? RM_CONSUMER : RM_LAUNCH;
   // the side streams of the robot groups (group 0 runs on the handle's stream)
   for (int g = 1; g < h->groups_req && e == hipSuccess; ++g) {
     e = hipStreamCreateWithFlags(&h->gstream[g - 1], hipStreamNonBlocking);
@@ -3597,6 +3647,12 @@ extern "C" int kmx_pgo_get_tcg_groups(kmx_pgo* h, int* groups, int32_t* bounds) 
     for (int g = 0; g <= kmx_pgo::MAX_GROUPS; ++g)
       bounds[g] = g < G ? h->grp[g].l0 : G > 0 ? h->grp[G - 1].l1 : 0;
   }
+  return KMX_OK;
+}
+
+extern "C" int kmx_pgo_get_group_reduction(kmx_pgo* h, int* form) {
+  KMX_CHECK(h && form, KMX_EINVAL, "null argument");
+  *form = ready(h) && groups_in_effect(h) > 1 ? h->grm : h->rm;
   return KMX_OK;
 }
 
@@ -3881,6 +3937,11 @@ extern "C" int kmx_pgo_set_graph(kmx_pgo* h, int n_robots, const int32_t* n_pose
       q.t0 = rt0[q.l0];
       q.nt = rt0[q.l1] - rt0[q.l0];
     }
+    // the grouped round's reduction form (kmx_pgo::grm)
+    int most = 0;
+    for (int l = 0; l < L; ++l) most = std::max(most, rt0[l + 1] - rt0[l]);
+    h->grm = h->grm_forced >= 0 ? h->grm_forced
+                                : (most <= kmx_pgo::GROUP_CONSUMER_MAX_TILES ? RM_CONSUMER : RM_LAUNCH);
   }
   std::vector<int> own_src(std::max<int64_t>(h->n_owned, 1), 0);
   for (int64_t k = 0; k < h->n_owned; ++k) own_src[k] = pub_src[h->first_owned + k];

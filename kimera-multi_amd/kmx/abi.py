@@ -158,6 +158,7 @@ def lib() -> C.CDLL:
         "kmx_pgo_set_stream": ([P, P], C.c_int),
         "kmx_pgo_set_tcg_poll": ([P, C.c_int], C.c_int),
         "kmx_pgo_get_tcg_groups": ([P, C.POINTER(C.c_int), pi32], C.c_int),
+        "kmx_pgo_get_group_reduction": ([P, C.POINTER(C.c_int)], C.c_int),
         "kmx_comm_unique_id": ([P, i64], C.c_int),
         "kmx_runtime_info": ([C.c_char_p, i64], C.c_int),
         "kmx_pgo_comm_init": ([P, P, C.c_int, C.c_int, f64], C.c_int),

@@ -65,6 +65,14 @@ class BlockSolver:
         check(self.L.kmx_pgo_get_tcg_groups(self.h, C.byref(g), None), "kmx_pgo_get_tcg_groups")
         return g.value
 
+    def group_reduction(self) -> int:
+        """Reduction form of the next round's launch chains
+        (kmx_pgo_get_group_reduction): 0 launched, 2 consumer; the grouped
+        round's form (KMX_GROUP_RED) where groups are in effect."""
+        f = C.c_int()
+        check(self.L.kmx_pgo_get_group_reduction(self.h, C.byref(f)), "kmx_pgo_get_group_reduction")
+        return f.value
+
     def tcg_group_bounds(self) -> list[int]:
         """The cut of the local robots into groups: group g holds the local
         robots [b[g], b[g + 1])."""
