@@ -645,6 +645,101 @@ int kmx_bow_fetch(kmx_bow* h, int32_t nq, int32_t max_results, int32_t* out_n,
 int kmx_bow_score_entries(kmx_bow* src, int32_t n, const int32_t* a_ids,
                           const int32_t* b_ids, double* out);
 
+/* ---- detectLoop / detectLoopWithRobot decided on the device: the nss gate,
+ * the alpha cut, computeIslands and checkTemporalConstraint run on the query
+ * results where kmx_bow_query_entries_async leaves them, and one record per
+ * query comes back. The temporal constraint's state
+ * {temporal_entries, latest_query_id, latest island start, latest island end}
+ * lives in the handle and persists across calls, so any split of a keyframe
+ * stream into calls gives the answers of one call. */
+enum {
+  KMX_BOW_NO_MATCHES = 0,
+  KMX_BOW_LOW_NSS_FACTOR = 1,
+  KMX_BOW_LOW_SCORE = 2,
+  KMX_BOW_NO_GROUPS = 3,
+  KMX_BOW_FAILED_TEMPORAL_CONSTRAINT = 4,
+  KMX_BOW_LOOP_DETECTED = 5
+};
+enum {
+  KMX_BOW_MODE_INTRA = 0, /* detectLoop: islands and the temporal constraint */
+  KMX_BOW_MODE_INTER = 1  /* detectLoopWithRobot: the top result, no temporal stage */
+};
+/* LcdParams.yaml:3-12. Checked on the host before any device call (KMX_EINVAL):
+ * use_nss 0 or 1, alpha and min_nss_factor finite, max_db_results in [1, 256],
+ * the six integers below it >= 0. */
+typedef struct {
+  int32_t use_nss;
+  double alpha;
+  double min_nss_factor;
+  int32_t max_db_results;
+  int32_t recent_frames_window;
+  int32_t max_intraisland_gap;
+  int32_t min_matches_per_island;
+  int32_t max_nrFrames_between_queries;
+  int32_t max_nrFrames_between_islands;
+  int32_t min_temporal_matches;
+} kmx_bow_detect_params;
+/* One per query (48 bytes). match_id is -1 and score 0.0 unless status is
+ * FAILED_TEMPORAL_CONSTRAINT or LOOP_DETECTED; then they are the best island's
+ * best member (inter mode: the top result). n_kept: results that passed the
+ * alpha cut (0 when the query was settled before it). island_start / _end /
+ * island_score: the best island (-1, -1, 0.0 without one). nss: the factor
+ * the cut used (1.0 without use_nss); 0.0 when there is no previous keyframe. */
+typedef struct {
+  int32_t query_id;
+  int32_t status;
+  int32_t match_id;
+  int32_t n_kept;
+  int32_t island_start;
+  int32_t island_end;
+  double score;
+  double nss;
+  double island_score;
+} kmx_bow_detect_record;
+/* Query q = stored entry entry_ids[q] of src (NULL: h). One call enqueues on
+ * h's stream, after src's: the gather and the query (intra: max_id =
+ * max(id - recent_frames_window, 0); inter: none), the nss factor against
+ * entry id - 1 of src, the decision, and in intra mode the temporal pass over
+ * the queries in order; then one device-to-host copy and one synchronise.
+ * Intra mode takes src == h (a robot queries its own database) and reports a
+ * query of entry 0 as LOW_NSS_FACTOR when use_nss is set. records_out[nq];
+ * cand_out (may be NULL) holds (query id, match id) of every LOOP_DETECTED in
+ * query order, room for 2 * nq ints; *n_cand_out their count (intra mode; 0
+ * in inter mode). KMX_EINVAL for bad params or an entry id outside src,
+ * KMX_ESTATE without a database; the handle stays usable. */
+int kmx_bow_detect_entries(kmx_bow* h, kmx_bow* src, int32_t nq, const int32_t* entry_ids,
+                           int32_t mode, const kmx_bow_detect_params* params,
+                           kmx_bow_detect_record* records_out, int32_t* cand_out,
+                           int32_t* n_cand_out);
+int kmx_bow_detect_entries_async(kmx_bow* h, kmx_bow* src, int32_t nq, const int32_t* entry_ids,
+                                 int32_t mode, const kmx_bow_detect_params* params);
+/* Wait for the last kmx_bow_detect_entries_async (same nq) and copy out. */
+int kmx_bow_detect_fetch(kmx_bow* h, int32_t nq, kmx_bow_detect_record* records_out,
+                         int32_t* cand_out, int32_t* n_cand_out);
+/* The same decision on caller-supplied query results: n[nq], ids / scores
+ * [nq][K] sorted by score descending (ties: lower id first, ids unique per
+ * query), K in [1, 256] (the row stride; params->max_db_results is not read
+ * here), n[q] in [0, K], else KMX_EINVAL.
+ * query_ids[nq] (NULL: 0 .. nq - 1) are the keyframe ids the temporal
+ * constraint sees; nss[nq] and has_prev[nq] (either may be NULL: 1.0 / all 1)
+ * the nss factors and whether a previous keyframe exists. use_state != 0: the
+ * temporal pass starts from the handle's state and leaves it updated; 0: it
+ * starts from zeros and the handle's state is untouched. */
+int kmx_bow_decide_results(kmx_bow* h, int32_t nq, int32_t K, const int32_t* query_ids,
+                           const int32_t* n, const int32_t* ids, const double* scores,
+                           const double* nss, const int32_t* has_prev, int32_t mode,
+                           const kmx_bow_detect_params* params, int32_t use_state,
+                           kmx_bow_detect_record* records_out);
+/* The temporal constraint's state, 4 x int32 (above). kmx_bow_reset and
+ * kmx_bow_set_database zero it. */
+int kmx_bow_get_temporal_state(kmx_bow* h, int32_t* state4_out);
+int kmx_bow_set_temporal_state(kmx_bow* h, const int32_t* state4);
+/* With timing on, a detection call records events on the handle's stream;
+ * kmx_bow_read_detect_timing waits and returns the last call's milliseconds:
+ * {gather + query + nss factor, k_bow_decide, k_bow_temporal}. */
+int kmx_bow_enable_timing(kmx_bow* h, int on);
+int kmx_bow_read_detect_timing(kmx_bow* h, double* ms3_out);
+
 /* ------------------------------------------------------------------------- */
 /* DBoW2 vocabulary transform: ORB descriptors -> BowVectors                  */
 /* ------------------------------------------------------------------------- */

@@ -24,6 +24,11 @@
 //     the device (k_bow_seal_*, k_bow_cptr) every tail_cap adds. Queries and
 //     nss factors by entry id (k_bow_gather, k_bow_entry_score) read the
 //     forward store, so a keyframe's vector never leaves the GPU.
+//   * detectLoop's decision (kmx_bow_detect_entries / kmx_bow_decide_results):
+//     k_bow_decide, a wave per query, does the nss gate, the alpha cut and
+//     computeIslands; k_bow_temporal, one wave, checkTemporalConstraint over
+//     the queries in order, its state resident in the handle across calls. One
+//     48-byte record per query comes back.
 // Compiled with -ffp-contract=off (no FMA to contract here anyway).
 #include <hip/hip_runtime.h>
 
@@ -558,12 +563,8 @@ constexpr int TL_QW = 2048;         // query words staged in LDS (longer queries
 constexpr int TL_SORT = 2048;       // >= TAIL_MAX + MAX_RESULTS, a power of two
 static_assert(TAIL_MAX + MAX_RESULTS <= TL_SORT && (TL_SORT & (TL_SORT - 1)) == 0, "tail sort capacity");
 
-// Same as L1Scoring::score of stored entries a_ids[t], b_ids[t]; an id of -1
-// scores 0 and reads nothing.
-__global__ void k_bow_entry_score(int n, BowFwd f, const int* a_ids, const int* b_ids, double* out) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  const int a = a_ids[t], b = b_ids[t];
+// L1Scoring::score of stored entries a and b; an id of -1 scores 0 and reads nothing.
+__device__ __forceinline__ double entry_score(const BowFwd& f, int a, int b) {
   double s = 0.0;
   if (a >= 0 && b >= 0) {
     long long i = f.fptr[a], j = f.fptr[b];
@@ -581,7 +582,14 @@ __global__ void k_bow_entry_score(int n, BowFwd f, const int* a_ids, const int* 
       }
     }
   }
-  out[t] = -s / 2.0;
+  return -s / 2.0;
+}
+
+// The same for pairs of stored entries a_ids[t], b_ids[t].
+__global__ void k_bow_entry_score(int n, BowFwd f, const int* a_ids, const int* b_ids, double* out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  out[t] = entry_score(f, a_ids[t], b_ids[t]);
 }
 
 // Inclusive scan of one value per thread over a block of TL_BLOCK threads
@@ -850,6 +858,288 @@ __global__ void k_bow_cptr(int n_words, int nsub, int sch, const int* ptr, const
   }
 }
 
+// ---------------------------------------------------------------------------
+// detectLoop decided on the device: k_bow_decide, one
+// wave per query, takes the query results where the kernels above leave them
+// through the nss gate, the alpha cut and computeIslands to the best island;
+// k_bow_temporal, one wave, walks the call's queries in order through
+// checkTemporalConstraint and compacts the LOOP_DETECTED pairs.
+constexpr int DEC_PENDING = -1;  // k_bow_decide -> k_bow_temporal: an island awaits the constraint
+constexpr int DEC_WAVE = 64;
+
+struct BowDecide {
+  int use_nss;
+  double alpha, min_nss;
+  int gap, min_matches;
+};
+
+// k_bow_decide. A workgroup is one wave, so its __syncthreads() orders the
+// wave's LDS traffic and is no workgroup barrier. Every branch around one is
+// taken by the whole wave (n, k and the status are the same in all lanes).
+//   * the kept count k: the prefix with score >= alpha * nss (first failing
+//     index, a min over the lanes);
+//   * the k pairs in id order: each lane ranks its <= 4 elements by counting
+//     the ids below them in LDS (ids are unique; the index breaks a tie so
+//     that the ranks are a permutation whatever a caller passes);
+//   * island heads by ballot: island j's first position lands in s_head[j];
+//   * one lane per island walks its members in id order: the sum is one chain
+//     from 0.0, as computeIslands adds it (a tree or shuffle sum would round
+//     differently), the best member by strict > (lowest id on a tie);
+//   * the best kept island: a lane's first maximum over its islands, then a
+//     shuffle reduction on (island_score, island index), so the first island
+//     in id order wins a tie, as std::max_element does.
+// tin[q] = {status or DEC_PENDING, query id, island start, island end} and
+// tmatch[q] = the match id are the temporal pass's coalesced input. Block 0 also copies the query kernels'
+// error flag into the result header.
+__global__ __launch_bounds__(DEC_WAVE) void k_bow_decide(int nq, int K, int mode, BowDecide p, const int* qids,
+                                                         const int* n_in, const int* id_in, const double* sc_in,
+                                                         const double* nss_in, const int* has_prev,
+                                                         kmx_bow_detect_record* rec, int4* tin, int* tmatch,
+                                                         const int* qerr, int* hdr) {
+  __shared__ int u_id[MAX_RESULTS];
+  __shared__ double u_sc[MAX_RESULTS];
+  __shared__ int s_id[MAX_RESULTS];
+  __shared__ double s_sc[MAX_RESULTS];
+  __shared__ int s_head[MAX_RESULTS];
+  const int lane = threadIdx.x;
+  if (blockIdx.x == 0 && lane == 0) {  // the header: no candidates yet (k_bow_temporal counts them), the error flag
+    hdr[0] = 0;
+    hdr[1] = qerr ? qerr[0] : 0;
+  }
+  for (int q = blockIdx.x; q < nq; q += gridDim.x) {
+    const int qid = qids ? qids[q] : q;
+    const int n = max(0, min(n_in[q], K));
+    const bool hp = has_prev ? has_prev[q] != 0 : true;
+    const double nss = (p.use_nss && nss_in) ? nss_in[q] : 1.0;
+    const double nss_rep = hp ? nss : 0.0;
+    auto emit = [&](int status, int match, int kept, int i_start, int i_end, double score, double i_score) {
+      if (lane == 0) {
+        kmx_bow_detect_record r;
+        r.query_id = qid;
+        r.status = status;
+        r.match_id = match;
+        r.n_kept = kept;
+        r.island_start = i_start;
+        r.island_end = i_end;
+        r.score = score;
+        r.nss = nss_rep;
+        r.island_score = i_score;
+        rec[q] = r;
+        tin[q] = make_int4(status, qid, i_start, i_end);
+        tmatch[q] = match;
+      }
+    };
+    if (n == 0) {  // before the nss test, as on the host
+      emit(KMX_BOW_NO_MATCHES, -1, 0, -1, -1, 0.0, 0.0);
+      continue;
+    }
+    const bool low_nss = mode == KMX_BOW_MODE_INTER ? !(hp && nss >= p.min_nss) : (!hp || nss < p.min_nss);
+    if (p.use_nss && low_nss) {
+      emit(KMX_BOW_LOW_NSS_FACTOR, -1, 0, -1, -1, 0.0, 0.0);
+      continue;
+    }
+    const double thr = p.alpha * nss;  // one multiplication
+    const size_t row = (size_t)q * K;
+    if (mode == KMX_BOW_MODE_INTER) {  // the top result, no islands
+      const int id0 = id_in[row];
+      const double sc0 = sc_in[row];
+      if (sc0 >= thr) emit(KMX_BOW_LOOP_DETECTED, id0, 1, id0, id0, sc0, sc0);
+      else emit(KMX_BOW_LOW_SCORE, -1, 0, -1, -1, 0.0, 0.0);
+      continue;
+    }
+    __syncthreads();  // the previous query's LDS reads are done
+    int fail = n;     // first index whose score fails the cut: a prefix, not a count
+    for (int i = lane; i < n; i += DEC_WAVE) {
+      const int id = id_in[row + i];
+      const double s = sc_in[row + i];
+      u_id[i] = id;
+      u_sc[i] = s;
+      if (!(s >= thr)) fail = min(fail, i);
+    }
+#pragma unroll
+    for (int off = DEC_WAVE / 2; off > 0; off >>= 1) fail = min(fail, __shfl_xor(fail, off, DEC_WAVE));
+    const int k = fail;
+    if (k == 0) {
+      emit(KMX_BOW_LOW_SCORE, -1, 0, -1, -1, 0.0, 0.0);
+      continue;
+    }
+    __syncthreads();
+    if (k == 1) {  // computeIslands keeps a single result whatever min_matches_per_island says
+      emit(DEC_PENDING, u_id[0], 1, u_id[0], u_id[0], u_sc[0], u_sc[0]);
+      continue;
+    }
+    for (int i = lane; i < k; i += DEC_WAVE) {
+      const int id = u_id[i];
+      int r = 0;
+      for (int j = 0; j < k; ++j) {
+        const int o = u_id[j];
+        r += (o < id || (o == id && j < i)) ? 1 : 0;
+      }
+      s_id[r] = id;
+      s_sc[r] = u_sc[i];
+    }
+    __syncthreads();
+    int ni = 0;
+    for (int i0 = 0; i0 < k; i0 += DEC_WAVE) {
+      const int i = i0 + lane;
+      const bool head = i < k && (i == 0 || (long long)s_id[i] - s_id[i - 1] >= p.gap);
+      const unsigned long long m = __ballot(head);
+      if (head) s_head[ni + __popcll(m & ((1ull << lane) - 1ull))] = i;
+      ni += __popcll(m);
+    }
+    __syncthreads();
+    bool have = false;
+    double b_sum = 0.0, l_best_sc = 0.0;
+    int b_idx = 0x7fffffff, l_start = -1, l_end = -1, l_best = -1;
+    for (int j = lane; j < ni; j += DEC_WAVE) {
+      const int i0 = s_head[j], i1 = (j + 1 < ni) ? s_head[j + 1] : k;
+      const int st = s_id[i0], en = s_id[i1 - 1];
+      double sum = 0.0, bs = s_sc[i0];
+      int be = st;
+      for (int i = i0; i < i1; ++i) {  // ordered: left to right in id order, from 0.0
+        const double sc = s_sc[i];
+        sum += sc;
+        if (i > i0 && sc > bs) {
+          bs = sc;
+          be = s_id[i];
+        }
+      }
+      // the id span, not the member count
+      if ((long long)en - st + 1 >= p.min_matches && (!have || sum > b_sum)) {
+        have = true;
+        b_sum = sum;
+        b_idx = j;
+        l_start = st;
+        l_end = en;
+        l_best = be;
+        l_best_sc = bs;
+      }
+    }
+#pragma unroll
+    for (int off = DEC_WAVE / 2; off > 0; off >>= 1) {
+      const int o_have = __shfl_xor(have ? 1 : 0, off, DEC_WAVE);
+      const double o_sum = __shfl_xor(b_sum, off, DEC_WAVE);
+      const int o_idx = __shfl_xor(b_idx, off, DEC_WAVE);
+      if (o_have && (!have || o_sum > b_sum || (o_sum == b_sum && o_idx < b_idx))) {
+        have = true;
+        b_sum = o_sum;
+        b_idx = o_idx;
+      }
+    }
+    if (!have) {
+      emit(KMX_BOW_NO_GROUPS, -1, k, -1, -1, 0.0, 0.0);
+      continue;
+    }
+    const int owner = b_idx & (DEC_WAVE - 1);  // the lane whose own best island won
+    emit(DEC_PENDING, __shfl(l_best, owner, DEC_WAVE), k, __shfl(l_start, owner, DEC_WAVE),
+         __shfl(l_end, owner, DEC_WAVE), __shfl(l_best_sc, owner, DEC_WAVE), b_sum);
+  }
+}
+
+// k_bow_temporal: checkTemporalConstraint over the call's queries in order,
+// one wave. The state {entries, latest query, latest island start, end} is a
+// recurrence, but its inputs are not: a step takes TMP_DEPTH * 64 queries, each
+// lane loading TMP_DEPTH tin (16 bytes per lane, contiguous per load) and match
+// ids, all independent, and the next step's loads are issued before the
+// current ones are stepped through (one group of 64 per step in flight left
+// the wave waiting a memory latency per 64 queries). The state is stepped in
+// wave-uniform registers over the pending lanes only (ballot, then readlane by
+// the set bit). A query settled by k_bow_decide leaves the state alone. Every
+// LOOP_DETECTED appends (query id, match id) to cand in query order; hdr[0] =
+// their count. All stores are per-lane vector stores.
+constexpr int TMP_DEPTH = 4;
+
+__global__ __launch_bounds__(DEC_WAVE) void k_bow_temporal(int nq, int max_between_queries, int max_between_islands,
+                                                           int min_temporal, const int4* tin, const int* tmatch,
+                                                           kmx_bow_detect_record* rec, int* state, int* cand,
+                                                           int* hdr) {
+  const int lane = threadIdx.x;
+  int te = __builtin_amdgcn_readfirstlane(state[0]);
+  int lq = __builtin_amdgcn_readfirstlane(state[1]);
+  int a1 = __builtin_amdgcn_readfirstlane(state[2]);
+  int a2 = __builtin_amdgcn_readfirstlane(state[3]);
+  int nc = 0;
+  const int4 none = make_int4(KMX_BOW_NO_MATCHES, 0, 0, 0);
+  int4 nxt[TMP_DEPTH];
+  int nxt_m[TMP_DEPTH];
+  auto load = [&](int q0) {
+#pragma unroll
+    for (int d = 0; d < TMP_DEPTH; ++d) {
+      const int q = q0 + d * DEC_WAVE + lane;
+      nxt[d] = q < nq ? tin[q] : none;
+      nxt_m[d] = q < nq ? tmatch[q] : -1;
+    }
+  };
+  load(0);
+  for (int q0 = 0; q0 < nq; q0 += TMP_DEPTH * DEC_WAVE) {
+    int4 cur[TMP_DEPTH];
+    int cur_m[TMP_DEPTH];
+#pragma unroll
+    for (int d = 0; d < TMP_DEPTH; ++d) {
+      cur[d] = nxt[d];
+      cur_m[d] = nxt_m[d];
+    }
+    load(q0 + TMP_DEPTH * DEC_WAVE);
+#pragma unroll
+    for (int d = 0; d < TMP_DEPTH; ++d) {
+      const int4 t = cur[d];
+      const int q = q0 + d * DEC_WAVE + lane;
+      const bool pend = q < nq && t.x == DEC_PENDING;
+      int st = t.x;
+      unsigned long long m = __ballot(pend);
+      while (m) {
+        const int l = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const int qid = __builtin_amdgcn_readlane(t.y, l);
+        const int b1 = __builtin_amdgcn_readlane(t.z, l), b2 = __builtin_amdgcn_readlane(t.w, l);
+        // checkTemporalConstraint, as selects on scalars (no branch per query)
+        const bool fresh = (te == 0) | (qid - lq > max_between_queries);
+        const bool overlap = ((b1 <= a1) & (a1 <= b2)) | ((a1 <= b1) & (b1 <= a2)) | ((b1 <= a2) & (a2 <= b2)) |
+                             ((a1 <= b2) & (b2 <= a2));
+        const bool near = max(a1 - b2, b1 - a2) <= max_between_islands;
+        te = (!fresh & (overlap | near)) ? te + 1 : 1;
+        lq = qid;
+        a1 = b1;
+        a2 = b2;
+        if (lane == l) st = te > min_temporal ? KMX_BOW_LOOP_DETECTED : KMX_BOW_FAILED_TEMPORAL_CONSTRAINT;
+      }
+      if (pend) rec[q].status = st;
+      const bool loop = pend && st == KMX_BOW_LOOP_DETECTED;
+      const unsigned long long lm = __ballot(loop);
+      if (loop) {
+        const int pos = nc + __popcll(lm & ((1ull << lane) - 1ull));
+        cand[2 * pos] = t.y;
+        cand[2 * pos + 1] = cur_m[d];
+      }
+      nc += __popcll(lm);
+    }
+  }
+  if (lane < 4) state[lane] = lane == 0 ? te : lane == 1 ? lq : lane == 2 ? a1 : a2;
+  if (lane == 0) hdr[0] = nc;
+}
+
+// Before the query of kmx_bow_detect_entries, one thread per query: whether a
+// previous keyframe exists (entry id - 1 of src; inter mode: and is a
+// non-empty vector), the nss factor against it (k_bow_entry_score's sum; 0
+// without one or without use_nss), and in intra mode max_id = max(id - window, 0).
+// ids_in == nullptr: the queries are the consecutive entries first, first + 1,
+// ... (a keyframe stream), written to ids_out here instead of being uploaded.
+__global__ void k_bow_detect_prep(int nq, int mode, int window, int use_nss, BowFwd src, int first,
+                                  const int* ids_in, int* ids_out, int* has_prev, int* max_id, double* nss) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nq) return;
+  const int id = ids_in ? ids_in[t] : first + t;
+  if (!ids_in) ids_out[t] = id;
+  bool hp = id > 0;
+  if (mode == KMX_BOW_MODE_INTER) {
+    if (hp) hp = src.fptr[id] - src.fptr[id - 1] > 0;
+  } else {
+    max_id[t] = max(id - window, 0);
+  }
+  has_prev[t] = hp ? 1 : 0;
+  nss[t] = use_nss ? entry_score(src, id, id - 1) : 0.0;
+}
+
 template <typename T>
 int bow_alloc(T** p, size_t n) {
   *p = nullptr;
@@ -909,6 +1199,18 @@ struct kmx_bow {
   size_t ecap = 0;
   int* d_eid = nullptr;
   double* d_eout = nullptr;
+  // detection on the device: the temporal constraint's state (4 ints, then 4
+  // of scratch for a pass that leaves the state alone), grow-only scratch and
+  // the result block [records nq][n_cand, error][cand 2 * nq], with its
+  // pinned host mirror so that one copy brings a call's results back
+  int* d_tstate = nullptr;
+  size_t dcap = 0;
+  int* d_hasprev = nullptr;        // [dcap] has_prev, then [dcap] k_bow_decide's match ids
+  int4* d_tin = nullptr;
+  char *d_dout = nullptr, *h_dout = nullptr;
+  int det_nq = -1;                 // the enqueued call's query count (kmx_bow_detect_fetch)
+  bool timing = false;
+  hipEvent_t tev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 namespace {
@@ -937,6 +1239,14 @@ void bow_free_e(kmx_bow* h) {
   if (h->d_eout) (void)hipFree(h->d_eout);
   h->d_eid = nullptr; h->d_eout = nullptr;
   h->ecap = 0;
+}
+void bow_free_d(kmx_bow* h) {
+  for (void* p : {(void*)h->d_hasprev, (void*)h->d_tin, (void*)h->d_dout})
+    if (p) (void)hipFree(p);
+  if (h->h_dout) (void)hipHostFree(h->h_dout);
+  h->d_hasprev = nullptr; h->d_tin = nullptr; h->d_dout = nullptr; h->h_dout = nullptr;
+  h->dcap = 0;
+  h->det_nq = -1;
 }
 void bow_free_q(kmx_bow* h) {
   for (void* p : {(void*)h->d_qptr, (void*)h->d_qw, (void*)h->d_qv, (void*)h->d_maxid, (void*)h->d_n,
@@ -1106,8 +1416,11 @@ extern "C" int kmx_bow_create(int device, kmx_bow** out) {
   }
   h->own_stream = true;
   if (hipMalloc(reinterpret_cast<void**>(&h->d_err), 2 * sizeof(int)) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&h->d_tstate), 8 * sizeof(int)) != hipSuccess ||
+      hipMemset(h->d_tstate, 0, 8 * sizeof(int)) != hipSuccess ||
       hipEventCreateWithFlags(&h->ev, hipEventDisableTiming) != hipSuccess) {
     if (h->d_err) (void)hipFree(h->d_err);
+    if (h->d_tstate) (void)hipFree(h->d_tstate);
     (void)hipStreamDestroy(h->stream);
     delete h;
     return kmx::fail(KMX_ENOMEM, "hipMalloc failed");
@@ -1126,8 +1439,12 @@ extern "C" int kmx_bow_destroy(kmx_bow* h) {
   bow_free_p(h);
   bow_free_fwd(h);
   bow_free_e(h);
+  bow_free_d(h);
+  for (hipEvent_t e : h->tev)
+    if (e) (void)hipEventDestroy(e);
   if (h->ev) (void)hipEventDestroy(h->ev);
   if (h->d_err) (void)hipFree(h->d_err);
+  if (h->d_tstate) (void)hipFree(h->d_tstate);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return KMX_OK;
@@ -1237,6 +1554,7 @@ extern "C" int kmx_bow_set_database(kmx_bow* h, int32_t n_words, int32_t n_entri
   }
   h->h_fptr.swap(fp);
   h->n_entries = h->n_sealed = n_entries;
+  KMX_HIP(hipMemsetAsync(h->d_tstate, 0, 8 * sizeof(int), h->stream));  // a new stream of keyframes
   return KMX_OK;
   KMX_GUARD_END
 }
@@ -1572,6 +1890,238 @@ extern "C" int kmx_bow_score_entries(kmx_bow* src, int32_t n, const int32_t* a_i
   KMX_HIP(hipGetLastError());
   KMX_HIP(hipMemcpyAsync(out, src->d_eout, sizeof(double) * n, hipMemcpyDeviceToHost, src->stream));
   KMX_HIP(hipStreamSynchronize(src->stream));
+  return KMX_OK;
+  KMX_GUARD_END
+}
+
+// ---- detectLoop / detectLoopWithRobot decided on the device
+namespace {
+// The result block of a call of nq queries: records, then {n_cand, error}, then the candidate pairs.
+size_t det_hdr_off(size_t nq) { return sizeof(kmx_bow_detect_record) * nq; }
+size_t det_cand_off(size_t nq) { return det_hdr_off(nq) + 2 * sizeof(int); }
+size_t det_bytes(size_t nq) { return det_cand_off(nq) + 2 * sizeof(int) * nq; }
+static_assert(sizeof(kmx_bow_detect_record) == 48, "kmx_bow_detect_record is 48 bytes");
+
+int bow_reserve_detect(kmx_bow* h, size_t nq) {
+  if (nq <= h->dcap) return KMX_OK;
+  KMX_HIP(hipStreamSynchronize(h->stream));
+  bow_free_d(h);
+  const size_t cap = std::max<size_t>(nq, 1024);
+  int rc;
+  if ((rc = bow_alloc(&h->d_hasprev, 2 * cap)) || (rc = bow_alloc(&h->d_tin, cap)) ||
+      (rc = bow_alloc(&h->d_dout, det_bytes(cap)))) {
+    bow_free_d(h);
+    return rc;
+  }
+  if (hipHostMalloc(reinterpret_cast<void**>(&h->h_dout), det_bytes(cap), hipHostMallocDefault) != hipSuccess) {
+    h->h_dout = nullptr;
+    bow_free_d(h);
+    return kmx::fail(KMX_ENOMEM, "hipHostMalloc failed");
+  }
+  h->dcap = cap;
+  return KMX_OK;
+}
+
+int bow_time(kmx_bow* h, int k) {  // event k of the enqueued detection, when timing is on
+  if (!h->timing) return KMX_OK;
+  if (!h->tev[k]) KMX_HIP(hipEventCreate(&h->tev[k]));
+  KMX_HIP(hipEventRecord(h->tev[k], h->stream));
+  return KMX_OK;
+}
+
+// k_bow_decide over nq rows of stride K on the device and, in intra mode,
+// k_bow_temporal on `state`; then the copy of the result block to its host
+// mirror (no synchronise).
+int bow_launch_decide(kmx_bow* h, int32_t nq, int32_t K, int32_t mode, const kmx_bow_detect_params* p,
+                      const int* qids, const int* n, const int* ids, const double* scores, const double* nss,
+                      const int* has_prev, const int* qerr, int* state) {
+  char* out = h->d_dout;
+  kmx_bow_detect_record* rec = reinterpret_cast<kmx_bow_detect_record*>(out);
+  int* hdr = reinterpret_cast<int*>(out + det_hdr_off((size_t)nq));
+  int* cand = reinterpret_cast<int*>(out + det_cand_off((size_t)nq));
+  const BowDecide d{p->use_nss, p->alpha, p->min_nss_factor, p->max_intraisland_gap, p->min_matches_per_island};
+  hipLaunchKernelGGL(k_bow_decide, dim3(std::min(nq, 1 << 20)), dim3(DEC_WAVE), 0, h->stream, nq, K, mode, d, qids,
+                     n, ids, scores, nss, has_prev, rec, h->d_tin, h->d_hasprev + h->dcap, qerr, hdr);
+  KMX_HIP(hipGetLastError());
+  if (int rc = bow_time(h, 2)) return rc;
+  if (mode == KMX_BOW_MODE_INTRA) {
+    hipLaunchKernelGGL(k_bow_temporal, dim3(1), dim3(DEC_WAVE), 0, h->stream, nq, p->max_nrFrames_between_queries,
+                       p->max_nrFrames_between_islands, p->min_temporal_matches, (const int4*)h->d_tin,
+                       (const int*)(h->d_hasprev + h->dcap), rec, state,
+                       cand, hdr);
+    KMX_HIP(hipGetLastError());
+  }
+  if (int rc = bow_time(h, 3)) return rc;
+  KMX_HIP(hipMemcpyAsync(h->h_dout, out, det_bytes((size_t)nq), hipMemcpyDeviceToHost, h->stream));
+  h->det_nq = nq;
+  return KMX_OK;
+}
+
+int bow_fetch_decide(kmx_bow* h, int32_t nq, kmx_bow_detect_record* records_out, int32_t* cand_out,
+                     int32_t* n_cand_out) {
+  KMX_HIP(hipStreamSynchronize(h->stream));
+  const int* hdr = reinterpret_cast<const int*>(h->h_dout + det_hdr_off((size_t)nq));
+  KMX_CHECK(!hdr[1], KMX_EUNSUP, "too many exactly tied scores at the max_results cut");
+  const int nc = std::max(0, std::min(hdr[0], nq));
+  std::copy_n(reinterpret_cast<const kmx_bow_detect_record*>(h->h_dout), nq, records_out);
+  if (cand_out) std::copy_n(reinterpret_cast<const int*>(h->h_dout + det_cand_off((size_t)nq)), 2 * (size_t)nc, cand_out);
+  if (n_cand_out) *n_cand_out = nc;
+  return KMX_OK;
+}
+}  // namespace
+
+extern "C" int kmx_bow_detect_entries_async(kmx_bow* h, kmx_bow* src, int32_t nq, const int32_t* entry_ids,
+                                            int32_t mode, const kmx_bow_detect_params* params) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(h, KMX_EINVAL, "null handle");
+  if (!src) src = h;
+  std::string err;
+  if (int rc = kmx::bow_check_detect_params(params, mode, MAX_RESULTS, &err)) return kmx::fail(rc, err);
+  KMX_CHECK(h->d_ptr && src->d_ptr, KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
+  KMX_CHECK(nq >= 0 && (nq == 0 || entry_ids), KMX_EINVAL, "bad argument");
+  KMX_CHECK(src->device == h->device, KMX_EINVAL, "the source database is on another device");
+  KMX_CHECK(mode == KMX_BOW_MODE_INTER || src == h, KMX_EINVAL, "intra mode queries the database's own entries");
+  size_t nw = 0;
+  bool consecutive = true;  // a keyframe stream: the ids are made on the device, not uploaded
+  for (int q = 0; q < nq; ++q) {
+    KMX_CHECK(entry_ids[q] >= 0 && entry_ids[q] < src->n_entries, KMX_EINVAL, "entry id outside the source database");
+    nw += (size_t)(src->h_fptr[(size_t)entry_ids[q] + 1] - src->h_fptr[entry_ids[q]]);
+    consecutive = consecutive && entry_ids[q] - entry_ids[0] == q;
+  }
+  h->det_nq = -1;
+  if (nq == 0) {
+    h->det_nq = 0;
+    return KMX_OK;
+  }
+  const int32_t K = params->max_db_results;
+  const bool intra = mode == KMX_BOW_MODE_INTRA;
+  KMX_HIP(hipSetDevice(h->device));
+  int rc;
+  if ((rc = bow_reserve_queries(h, (size_t)nq, nw, K)) || (rc = bow_reserve_ids(h, (size_t)nq)) ||
+      (rc = bow_reserve_detect(h, (size_t)nq)))
+    return rc;
+  if (src != h && src->stream != h->stream) {  // after the adds enqueued on the source's stream
+    KMX_HIP(hipEventRecord(h->ev, src->stream));
+    KMX_HIP(hipStreamWaitEvent(h->stream, h->ev, 0));
+  }
+  if ((rc = bow_time(h, 0))) return rc;
+  if (!consecutive)
+    KMX_HIP(hipMemcpyAsync(h->d_eid, entry_ids, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
+  BowFwd f{src->d_fptr, src->d_fw, src->d_fv};
+  hipLaunchKernelGGL(k_bow_detect_prep, dim3((nq + 255) / 256), dim3(256), 0, h->stream, nq, mode,
+                     params->recent_frames_window, params->use_nss, f, entry_ids[0],
+                     consecutive ? (const int*)nullptr : (const int*)h->d_eid, h->d_eid, h->d_hasprev, h->d_maxid,
+                     h->d_eout);
+  KMX_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_bow_scan_len<1>, dim3(1), dim3(TL_BLOCK), 0, h->stream, nq, (const int*)h->d_eid, f.fptr,
+                     h->d_qptr);
+  KMX_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_bow_gather, dim3(nq), dim3(256), 0, h->stream, f, (const int*)h->d_eid,
+                     (const long long*)h->d_qptr, h->d_qw, h->d_qv);
+  KMX_HIP(hipGetLastError());
+  if ((rc = bow_launch_query(h, nq, intra, K))) return rc;
+  if ((rc = bow_time(h, 1))) return rc;
+  return bow_launch_decide(h, nq, K, mode, params, h->d_eid, h->d_n, h->d_id, h->d_score,
+                           params->use_nss ? h->d_eout : nullptr, h->d_hasprev, h->d_err, h->d_tstate);
+  KMX_GUARD_END
+}
+
+extern "C" int kmx_bow_detect_fetch(kmx_bow* h, int32_t nq, kmx_bow_detect_record* records_out, int32_t* cand_out,
+                                    int32_t* n_cand_out) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(h && nq >= 0 && (nq == 0 || records_out), KMX_EINVAL, "bad argument");
+  KMX_CHECK(nq == h->det_nq, KMX_EINVAL, "no enqueued detection of this size");
+  if (n_cand_out) *n_cand_out = 0;
+  if (nq == 0) return KMX_OK;
+  KMX_HIP(hipSetDevice(h->device));
+  return bow_fetch_decide(h, nq, records_out, cand_out, n_cand_out);
+  KMX_GUARD_END
+}
+
+extern "C" int kmx_bow_detect_entries(kmx_bow* h, kmx_bow* src, int32_t nq, const int32_t* entry_ids, int32_t mode,
+                                      const kmx_bow_detect_params* params, kmx_bow_detect_record* records_out,
+                                      int32_t* cand_out, int32_t* n_cand_out) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(nq <= 0 || records_out, KMX_EINVAL, "null output");
+  if (int rc = kmx_bow_detect_entries_async(h, src, nq, entry_ids, mode, params)) return rc;
+  return kmx_bow_detect_fetch(h, nq, records_out, cand_out, n_cand_out);
+  KMX_GUARD_END
+}
+
+extern "C" int kmx_bow_decide_results(kmx_bow* h, int32_t nq, int32_t K, const int32_t* query_ids, const int32_t* n,
+                                      const int32_t* ids, const double* scores, const double* nss,
+                                      const int32_t* has_prev, int32_t mode, const kmx_bow_detect_params* params,
+                                      int32_t use_state, kmx_bow_detect_record* records_out) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(h, KMX_EINVAL, "null handle");
+  std::string err;
+  if (int rc = kmx::bow_check_detect_params(params, mode, MAX_RESULTS, &err)) return kmx::fail(rc, err);
+  if (int rc = kmx::bow_check_result_counts(nq, K, MAX_RESULTS, n, &err)) return kmx::fail(rc, err);
+  if (nq == 0) return KMX_OK;
+  KMX_CHECK(ids && scores && records_out, KMX_EINVAL, "null argument");
+  KMX_HIP(hipSetDevice(h->device));
+  int rc;
+  if ((rc = bow_reserve_queries(h, (size_t)nq, 0, K)) || (rc = bow_reserve_ids(h, (size_t)nq)) ||
+      (rc = bow_reserve_detect(h, (size_t)nq)))
+    return rc;
+  const size_t rows = (size_t)nq * K;
+  KMX_HIP(hipMemcpyAsync(h->d_n, n, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->d_id, ids, sizeof(int) * rows, hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->d_score, scores, sizeof(double) * rows, hipMemcpyHostToDevice, h->stream));
+  if (query_ids) KMX_HIP(hipMemcpyAsync(h->d_eid, query_ids, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
+  if (nss) KMX_HIP(hipMemcpyAsync(h->d_eout, nss, sizeof(double) * nq, hipMemcpyHostToDevice, h->stream));
+  if (has_prev) KMX_HIP(hipMemcpyAsync(h->d_hasprev, has_prev, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
+  int* state = h->d_tstate;
+  if (!use_state) {  // a pass of its own: from zeros, in the scratch half
+    state += 4;
+    KMX_HIP(hipMemsetAsync(state, 0, 4 * sizeof(int), h->stream));
+  }
+  if ((rc = bow_time(h, 0)) || (rc = bow_time(h, 1))) return rc;
+  if ((rc = bow_launch_decide(h, nq, K, mode, params, query_ids ? h->d_eid : nullptr, h->d_n, h->d_id, h->d_score,
+                              nss ? h->d_eout : nullptr, has_prev ? h->d_hasprev : nullptr, nullptr, state)))
+    return rc;
+  return bow_fetch_decide(h, nq, records_out, nullptr, nullptr);
+  KMX_GUARD_END
+}
+
+extern "C" int kmx_bow_get_temporal_state(kmx_bow* h, int32_t* state4_out) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(h && state4_out, KMX_EINVAL, "null argument");
+  KMX_HIP(hipSetDevice(h->device));
+  KMX_HIP(hipMemcpyAsync(state4_out, h->d_tstate, 4 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipStreamSynchronize(h->stream));
+  return KMX_OK;
+  KMX_GUARD_END
+}
+
+extern "C" int kmx_bow_set_temporal_state(kmx_bow* h, const int32_t* state4) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(h && state4, KMX_EINVAL, "null argument");
+  KMX_HIP(hipSetDevice(h->device));
+  KMX_HIP(hipMemcpyAsync(h->d_tstate, state4, 4 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipStreamSynchronize(h->stream));  // the caller's array is free again
+  return KMX_OK;
+  KMX_GUARD_END
+}
+
+extern "C" int kmx_bow_enable_timing(kmx_bow* h, int on) {
+  KMX_CHECK(h, KMX_EINVAL, "null handle");
+  h->timing = on != 0;
+  return KMX_OK;
+}
+
+extern "C" int kmx_bow_read_detect_timing(kmx_bow* h, double* ms3_out) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(h && ms3_out, KMX_EINVAL, "null argument");
+  KMX_CHECK(h->timing && h->tev[0] && h->tev[1] && h->tev[2] && h->tev[3], KMX_ESTATE,
+            "no detection was enqueued with timing on");
+  KMX_HIP(hipSetDevice(h->device));
+  KMX_HIP(hipStreamSynchronize(h->stream));
+  for (int k = 0; k < 3; ++k) {
+    float ms = 0.f;
+    KMX_HIP(hipEventElapsedTime(&ms, h->tev[k], h->tev[k + 1]));
+    ms3_out[k] = ms;
+  }
   return KMX_OK;
   KMX_GUARD_END
 }

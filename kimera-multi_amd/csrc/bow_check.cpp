@@ -1,10 +1,14 @@
 // bow_check.cpp — bow.hip's host code (bow_host.h: the CSR validation of
-// kmx_bow_add_entries) as a stand-alone program, built by `make bow_check`
-// with the host address and undefined-behaviour sanitizers. It feeds
+// kmx_bow_add_entries, the parameter and shape checks of kmx_bow_detect_entries
+// and kmx_bow_decide_results) as a stand-alone program, built by `make
+// bow_check` with the host address and undefined-behaviour sanitizers. It feeds
 // kmx::bow_check_csr the inputs kmx_bow_add_entries must reject, in arrays of
-// exactly the stated size so that a read past either is a report. CPU only.
+// exactly the stated size so that a read past either is a report, and
+// kmx::bow_check_detect_params / bow_check_result_counts malformed parameter
+// sets and counts. CPU only.
 #include <climits>
 #include <cstdio>
+#include <limits>
 #include <random>
 #include <string>
 #include <vector>
@@ -26,6 +30,25 @@ void expect_code(int32_t n_words, int64_t n_now, int64_t post_now, const std::ve
                                     w.empty() ? nullptr : w.data(), &err);
   if (rc != code || (code != KMX_OK && err.find(what) == std::string::npos)) {
     std::fprintf(stderr, "expected %d (%s), got %d (%s)\n", code, what, rc, err.c_str());
+    ++g_fail;
+  }
+}
+
+void expect_params(const kmx_bow_detect_params* p, int32_t mode, int code, const char* what) {
+  std::string err;
+  const int rc = kmx::bow_check_detect_params(p, mode, 256, &err);
+  if (rc != code || (code != KMX_OK && err.find(what) == std::string::npos)) {
+    std::fprintf(stderr, "params: expected %d (%s), got %d (%s)\n", code, what, rc, err.c_str());
+    ++g_fail;
+  }
+}
+
+void expect_counts(int32_t K, const std::vector<int32_t>& n, int code, const char* what) {
+  std::vector<int32_t> c(n);  // exactly nq ints
+  std::string err;
+  const int rc = kmx::bow_check_result_counts((int64_t)c.size(), K, 256, c.empty() ? nullptr : c.data(), &err);
+  if (rc != code || (code != KMX_OK && err.find(what) == std::string::npos)) {
+    std::fprintf(stderr, "counts: expected %d (%s), got %d (%s)\n", code, what, rc, err.c_str());
     ++g_fail;
   }
 }
@@ -78,10 +101,66 @@ int main() {
       expect_code(n_words, rep, rep * 7, vptr, broken, KMX_EINVAL, "word id >= n_words");
     }
   }
+  // ---- the detection parameters (kmx_bow_detect_entries / kmx_bow_decide_results)
+  const kmx_bow_detect_params good{1, 0.4, 0.05, 50, 100, 3, 1, 2, 3, 1};
+  expect_params(&good, KMX_BOW_MODE_INTRA, KMX_OK, "");
+  expect_params(&good, KMX_BOW_MODE_INTER, KMX_OK, "");
+  expect_params(nullptr, KMX_BOW_MODE_INTRA, KMX_EINVAL, "null params");
+  expect_params(&good, 2, KMX_EINVAL, "mode");
+  expect_params(&good, -1, KMX_EINVAL, "mode");
+  int n_params = 0;
+  auto with = [&](auto set, const char* what) {
+    kmx_bow_detect_params p = good;
+    set(p);
+    expect_params(&p, KMX_BOW_MODE_INTRA, what[0] ? KMX_EINVAL : KMX_OK, what);
+    ++n_params;
+  };
+  const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+  with([](kmx_bow_detect_params& p) { p.max_db_results = 0; }, "max_db_results");
+  with([](kmx_bow_detect_params& p) { p.max_db_results = 257; }, "max_db_results");
+  with([](kmx_bow_detect_params& p) { p.max_db_results = -1; }, "max_db_results");
+  with([](kmx_bow_detect_params& p) { p.max_db_results = INT32_MAX; }, "max_db_results");
+  with([](kmx_bow_detect_params& p) { p.max_db_results = 1; }, "");
+  with([](kmx_bow_detect_params& p) { p.max_db_results = 256; }, "");
+  with([](kmx_bow_detect_params& p) { p.use_nss = 2; }, "use_nss");
+  with([](kmx_bow_detect_params& p) { p.use_nss = -1; }, "use_nss");
+  with([](kmx_bow_detect_params& p) { p.use_nss = 0; }, "");
+  with([&](kmx_bow_detect_params& p) { p.alpha = inf; }, "alpha");
+  with([&](kmx_bow_detect_params& p) { p.alpha = -inf; }, "alpha");
+  with([&](kmx_bow_detect_params& p) { p.alpha = nan; }, "alpha");
+  with([](kmx_bow_detect_params& p) { p.alpha = 0.0; }, "");
+  with([&](kmx_bow_detect_params& p) { p.min_nss_factor = nan; }, "min_nss_factor");
+  with([&](kmx_bow_detect_params& p) { p.min_nss_factor = inf; }, "min_nss_factor");
+  with([](kmx_bow_detect_params& p) { p.recent_frames_window = -1; }, "recent_frames_window");
+  with([](kmx_bow_detect_params& p) { p.recent_frames_window = 0; }, "");
+  with([](kmx_bow_detect_params& p) { p.max_intraisland_gap = -3; }, "max_intraisland_gap");
+  with([](kmx_bow_detect_params& p) { p.min_matches_per_island = INT32_MIN; }, "min_matches_per_island");
+  with([](kmx_bow_detect_params& p) { p.max_nrFrames_between_queries = -1; }, "max_nrFrames_between_queries");
+  with([](kmx_bow_detect_params& p) { p.max_nrFrames_between_queries = 0; }, "");
+  with([](kmx_bow_detect_params& p) { p.max_nrFrames_between_islands = -1; }, "max_nrFrames_between_islands");
+  with([](kmx_bow_detect_params& p) { p.min_temporal_matches = -1; }, "min_temporal_matches");
+  with([](kmx_bow_detect_params& p) { p.min_temporal_matches = 0; }, "");
+  // the result counts of kmx_bow_decide_results, in an array of exactly nq
+  expect_counts(7, {}, KMX_OK, "");
+  expect_counts(7, {0, 7, 3}, KMX_OK, "");
+  expect_counts(7, {0, 8, 3}, KMX_EINVAL, "outside [0, K]");
+  expect_counts(7, {0, 7, -1}, KMX_EINVAL, "outside [0, K]");
+  expect_counts(0, {0}, KMX_EINVAL, "K must be");
+  expect_counts(257, {0}, KMX_EINVAL, "K must be");
+  expect_counts(256, {256}, KMX_OK, "");
+  {
+    std::string err;
+    if (kmx::bow_check_result_counts(3, 7, 256, nullptr, &err) != KMX_EINVAL ||
+        kmx::bow_check_result_counts(-1, 7, 256, nullptr, &err) != KMX_EINVAL ||
+        kmx::bow_check_result_counts((int64_t)INT32_MAX, 7, 256, nullptr, &err) != KMX_EINVAL) {
+      std::fprintf(stderr, "null or absurd result counts were not refused\n");
+      ++g_fail;
+    }
+  }
   if (g_fail) {
     std::fprintf(stderr, "bow_check: %d failure(s)\n", g_fail);
     return 1;
   }
-  std::printf("bow_check ok: %d random batches, malformed batches rejected\n", batches);
+  std::printf("bow_check ok: %d random batches, malformed batches rejected; %d parameter sets\n", batches, n_params);
   return 0;
 }

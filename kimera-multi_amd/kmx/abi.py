@@ -133,6 +133,30 @@ class ChordalBlockInfo(C.Structure):
                 ("relres_rot", C.c_double * 3), ("relres_trans", C.c_double * 3)]
 
 
+class BowDetectParams(C.Structure):
+    """kmx_bow_detect_params (LcdParams.yaml:3-12)."""
+    _fields_ = [("use_nss", C.c_int32), ("alpha", C.c_double), ("min_nss_factor", C.c_double),
+                ("max_db_results", C.c_int32), ("recent_frames_window", C.c_int32),
+                ("max_intraisland_gap", C.c_int32), ("min_matches_per_island", C.c_int32),
+                ("max_nrFrames_between_queries", C.c_int32), ("max_nrFrames_between_islands", C.c_int32),
+                ("min_temporal_matches", C.c_int32)]
+
+
+class BowDetectRecord(C.Structure):
+    """kmx_bow_detect_record: one per query of a device-side detection (48 bytes)."""
+    _fields_ = [("query_id", C.c_int32), ("status", C.c_int32), ("match_id", C.c_int32), ("n_kept", C.c_int32),
+                ("island_start", C.c_int32), ("island_end", C.c_int32), ("score", C.c_double), ("nss", C.c_double),
+                ("island_score", C.c_double)]
+
+
+# the same layout for numpy: np.zeros(nq, BOW_RECORD_DTYPE) is a kmx_bow_detect_record[nq]
+BOW_RECORD_DTYPE = np.dtype([(n, np.int32 if t is C.c_int32 else np.float64) for n, t in BowDetectRecord._fields_])
+assert BOW_RECORD_DTYPE.itemsize == C.sizeof(BowDetectRecord) == 48
+
+# kmx_abi.h: the status enum in its order, and the two modes
+BOW_STATUS = ("NO_MATCHES", "LOW_NSS_FACTOR", "LOW_SCORE", "NO_GROUPS", "FAILED_TEMPORAL_CONSTRAINT", "LOOP_DETECTED")
+BOW_MODE_INTRA, BOW_MODE_INTER = 0, 1
+
 _lib = None
 
 
@@ -240,6 +264,16 @@ def lib() -> C.CDLL:
         "kmx_bow_query_entries_async": ([P, P, i32, pi32, pi32, i32], C.c_int),
         "kmx_bow_fetch": ([P, i32, i32, pi32, pi32, pf64], C.c_int),
         "kmx_bow_score_entries": ([P, i32, pi32, pi32, pf64], C.c_int),
+        "kmx_bow_detect_entries": ([P, P, i32, pi32, i32, C.POINTER(BowDetectParams), C.POINTER(BowDetectRecord),
+                                    pi32, pi32], C.c_int),
+        "kmx_bow_detect_entries_async": ([P, P, i32, pi32, i32, C.POINTER(BowDetectParams)], C.c_int),
+        "kmx_bow_detect_fetch": ([P, i32, C.POINTER(BowDetectRecord), pi32, pi32], C.c_int),
+        "kmx_bow_decide_results": ([P, i32, i32, pi32, pi32, pi32, pf64, pf64, pi32, i32,
+                                    C.POINTER(BowDetectParams), i32, C.POINTER(BowDetectRecord)], C.c_int),
+        "kmx_bow_get_temporal_state": ([P, pi32], C.c_int),
+        "kmx_bow_set_temporal_state": ([P, pi32], C.c_int),
+        "kmx_bow_enable_timing": ([P, C.c_int], C.c_int),
+        "kmx_bow_read_detect_timing": ([P, pf64], C.c_int),
         "kmx_voc_create": ([C.c_int, i32, pi32, pu8, pf64, i32, pi32, C.c_int, C.POINTER(P)], C.c_int),
         "kmx_voc_destroy": ([P], C.c_int),
         "kmx_voc_set_stream": ([P, P], C.c_int),

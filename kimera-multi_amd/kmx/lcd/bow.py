@@ -21,6 +21,13 @@ drawio:1565) on top of kmx_bow_* (C ABI, bow.hip):
                              max_id = frame - recent_frames_window, nss / alpha
                              cut, computeIslands, checkTemporalConstraint
                              (sequential control on the host, queries batched)
+  BowDatabase.detect_entries / decide_results / temporal_state,
+  BowDetector.detectLoopStream / detectLoopStreamCandidates /
+  detectLoopWithRobotDevice  the same decisions made on the device
+                             (kmx_bow_detect_entries): one record per keyframe
+                             comes back, the temporal constraint's state stays
+                             in the database across calls, so one keyframe per
+                             call gives what one call over the stream gives
 
 Constants are LcdParams (params/D455/LcdParams.yaml:3-12). DBoW2 and
 kimera_multi_lcd are not vendored: the restatement is "parity unpinned" and
@@ -162,6 +169,75 @@ class BowDatabase:
         out = np.zeros(a.shape[0])
         check(self.L.kmx_bow_score_entries(self.h, a.shape[0], iptr(a), iptr(b), fptr(out)), "kmx_bow_score_entries")
         return out
+
+    # ---- detectLoop / detectLoopWithRobot decided on the device
+    def detect_entries(self, ids, params: "abi.BowDetectParams", mode: int = abi.BOW_MODE_INTRA, src=None):
+        """kmx_bow_detect_entries: query, nss gate, alpha cut, islands and (intra
+        mode) the temporal constraint for stored entries `ids` of `src` (None:
+        this database), decided on the device. Returns (records, candidates):
+        a numpy array of abi.BOW_RECORD_DTYPE, one per query, and the int32
+        [n, 2] (query id, match id) pairs of the LOOP_DETECTED records (intra
+        mode). The temporal state stays in the database across calls."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        nq = ids.shape[0]
+        rec = np.zeros(nq, abi.BOW_RECORD_DTYPE)
+        cand = np.zeros((max(nq, 1), 2), np.int32)
+        nc = C.c_int32(0)
+        check(self.L.kmx_bow_detect_entries(self.h, (src or self).h, nq, iptr(ids), int(mode), C.byref(params),
+                                            rec.ctypes.data_as(C.POINTER(abi.BowDetectRecord)), iptr(cand),
+                                            C.byref(nc)), "kmx_bow_detect_entries")
+        return rec, cand[:nc.value].copy()
+
+    def decide_results(self, n, ids, scores, params: "abi.BowDetectParams", nss=None, has_prev=None,
+                       query_ids=None, mode: int = abi.BOW_MODE_INTRA, use_state: bool = False):
+        """kmx_bow_decide_results: the same decision on query results the caller
+        holds (n [nq], ids / scores [nq, K] sorted by score descending, lower id
+        first on ties). use_state: run the temporal pass on the database's
+        state instead of from zeros. Returns the records."""
+        n = np.ascontiguousarray(n, np.int32)
+        ids = np.ascontiguousarray(ids, np.int32)
+        scores = np.ascontiguousarray(scores, np.float64)
+        nq = n.shape[0]
+        if ids.ndim != 2 or ids.shape != scores.shape or ids.shape[0] != nq:
+            raise ValueError("ids and scores must be [nq, K]")
+        opt = [None if a is None else np.ascontiguousarray(a, t)
+               for a, t in ((query_ids, np.int32), (nss, np.float64), (has_prev, np.int32))]
+        if any(a is not None and a.shape != (nq,) for a in opt):
+            raise ValueError("query_ids, nss and has_prev must be [nq]")
+        qid, ns, hp = opt
+        rec = np.zeros(nq, abi.BOW_RECORD_DTYPE)
+        check(self.L.kmx_bow_decide_results(self.h, nq, ids.shape[1], iptr(qid) if qid is not None else None, iptr(n),
+                                            iptr(ids), fptr(scores), fptr(ns) if ns is not None else None,
+                                            iptr(hp) if hp is not None else None, int(mode), C.byref(params),
+                                            1 if use_state else 0,
+                                            rec.ctypes.data_as(C.POINTER(abi.BowDetectRecord))),
+              "kmx_bow_decide_results")
+        return rec
+
+    @property
+    def temporal_state(self):
+        """The temporal constraint's state on the device: int32 [4] =
+        (temporal entries, latest query id, latest island start, end)."""
+        st = np.zeros(4, np.int32)
+        check(self.L.kmx_bow_get_temporal_state(self.h, iptr(st)), "kmx_bow_get_temporal_state")
+        return st
+
+    @temporal_state.setter
+    def temporal_state(self, state):
+        st = np.ascontiguousarray(state, np.int32)
+        if st.shape != (4,):
+            raise ValueError("the temporal state is 4 integers")
+        check(self.L.kmx_bow_set_temporal_state(self.h, iptr(st)), "kmx_bow_set_temporal_state")
+
+    def enable_timing(self, on: bool = True):
+        check(self.L.kmx_bow_enable_timing(self.h, 1 if on else 0), "kmx_bow_enable_timing")
+
+    def detect_timing(self):
+        """Milliseconds of the last detection call with timing on:
+        (gather + query + nss, k_bow_decide, k_bow_temporal)."""
+        ms = np.zeros(3)
+        check(self.L.kmx_bow_read_detect_timing(self.h, fptr(ms)), "kmx_bow_read_detect_timing")
+        return ms
 
     def query(self, qptr, words, weights, max_results: int = 50, max_id=None):
         """queryL1 of each query vector -> (n [nq], ids [nq, K], scores [nq, K])."""
@@ -414,6 +490,53 @@ class BowDetector:
         n, ids, sc = db.query_entries(fids, p.max_db_results, max_id)
         nss_tail = db.score_entries(fids[1:], fids[:-1]) if n_frames > 1 else np.zeros(0)
         return self._stream_decisions(fids, n, ids, sc, nss_tail)
+
+    # ---- decided on the device: one record per keyframe comes back
+    def detect_params(self) -> "abi.BowDetectParams":
+        """The BoW detection fields of the detector's LcdParams as kmx_bow_detect_params."""
+        p = self.p
+        return abi.BowDetectParams(int(p.use_nss), float(p.alpha), float(p.min_nss_factor), int(p.max_db_results),
+                                   int(p.recent_frames_window), int(p.max_intraisland_gap),
+                                   int(p.min_matches_per_island), int(p.max_nrFrames_between_queries),
+                                   int(p.max_nrFrames_between_islands), int(p.min_temporal_matches))
+
+    def detectLoopStream(self, robot: int, first_frame: int, n_frames: int, reset: bool = False,
+                         candidates: bool = False):
+        """detectLoop over entries first_frame .. first_frame + n_frames - 1 of
+        `robot`'s database, decided on the device (kmx_bow_detect_entries): the
+        list of (frame, status, match, score) detectLoopResident returns, from
+        one 48-byte record per keyframe. The temporal constraint's state lives
+        in the database and carries across calls, and a keyframe's previous
+        keyframe is the entry before it, so a stream fed in any split, one
+        keyframe per call included, gets the answers of one call over all of
+        it. reset=True starts a new stream (zero state) first.
+
+        The one difference from detectLoopResident: there, the first keyframe
+        of every call has no previous keyframe and is LOW_NSS_FACTOR when
+        use_nss is set; here only entry 0 is, since the previous keyframe of a
+        window starting at first_frame > 0 is entry first_frame - 1 of the
+        database. candidates=True returns (list, int32 [n, 2] array of the
+        LOOP_DETECTED (query, match) pairs) instead."""
+        db = self.db[robot]
+        if reset:
+            db.temporal_state = np.zeros(4, np.int32)
+        fids = np.arange(first_frame, first_frame + n_frames, dtype=np.int32)
+        rec, cand = db.detect_entries(fids, self.detect_params(), abi.BOW_MODE_INTRA)
+        out = [(int(q), abi.BOW_STATUS[s], int(m), float(sc))
+               for q, s, m, sc in zip(rec["query_id"], rec["status"], rec["match_id"], rec["score"])]
+        return (out, cand) if candidates else out
+
+    def detectLoopStreamCandidates(self, robot: int, first_frame: int, n_frames: int, reset: bool = False):
+        """detectLoopStream's compact result: the (query, match) pairs of the
+        LOOP_DETECTED keyframes, in order (what the verification stage takes)."""
+        return self.detectLoopStream(robot, first_frame, n_frames, reset, candidates=True)[1]
+
+    def detectLoopWithRobotDevice(self, robot: int, query_robot: int, query_ids):
+        """detectLoopWithRobotResident decided on the device: the same
+        (match entry id or -1, score, nss) arrays from one record per query."""
+        db, src = self.db[robot], self.db[query_robot]
+        rec, _ = db.detect_entries(query_ids, self.detect_params(), abi.BOW_MODE_INTER, src=src)
+        return rec["match_id"].copy(), rec["score"].copy(), rec["nss"].copy()
 
     def detectLoopWithRobotResident(self, robot: int, query_robot: int, query_ids):
         """detectLoopWithRobot with the queries = entries `query_ids` of
