@@ -40,7 +40,8 @@ extern "C" {
 #define KMX_EHIP (-2)     /* HIP runtime error */
 #define KMX_ESTATE (-3)   /* call out of order (e.g. iterate before set_graph) */
 #define KMX_ENOMEM (-4)
-#define KMX_EUNSUP (-5)   /* unsupported parameter value (e.g. relaxation rank) */
+#define KMX_EUNSUP (-5)   /* unsupported parameter value (e.g. relaxation rank), or an
+                              input past a fixed capacity (kmx_bow_query: tied scores) */
 #define KMX_ETIMEOUT (-6) /* a bounded wait expired (kmx_pgo_sync_timeout)       */
 
 const char* kmx_last_error(void);
@@ -559,24 +560,51 @@ int kmx_lcd_read_timing(kmx_lcd* h, double* knn_ms, double* ransac_ms);
  * LoopClosureDetector::detectLoop / detectLoopWithRobot (drawio:2574-2580,
  * 2612-2633; LcdParams.yaml:3-12). BowVectors are CSR: vptr[n+1] (int64),
  * words (uint32, strictly increasing per vector) and weights (L1-normalised
- * double). Entry id = position in the database. */
+ * double). Entry id = position in the database.
+ *
+ * Weights. Every weight of a BowVector is finite and > 0 (DBoW2 stores no
+ * other: `if (w > 0) addWeight`, then the L1 normalisation). The query reads
+ * an accumulator of exactly 0.0 as "entry not touched yet", which holds because
+ * every contribution |q - d| - |q| - |d| of such weights is negative. Database
+ * vectors are checked on the host (kmx_bow_set_database, kmx_bow_add_entries:
+ * KMX_EINVAL, the database unchanged); for query vectors passed as host arrays
+ * the same rule is the caller's contract and is not checked.
+ *
+ * KMX_EUNSUP from a query. The best max_results entries are selected without
+ * sorting the database: up to 6 histogram passes of 1024 bins narrow the range
+ * [-2, 0] of the accumulator (cell widths 2^-9, 2^-19, ..., 2^-59) until the
+ * entries certainly selected plus the cell holding the cut fit a sort buffer of
+ * 2048 entries (KMX_BOW_LDS=0), or of 1024 entries per chunk of at most 14336
+ * consecutive entry ids (the default; KMX_BOW_CHUNK sets a smaller chunk,
+ * rounded up to a multiple of 16). The unsealed tail (<= 1024 entries) has room
+ * of its own. Cells of width 2^-59 separate all distinct scores >= 0.5, so the
+ * selection fails only when more entries than a buffer holds have (nearly)
+ * identical scores and the cut falls among them: a tie group that lies wholly
+ * behind the cut does not count. Then the call returns KMX_EUNSUP and its
+ * outputs are unspecified; the database is unchanged and the handle stays
+ * usable: the next call is answered as if the failed one had not been made. */
 typedef struct kmx_bow kmx_bow;
 int kmx_bow_create(int device, kmx_bow** out);
 int kmx_bow_destroy(kmx_bow* h);
 int kmx_bow_set_stream(kmx_bow* h, void* hip_stream);
-/* Build the inverted file of entries 0..n_entries-1 (Database::add in order). */
+/* Build the inverted file of entries 0..n_entries-1 (Database::add in order).
+ * The vectors are checked on the host before any device call, the database
+ * unchanged on failure: KMX_EINVAL as for kmx_bow_add_entries. */
 int kmx_bow_set_database(kmx_bow* h, int32_t n_words, int32_t n_entries,
                          const int64_t* vptr, const uint32_t* words,
                          const double* weights);
 /* queryL1 for nq query vectors: results with entry id < max_id[q] (NULL or
  * -1: all), sorted by score descending (ties: lower entry id first), at most
  * max_results (<= 256) each. out_n[nq]; out_ids / out_scores [nq][max_results];
- * score = 1 - 1/2 |v - w|_1. */
+ * score = 1 - 1/2 |v - w|_1. KMX_EUNSUP (above): too many tied scores at the cut
+ * of some query for the sort buffer (2048 entries, or 1024 per chunk); the
+ * outputs are unspecified and the handle stays usable. */
 int kmx_bow_query(kmx_bow* h, int32_t nq, const int64_t* qptr,
                   const uint32_t* words, const double* weights,
                   const int32_t* max_id, int32_t max_results, int32_t* out_n,
                   int32_t* out_ids, double* out_scores);
-/* Enqueue only (benchmark path); kmx_bow_sync waits. */
+/* Enqueue only (benchmark path); kmx_bow_sync waits, kmx_bow_fetch waits and
+ * reports. */
 int kmx_bow_query_async(kmx_bow* h, int32_t nq, const int64_t* qptr,
                         const uint32_t* words, const double* weights,
                         const int32_t* max_id, int32_t max_results);
@@ -602,15 +630,16 @@ int kmx_bow_reset(kmx_bow* h, int32_t n_words);
 /* Database::add of n host vectors in order; the first gets id n_entries
  * (*first_id_out, may be NULL). Checked on the host before any device call,
  * the database unchanged on failure: KMX_EINVAL for a non-monotone vptr, words
- * not strictly increasing, a word >= n_words, or totals >= INT32_MAX;
- * KMX_ESTATE without a database. An empty vector is a legal entry. */
+ * not strictly increasing, a word >= n_words, a weight that is not finite and
+ * > 0 (zero, -0.0, negative, NaN, infinite; a denormal is legal), null weights
+ * with words present, or totals >= INT32_MAX; KMX_ESTATE without a database. An empty vector is a legal entry. */
 int kmx_bow_add_entries(kmx_bow* h, int32_t n, const int64_t* vptr,
                         const uint32_t* words, const double* weights,
                         int32_t* first_id_out);
 /* Append the vectors voc's last kmx_voc_transform*[_async] left on the device,
  * ordered after voc's stream; no word or weight passes through the host.
  * KMX_EINVAL when voc's word count differs from the database's; KMX_ESTATE
- * when voc holds no batch. */
+ * when voc holds no batch. The transform emits positive finite weights only. */
 int kmx_bow_add_from_voc(kmx_bow* h, struct kmx_voc* voc, int32_t* first_id_out, int32_t* n_out);
 /* Move the tail into the inverted file now (on the device). An add seals by
  * itself when the tail holds more than tail_cap entries. */
@@ -629,7 +658,8 @@ int kmx_bow_get_entries(kmx_bow* h, int32_t first, int32_t n, int64_t* vptr_out,
 /* kmx_bow_query with query q = stored entry entry_ids[q] of src (src may be h
  * or another database on the same device); ordered after src's stream; no
  * query words are uploaded. src's forward store must not grow while a query
- * that reads it is in flight. */
+ * that reads it is in flight. KMX_EUNSUP as for kmx_bow_query (buffers of 2048
+ * entries, or 1024 per chunk); the handle stays usable. */
 int kmx_bow_query_entries(kmx_bow* h, kmx_bow* src, int32_t nq, const int32_t* entry_ids,
                           const int32_t* max_id, int32_t max_results, int32_t* out_n,
                           int32_t* out_ids, double* out_scores);
@@ -637,7 +667,10 @@ int kmx_bow_query_entries_async(kmx_bow* h, kmx_bow* src, int32_t nq,
                                 const int32_t* entry_ids, const int32_t* max_id,
                                 int32_t max_results);
 /* Wait for the last kmx_bow_query_async / kmx_bow_query_entries_async (same nq
- * and max_results) and copy its results out, as the synchronous forms do. */
+ * and max_results) and copy its results out, as the synchronous forms do:
+ * KMX_EUNSUP when that query's selection failed (buffers of 2048 entries, or
+ * 1024 per chunk); the handle stays usable, and a later query and its fetch
+ * are unaffected. */
 int kmx_bow_fetch(kmx_bow* h, int32_t nq, int32_t max_results, int32_t* out_n,
                   int32_t* out_ids, double* out_scores);
 /* L1Scoring::score of stored entries (a_ids[i], b_ids[i]) of src; an id of -1
@@ -706,14 +739,20 @@ typedef struct {
  * cand_out (may be NULL) holds (query id, match id) of every LOOP_DETECTED in
  * query order, room for 2 * nq ints; *n_cand_out their count (intra mode; 0
  * in inter mode). KMX_EINVAL for bad params or an entry id outside src,
- * KMX_ESTATE without a database; the handle stays usable. */
+ * KMX_ESTATE without a database; the handle stays usable.
+ * KMX_EUNSUP when the selection of some query of the call failed (as for
+ * kmx_bow_query: buffers of 2048 entries, or 1024 per chunk): no record or
+ * candidate is written, the temporal pass does not run, so the temporal state
+ * is what it was before the call, and the handle stays usable. */
 int kmx_bow_detect_entries(kmx_bow* h, kmx_bow* src, int32_t nq, const int32_t* entry_ids,
                            int32_t mode, const kmx_bow_detect_params* params,
                            kmx_bow_detect_record* records_out, int32_t* cand_out,
                            int32_t* n_cand_out);
 int kmx_bow_detect_entries_async(kmx_bow* h, kmx_bow* src, int32_t nq, const int32_t* entry_ids,
                                  int32_t mode, const kmx_bow_detect_params* params);
-/* Wait for the last kmx_bow_detect_entries_async (same nq) and copy out. */
+/* Wait for the last kmx_bow_detect_entries_async (same nq) and copy out.
+ * KMX_EUNSUP as for kmx_bow_detect_entries: nothing is written, the temporal
+ * state is untouched by the failed call, the handle stays usable. */
 int kmx_bow_detect_fetch(kmx_bow* h, int32_t nq, kmx_bow_detect_record* records_out,
                          int32_t* cand_out, int32_t* n_cand_out);
 /* The same decision on caller-supplied query results: n[nq], ids / scores
@@ -724,7 +763,10 @@ int kmx_bow_detect_fetch(kmx_bow* h, int32_t nq, kmx_bow_detect_record* records_
  * constraint sees; nss[nq] and has_prev[nq] (either may be NULL: 1.0 / all 1)
  * the nss factors and whether a previous keyframe exists. use_state != 0: the
  * temporal pass starts from the handle's state and leaves it updated; 0: it
- * starts from zeros and the handle's state is untouched. */
+ * starts from zeros and the handle's state is untouched. No selection runs
+ * here (the results are the caller's), so this call has no sort buffer to
+ * overflow and never returns KMX_EUNSUP; a caller that got KMX_EUNSUP from a
+ * query has no results to pass. */
 int kmx_bow_decide_results(kmx_bow* h, int32_t nq, int32_t K, const int32_t* query_ids,
                            const int32_t* n, const int32_t* ids, const double* scores,
                            const double* nss, const int32_t* has_prev, int32_t mode,

@@ -1054,6 +1054,10 @@ __global__ __launch_bounds__(DEC_WAVE) void k_bow_temporal(int nq, int max_betwe
                                                            kmx_bow_detect_record* rec, int* state, int* cand,
                                                            int* hdr) {
   const int lane = threadIdx.x;
+  // A query kernel raised its flag (k_bow_decide copied it to hdr[1]): the rows
+  // are an incomplete selection and the call returns KMX_EUNSUP, so the state
+  // stays what it was. hdr[0] is 0 from k_bow_decide. The whole wave leaves.
+  if (hdr[1] != 0) return;
   int te = __builtin_amdgcn_readfirstlane(state[0]);
   int lq = __builtin_amdgcn_readfirstlane(state[1]);
   int a1 = __builtin_amdgcn_readfirstlane(state[2]);
@@ -1466,19 +1470,16 @@ extern "C" int kmx_bow_set_database(kmx_bow* h, int32_t n_words, int32_t n_entri
                                     const uint32_t* words, const double* weights) {
   KMX_GUARD_BEGIN
   KMX_CHECK(h && vptr && n_words > 0 && n_entries >= 0, KMX_EINVAL, "bad argument");
+  {  // before any device call: a refused database leaves the handle as it was
+    std::string err;
+    if (int rc = kmx::bow_check_csr(n_words, 0, 0, n_entries, vptr, words, weights, &err)) return kmx::fail(rc, err);
+  }
   KMX_HIP(hipSetDevice(h->device));
   KMX_HIP(hipStreamSynchronize(h->stream));
   const int64_t nnz = vptr[n_entries];
   KMX_CHECK(nnz >= 0 && nnz < INT32_MAX, KMX_EINVAL, "database too large (postings must fit int32)");
   std::vector<int> ptr((size_t)n_words + 1, 0);
-  for (int e = 0; e < n_entries; ++e) {
-    KMX_CHECK(vptr[e + 1] >= vptr[e], KMX_EINVAL, "vptr not monotone");
-    for (int64_t k = vptr[e]; k < vptr[e + 1]; ++k) {
-      KMX_CHECK(words[k] < (uint32_t)n_words, KMX_EINVAL, "word id >= n_words");
-      KMX_CHECK(k == vptr[e] || words[k] > words[k - 1], KMX_EINVAL, "BowVector words must be strictly increasing");
-      ptr[words[k] + 1]++;
-    }
-  }
+  for (int64_t k = vptr[0]; k < vptr[n_entries]; ++k) ptr[words[k] + 1]++;  // words checked above
   for (int w = 0; w < n_words; ++w) ptr[w + 1] += ptr[w];
   std::vector<int> fill(ptr.begin(), ptr.end() - 1), ent(std::max<int64_t>(nnz, 1));
   std::vector<double> wt(std::max<int64_t>(nnz, 1));
@@ -1607,12 +1608,11 @@ extern "C" int kmx_bow_add_entries(kmx_bow* h, int32_t n, const int64_t* vptr, c
   KMX_CHECK(h, KMX_EINVAL, "null handle");
   KMX_CHECK(h->d_ptr, KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
   std::string err;
-  if (int rc = kmx::bow_check_csr(h->n_words, h->n_entries, h->h_fptr.back(), n, vptr, words, &err))
+  if (int rc = kmx::bow_check_csr(h->n_words, h->n_entries, h->h_fptr.back(), n, vptr, words, weights, &err))
     return kmx::fail(rc, err);
   if (first_id_out) *first_id_out = h->n_entries;
   if (n == 0) return KMX_OK;
   const int64_t total = vptr[n] - vptr[0], base = h->h_fptr.back();
-  KMX_CHECK(total == 0 || weights, KMX_EINVAL, "null weights");
   KMX_HIP(hipSetDevice(h->device));
   if (int rc = bow_fwd_reserve(h, (size_t)h->n_entries + n, (size_t)(base + total))) return rc;
   const size_t m0 = h->h_fptr.size();  // n_entries + 1
@@ -1654,6 +1654,8 @@ extern "C" int kmx_bow_add_from_voc(kmx_bow* h, kmx_voc* voc, int32_t* first_id_
   KMX_HIP(hipEventRecord(h->ev, vb.stream));
   KMX_HIP(hipStreamWaitEvent(h->stream, h->ev, 0));
   long long* fnew = h->d_fptr + h->n_entries;
+  // no weight check here (bow_check_csr's "finite and > 0"): k_voc_reduce keeps
+  // only leaves with a positive weight and divides by their positive sum
   hipLaunchKernelGGL(k_bow_scan_len<0>, dim3(1), dim3(TL_BLOCK), 0, h->stream, n, vb.nnz,
                      (const long long*)nullptr, fnew);
   KMX_HIP(hipGetLastError());

@@ -2,7 +2,8 @@
 // kmx_bow_add_entries, the parameter and shape checks of kmx_bow_detect_entries
 // and kmx_bow_decide_results) as a stand-alone program, built by `make
 // bow_check` with the host address and undefined-behaviour sanitizers. It feeds
-// kmx::bow_check_csr the inputs kmx_bow_add_entries must reject, in arrays of
+// kmx::bow_check_csr the inputs kmx_bow_add_entries and kmx_bow_set_database
+// must reject (weights that are not finite and > 0 among them), in arrays of
 // exactly the stated size so that a read past either is a report, and
 // kmx::bow_check_detect_params / bow_check_result_counts malformed parameter
 // sets and counts. CPU only.
@@ -19,15 +20,18 @@ namespace {
 
 int g_fail = 0;
 
+// `weights` empty: every word gets the legal weight 0.5
 void expect_code(int32_t n_words, int64_t n_now, int64_t post_now, const std::vector<int64_t>& vptr,
-                 const std::vector<uint32_t>& words, int code, const char* what) {
-  // exact-size copies, so a read past either array is a sanitizer report
+                 const std::vector<uint32_t>& words, int code, const char* what,
+                 const std::vector<double>& weights = {}) {
+  // exact-size copies, so a read past any array is a sanitizer report
   std::vector<int64_t> vp(vptr);
   std::vector<uint32_t> w(words);
+  std::vector<double> x(weights.empty() ? std::vector<double>(words.size(), 0.5) : weights);
   std::string err;
   const int64_t n = vp.empty() ? 0 : (int64_t)vp.size() - 1;
   const int rc = kmx::bow_check_csr(n_words, n_now, post_now, n, vp.empty() ? nullptr : vp.data(),
-                                    w.empty() ? nullptr : w.data(), &err);
+                                    w.empty() ? nullptr : w.data(), x.empty() ? nullptr : x.data(), &err);
   if (rc != code || (code != KMX_OK && err.find(what) == std::string::npos)) {
     std::fprintf(stderr, "expected %d (%s), got %d (%s)\n", code, what, rc, err.c_str());
     ++g_fail;
@@ -99,6 +103,38 @@ int main() {
       const size_t k = first + rng() % (words.size() - first);
       broken[k] = (uint32_t)n_words + (uint32_t)(rng() % 3);
       expect_code(n_words, rep, rep * 7, vptr, broken, KMX_EINVAL, "word id >= n_words");
+    }
+  }
+  // ---- the weights: finite and > 0 (the query kernels read an accumulator of 0.0 as "untouched")
+  {
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    const char* msg = "weights must be finite and > 0";
+    const std::vector<int64_t> vp{0, 2, 2, 5};
+    const std::vector<uint32_t> wd{1, 9, 0, 4, 8};
+    expect_code(10, 0, 0, vp, wd, KMX_OK, "", {0.25, 0.75, 0.5, 0.25, 0.25});
+    expect_code(10, 0, 0, vp, wd, KMX_OK, "", {0.25, 0.75, std::numeric_limits<double>::denorm_min(), 0.25, 0.25});
+    expect_code(10, 0, 0, vp, wd, KMX_OK, "", {std::numeric_limits<double>::min() / 4, 0.75, 0.5, 0.25, 1e300});
+    expect_code(10, 0, 0, vp, wd, KMX_EINVAL, msg, {0.0, 0.75, 0.5, 0.25, 0.25});
+    expect_code(10, 0, 0, vp, wd, KMX_EINVAL, msg, {0.25, -0.0, 0.5, 0.25, 0.25});
+    expect_code(10, 0, 0, vp, wd, KMX_EINVAL, msg, {0.25, 0.75, -0.5, 0.25, 0.25});
+    expect_code(10, 0, 0, vp, wd, KMX_EINVAL, msg, {0.25, 0.75, nan, 0.25, 0.25});
+    expect_code(10, 0, 0, vp, wd, KMX_EINVAL, msg, {0.25, 0.75, 0.5, inf, 0.25});
+    expect_code(10, 0, 0, vp, wd, KMX_EINVAL, msg, {0.25, 0.75, 0.5, -inf, 0.25});
+    // a bad weight in the last vector of a batch, at its last word
+    expect_code(10, 0, 0, vp, wd, KMX_EINVAL, msg, {0.25, 0.75, 0.5, 0.25, 0.0});
+    expect_code(10, 7, 70, vp, wd, KMX_EINVAL, msg, {0.25, 0.75, 0.5, 0.25, nan});
+    // weights before vptr[0] are not the batch's: never read, whatever they hold
+    expect_code(10, 0, 0, {3, 5}, {7, 7, 7, 2, 3}, KMX_OK, "", {nan, -1.0, 0.0, 0.5, 0.5});
+    expect_code(10, 0, 0, {3, 5}, {7, 7, 7, 2, 3}, KMX_EINVAL, msg, {0.5, 0.5, 0.5, 0.5, 0.0});
+    // null weights with postings stay an error; with none they are fine
+    std::string err;
+    const int64_t vp1[2] = {0, 1}, vp0[2] = {0, 0};
+    const uint32_t w1[1] = {3};
+    if (kmx::bow_check_csr(10, 0, 0, 1, vp1, w1, nullptr, &err) != KMX_EINVAL ||
+        err.find("null weights") == std::string::npos ||
+        kmx::bow_check_csr(10, 0, 0, 1, vp0, nullptr, nullptr, &err) != KMX_OK) {
+      std::fprintf(stderr, "null weights: not handled as stated\n");
+      ++g_fail;
     }
   }
   // ---- the detection parameters (kmx_bow_detect_entries / kmx_bow_decide_results)

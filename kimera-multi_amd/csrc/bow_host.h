@@ -12,14 +12,18 @@
 
 namespace kmx {
 
-// n BowVectors as CSR (vptr[n + 1], words) to be appended to a database over
-// n_words words that holds n_entries_now entries and n_postings_now postings.
-// KMX_OK, or KMX_EINVAL with *err set: vptr must be monotone from a value
-// >= 0, a vector's words strictly increasing and < n_words, and the totals
-// must stay below INT32_MAX (posting lists are indexed with int). The totals
-// are checked before a word is read, so an absurd vptr reads nothing.
+// n BowVectors as CSR (vptr[n + 1], words, weights) to be appended to a
+// database over n_words words that holds n_entries_now entries and
+// n_postings_now postings. KMX_OK, or KMX_EINVAL with *err set: vptr must be
+// monotone from a value >= 0, a vector's words strictly increasing and
+// < n_words, every weight finite and > 0, and the totals must stay below
+// INT32_MAX (posting lists are indexed with int). The totals are checked
+// before a word or a weight is read, so an absurd vptr reads nothing.
+// The weights: the query kernels take an accumulator of exactly 0.0 for "entry
+// not touched yet", which holds because a contribution |q - d| - |q| - |d| of
+// positive finite weights is negative; DBoW2 stores no other weight.
 inline int bow_check_csr(int32_t n_words, int64_t n_entries_now, int64_t n_postings_now, int64_t n,
-                         const int64_t* vptr, const uint32_t* words, std::string* err) {
+                         const int64_t* vptr, const uint32_t* words, const double* weights, std::string* err) {
   auto bad = [&](const char* m) {
     if (err) *err = m;
     return KMX_EINVAL;
@@ -34,10 +38,14 @@ inline int bow_check_csr(int32_t n_words, int64_t n_entries_now, int64_t n_posti
   const int64_t total = vptr[n] - vptr[0];
   if (total >= (int64_t)INT32_MAX - n_postings_now) return bad("database too large (postings must fit int32)");
   if (total > 0 && !words) return bad("null words");
+  if (total > 0 && !weights) return bad("null weights");
   for (int64_t e = 0; e < n; ++e)
     for (int64_t k = vptr[e]; k < vptr[e + 1]; ++k) {
       if (words[k] >= (uint32_t)n_words) return bad("word id >= n_words");
       if (k > vptr[e] && words[k] <= words[k - 1]) return bad("BowVector words must be strictly increasing");
+      // x - x is 0 for a finite x and NaN for an infinity or a NaN; -0.0 > 0.0 is false
+      const double x = weights[k];
+      if (!(x > 0.0) || !(x - x == 0.0)) return bad("BowVector weights must be finite and > 0");
     }
   return KMX_OK;
 }

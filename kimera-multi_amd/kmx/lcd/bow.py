@@ -75,9 +75,10 @@ class BowDatabase:
     def set_entries(self, vptr, words, weights):
         """Database::add of every vector, in order (replaces the database)."""
         vptr, words, weights = _csr(vptr, words, weights)
-        self.n = vptr.shape[0] - 1
-        check(self.L.kmx_bow_set_database(self.h, self.n_words, self.n, i64ptr(vptr), u32ptr(words),
+        n = vptr.shape[0] - 1
+        check(self.L.kmx_bow_set_database(self.h, self.n_words, n, i64ptr(vptr), u32ptr(words),
                                           fptr(weights)), "kmx_bow_set_database")
+        self.n = n  # a refused database leaves the old one in place
 
     # ---- streaming: Database::add, the vectors resident on the device
     def reset(self):

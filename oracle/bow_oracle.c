@@ -123,7 +123,8 @@ int orc_bowdb_query(void* h, const uint32_t* words, const double* weights, int n
       if (!(e < max_id || max_id == -1)) continue;
       const double d = db->wt[p];
       const double value = fabs(q - d) - fabs(q) - fabs(d);
-      if (db->acc[e] == 0.0) db->touched[nt++] = e; /* values are < 0: 0 means untouched */
+      if (db->acc[e] == 0.0) db->touched[nt++] = e; /* values are < 0: 0 means untouched (weights finite
+                                                     * and > 0: OracleBowDb checks them) */
       db->acc[e] += value;
     }
   }

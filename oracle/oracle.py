@@ -405,6 +405,12 @@ class OracleBowDb:
         self.words = np.ascontiguousarray(words, np.uint32)
         self.weights = np.ascontiguousarray(weights, np.float64)
         self.n = self.vptr.shape[0] - 1
+        # orc_bowdb_query reads acc == 0.0 as "entry not touched yet", which
+        # only positive finite weights guarantee (kmx_bow_set_database refuses
+        # the same vectors with KMX_EINVAL)
+        held = self.weights[int(self.vptr[0]):int(self.vptr[-1])]
+        if not (np.isfinite(held) & (held > 0)).all():
+            raise ValueError("BowVector weights must be finite and > 0")
         self.h = self.L.orc_bowdb_create(int(n_words), self.n, _i64(self.vptr), _u32(self.words), _f(self.weights))
 
     def __del__(self):
