@@ -911,6 +911,76 @@ int kmx_chordal_solve(kmx_chordal* h, const kmx_chordal_params* p,
  * download. KMX_ESTATE before the first solve. */
 int kmx_chordal_get_timing(kmx_chordal* h, double* ms /* [4] */);
 
+/* Robust chordal initialisation: GNC-TLS around the two solves, decided on the
+ * device (dpgo's robust local initialisation [U: dpgo is not vendored; the rule
+ * is kmx.dpgo.init.robust_chordal_initialization's, restated from the published
+ * GNC algorithm, Yang et al. 2020]). With
+ *   r^2 = kappa |R_j - R_i R_ij|_F^2 + tau |t_j - t_i - R_i t_ij|^2
+ * (dpgo's computeMeasurementError [U]; kappa and tau unscaled, on the projected
+ * rotations) and c = barc, an edge's factor for a block's mu is
+ *   g = 1 for r^2 <= mu/(mu+1) c^2, g = 0 for r^2 >= (mu+1)/mu c^2,
+ *   g = sqrt(c^2 mu (mu+1) / r^2) - mu in between,
+ * fixed edges keep g = 1, and the edge's weight in a solve is w0 g (w0: the
+ * handle's weight from set_graph / set_weights; an edge of w0 = 0 stays out and
+ * is not counted). The first solve runs at g = 1. From its residuals a block
+ * takes mu_0 (mu_init, or c^2 / (2 max r^2 - c^2) over its counted edges; with
+ * 2 max r^2 <= c^2 it is done with 0 updates). Then, per block: g from the last
+ * solve's residuals and mu; done (converged) when every g is 0 or 1 and none
+ * differs from the g of the last solve; otherwise one more solve with w0 g,
+ * warm-started (an update), and mu <- mu mu_step. A block stops after
+ * max_updates updates with converged = 0. mu, the counts and the done flag are
+ * per block and live on the device; a done block is frozen (no CG, no
+ * projection, no weight is rewritten), so a block's result does not depend on
+ * the other blocks of the batch, bit for bit. */
+typedef struct {
+  double barc;         /* 0: 5.0 (kmx_pgo's GNCBarc default) */
+  double mu_init;      /* 0: per block from its largest residual, c^2 / (2 max r^2 - c^2); > 0: fixed (dpgo: 1e-5) */
+  double mu_step;      /* 0: 1.4 */
+  int32_t max_updates; /* 0: 100 */
+  int32_t reserved;    /* 0. (1: every update's rotation CG starts from the projected rotations and not
+                          from the previous unprojected iterate; kept for the measurement of DESIGN.md 14) */
+} kmx_chordal_robust_params;
+typedef struct {       /* per block */
+  int32_t updates;     /* solves after the first */
+  int32_t converged;   /* 0: max_updates cut it short */
+  int32_t n_kept, n_rejected, n_fractional; /* the returned g over the edges that are not fixed and have w0 > 0 */
+  int32_t reserved;
+  double mu;           /* the mu the returned g was formed with (0: no g was formed) */
+} kmx_chordal_robust_info;
+
+/* dpgo's computeMeasurementError [U] on caller-supplied poses (R [n][9],
+ * t [n][3], used as given, anchors included), and, with mu != NULL, the GNC-TLS
+ * factor of every edge for mu[block]: the loop's own kernel. Edges of w0 = 0
+ * are evaluated like any other; fixed edges report g = 1. The handle's
+ * weights and graph are untouched. KMX_ESTATE without a graph. */
+int kmx_chordal_residuals(kmx_chordal* h, const double* R, const double* t,
+                          const double* mu /* [n_blocks] or NULL */, double barc /* 0: 5.0 */,
+                          const uint8_t* fixed /* [n_edges] or NULL: none */,
+                          double* r2_out /* [n_edges] */, double* g_out /* [n_edges] or NULL */);
+/* The loop above. p as in kmx_chordal_solve (every solve of the loop), rp NULL
+ * or a field 0: the default. Checked on the host before any device call, the
+ * handle untouched on failure: the parameters finite and >= 0, mu_step > 1
+ * when given; and the fixed edges of w0 > 0 must BY THEMSELVES connect every
+ * free pose to an anchor (fixed NULL: no edge is fixed), KMX_EINVAL otherwise.
+ * That precondition is what lets the device choose the other weights, down to
+ * 0, without a connectivity check on the host per update: whatever it chooses,
+ * both systems stay positive definite. g_out [n_edges] (or NULL): the factors
+ * of the last solve; info [n_blocks] (or NULL): a block's last solve;
+ * rinfo [n_blocks] (or NULL). The handle's weights are not changed: a
+ * kmx_chordal_solve after it gives the bits it gave before. */
+int kmx_chordal_solve_robust(kmx_chordal* h, const kmx_chordal_params* p,
+                             const kmx_chordal_robust_params* rp, const uint8_t* fixed,
+                             const double* R_init, const double* t_init, double* R_out, double* t_out,
+                             double* g_out, kmx_chordal_block_info* info /* last update's solve */,
+                             kmx_chordal_robust_info* rinfo);
+/* Figures of the last kmx_chordal_solve_robust (HIP events and device-side
+ * counts): [0] device ms of the whole call, [1] of the first (cold) solve,
+ * [2] of all GNC passes and decisions together, [3] their number, [4] / [5] CG
+ * iterations of the rotation / translation stage summed over the blocks and
+ * solves (a block's largest row count per solve), [6] solves run by the host
+ * loop (the first included), [7] 0. KMX_ESTATE before the first robust solve. */
+int kmx_chordal_get_robust_stats(kmx_chordal* h, double* out /* [8] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 // chordal_check.cpp — chordal.hip's host code (chordal_host.h: the checks of
 // kmx_chordal_set_graph / kmx_chordal_set_weights and the incidence CSR and
-// tile list they build) as a stand-alone program, built by `make chordal_check`
+// tile list they build, and the parameter and fixed-mask checks of
+// kmx_chordal_solve_robust) as a stand-alone program, built by `make chordal_check`
 // with the host address and undefined-behaviour sanitizers. Every array is
 // passed in a vector of exactly the stated size, so a read past one is a
 // report. CPU only.
@@ -243,6 +244,98 @@ int main() {
       ++g_fail;
     }
   }
+  // the robust solve's checks: its parameters, and the fixed mask, whose edges
+  // of weight > 0 must connect every free pose to an anchor by themselves
+  int robust = 0;
+  {
+    auto params = [&](kmx_chordal_robust_params rp, int code, const char* what, const char* name) {
+      kmx::ChordalRobust q;
+      q.max_updates = -7;  // a refusal must leave *out alone
+      std::string err;
+      const int rc = kmx::chordal_robust_params(&rp, &q, &err);
+      if (rc != code || (code != KMX_OK && (err.find(what) == std::string::npos || q.max_updates != -7))) {
+        std::fprintf(stderr, "robust params %s: expected %d (%s), got %d (%s)\n", name, code, what, rc, err.c_str());
+        ++g_fail;
+      }
+      ++robust;
+    };
+    const kmx_chordal_robust_params zero = {0.0, 0.0, 0.0, 0, 0};
+    params(zero, KMX_OK, "", "all defaults");
+    kmx::ChordalRobust q;
+    std::string err;
+    if (kmx::chordal_robust_params(nullptr, &q, &err) != KMX_OK || q.barc != 5.0 || q.mu_init != 0.0 ||
+        q.mu_step != 1.4 || q.max_updates != 100 || q.start_projected) {
+      std::fprintf(stderr, "robust params: wrong defaults\n");
+      ++g_fail;
+    }
+    { auto rp = zero; rp.barc = 3.0; rp.mu_init = 1e-5; rp.mu_step = 1.0000001; rp.max_updates = 7; rp.reserved = 1; params(rp, KMX_OK, "", "all given"); }
+    { auto rp = zero; rp.barc = nan; params(rp, KMX_EINVAL, "barc", "NaN barc"); }
+    { auto rp = zero; rp.barc = -1.0; params(rp, KMX_EINVAL, "barc", "negative barc"); }
+    { auto rp = zero; rp.barc = inf; params(rp, KMX_EINVAL, "barc", "infinite barc"); }
+    { auto rp = zero; rp.mu_init = nan; params(rp, KMX_EINVAL, "mu_init", "NaN mu_init"); }
+    { auto rp = zero; rp.mu_init = -1e-5; params(rp, KMX_EINVAL, "mu_init", "negative mu_init"); }
+    { auto rp = zero; rp.mu_step = 1.0; params(rp, KMX_EINVAL, "mu_step must be > 1", "mu_step = 1"); }
+    { auto rp = zero; rp.mu_step = 0.5; params(rp, KMX_EINVAL, "mu_step must be > 1", "mu_step < 1"); }
+    { auto rp = zero; rp.mu_step = nan; params(rp, KMX_EINVAL, "mu_step", "NaN mu_step"); }
+    { auto rp = zero; rp.mu_step = -2.0; params(rp, KMX_EINVAL, "mu_step", "negative mu_step"); }
+    { auto rp = zero; rp.max_updates = -1; params(rp, KMX_EINVAL, "max_updates", "negative max_updates"); }
+    { auto rp = zero; rp.reserved = 2; params(rp, KMX_EINVAL, "reserved", "reserved = 2"); }
+  }
+  {
+    Graph g = chain(6);  // edges 0..4: the chain; 5, 6: loop closures; 7: a second 2 -> 3
+    g.edge(0, 5);
+    g.edge(1, 4);
+    g.edge(2, 3);
+    kmx::ChordalGraph c;
+    std::string err;
+    if (g.build(&c, &err) != KMX_OK) ++g_fail;
+    auto mask = [&](std::vector<uint8_t> fx, bool null, int code, const char* what, const char* name) {
+      std::string e2;
+      const int rc = kmx::chordal_check_fixed(c, null ? nullptr : fx.data(), &e2);
+      if (rc != code || (code != KMX_OK && e2.find(what) == std::string::npos)) {
+        std::fprintf(stderr, "fixed mask %s: expected %d (%s), got %d (%s)\n", name, code, what, rc, e2.c_str());
+        ++g_fail;
+      }
+      ++robust;
+    };
+    mask({1, 1, 1, 1, 1, 0, 0, 0}, false, KMX_OK, "", "the chain");
+    mask({1, 1, 0, 1, 1, 0, 0, 1}, false, KMX_OK, "", "the chain through the parallel edge");
+    mask({1, 1, 0, 1, 1, 0, 0, 0}, false, KMX_EINVAL, "pose 3 is not connected", "a mask that disconnects a pose");
+    mask({0, 0, 0, 0, 0, 0, 0, 0}, false, KMX_EINVAL, "pose 1 is not connected", "a mask of zeros");
+    mask({}, true, KMX_EINVAL, "pose 1 is not connected", "a null mask");
+    mask({0, 1, 1, 1, 1, 1, 0, 0}, false, KMX_OK, "", "pose 1 reached over the loop closure 0 -> 5");
+    c.w0[5] = 0.0;  // ... which does not count at weight 0
+    mask({0, 1, 1, 1, 1, 1, 0, 0}, false, KMX_EINVAL, "pose 1 is not connected", "a fixed edge of weight 0");
+    std::vector<uint8_t> rec;
+    const std::vector<uint8_t> fx = {1, 0, 1, 0, 1, 0, 1, 0};
+    kmx::chordal_record_fixed(c, fx.data(), &rec);
+    bool ok = rec.size() == c.inc_edge.size();
+    for (size_t k = 0; ok && k < rec.size(); ++k) ok = rec[k] == fx[c.inc_edge[k]];
+    kmx::chordal_record_fixed(c, nullptr, &rec);
+    for (size_t k = 0; ok && k < rec.size(); ++k) ok = rec[k] == 0;
+    if (!ok || rec.size() != c.inc_edge.size()) {
+      std::fprintf(stderr, "chordal_record_fixed: wrong flags\n");
+      ++g_fail;
+    }
+    if (c.w0.size() != 8 || c.w0[0] != 1.0) {
+      std::fprintf(stderr, "chordal_build: w0 not kept\n");
+      ++g_fail;
+    }
+  }
+  {
+    Graph g;  // every pose an anchor: no fixed edge is needed
+    g.n = 3;
+    g.block_ptr = {0, 3};
+    g.anchors = {0, 1, 2};
+    g.edge(0, 1);
+    kmx::ChordalGraph c;
+    std::string err;
+    if (g.build(&c, &err) != KMX_OK || kmx::chordal_check_fixed(c, nullptr, &err) != KMX_OK) {
+      std::fprintf(stderr, "fixed mask: all anchors refused (%s)\n", err.c_str());
+      ++g_fail;
+    }
+    ++robust;
+  }
   // random multi-block graphs with parallel edges, hubs and empty blocks
   std::mt19937 rng(1234);
   int graphs = 0;
@@ -272,6 +365,7 @@ int main() {
     std::fprintf(stderr, "chordal_check: %d failure(s)\n", g_fail);
     return 1;
   }
-  std::printf("chordal_check ok: %d random graphs, CSR and tiles verified, %d malformed graphs refused\n", graphs, refused);
+  std::printf("chordal_check ok: %d random graphs, CSR and tiles verified, %d malformed graphs refused, %d robust-solve checks\n",
+              graphs, refused, robust);
   return 0;
 }

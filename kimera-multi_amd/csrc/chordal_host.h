@@ -36,6 +36,7 @@ struct ChordalGraph {
   std::vector<int32_t> tile_ptr;    // [nb + 1] a block's tiles
   std::vector<double> kappa, tau;   // [m]
   std::vector<int32_t> src, dst;    // [m] (kept for the connectivity check of set_weights)
+  std::vector<double> w0;           // [m] the weights in force (set_graph / set_weights), for the robust solve's check
 };
 
 namespace chordal_detail {
@@ -130,6 +131,8 @@ inline int chordal_build(int32_t n, int32_t nb, const int32_t* block_ptr, int64_
   g.tau.assign(tau, tau + m);
   g.src.assign(src, src + m);
   g.dst.assign(dst, dst + m);
+  g.w0.assign((size_t)m, 1.0);
+  if (weight) g.w0.assign(weight, weight + m);
   // incidence CSR by counting sort: a pose's records come in edge order, and
   // an edge's two records are distinct (src != dst)
   g.inc_ptr.assign((size_t)n + 1, 0);
@@ -182,6 +185,63 @@ inline void chordal_record_weights(const ChordalGraph& g, const double* weight, 
     (*wk)[k] = w * g.kappa[e];
     (*wt)[k] = w * g.tau[e];
   }
+}
+
+// kmx_chordal_robust_params with the defaults filled in.
+struct ChordalRobust {
+  double barc = 5.0, mu_init = 0.0, mu_step = 1.4;
+  int32_t max_updates = 100;
+  bool start_projected = false;  // reserved == 1
+};
+
+// The parameter checks of kmx_chordal_solve_robust (rp NULL: the defaults).
+inline int chordal_robust_params(const kmx_chordal_robust_params* rp, ChordalRobust* out, std::string* err) {
+  auto bad = [&](const std::string& s) {
+    if (err) *err = s;
+    return KMX_EINVAL;
+  };
+  ChordalRobust r;
+  if (rp) {
+    if (!std::isfinite(rp->barc) || rp->barc < 0) return bad("barc must be finite and >= 0 (0: 5.0)");
+    if (!std::isfinite(rp->mu_init) || rp->mu_init < 0) return bad("mu_init must be finite and >= 0 (0: from the residuals)");
+    if (!std::isfinite(rp->mu_step) || rp->mu_step < 0) return bad("mu_step must be finite and >= 0 (0: 1.4)");
+    if (rp->mu_step != 0 && !(rp->mu_step > 1)) return bad("mu_step must be > 1 when it is given");
+    if (rp->max_updates < 0) return bad("max_updates must be >= 0 (0: 100)");
+    if (rp->reserved != 0 && rp->reserved != 1) return bad("reserved must be 0 (1: the projected warm start)");
+    if (rp->barc > 0) r.barc = rp->barc;
+    r.mu_init = rp->mu_init;
+    if (rp->mu_step > 0) r.mu_step = rp->mu_step;
+    if (rp->max_updates > 0) r.max_updates = rp->max_updates;
+    r.start_projected = rp->reserved == 1;
+  }
+  if (out) *out = r;
+  return KMX_OK;
+}
+
+// The robust solve lets the device choose the weights of the edges that are
+// not fixed, down to 0, without a connectivity check per update. That is safe
+// only when the fixed edges of weight > 0 connect every free pose to an anchor
+// by themselves: checked here, once, with chordal_check_weights' union-find
+// (fixed NULL: no edge is fixed, so every pose must be an anchor).
+inline int chordal_check_fixed(const ChordalGraph& g, const uint8_t* fixed, std::string* err) {
+  std::vector<double> w((size_t)g.m, 0.0);
+  if (fixed)
+    for (int64_t e = 0; e < g.m; ++e)
+      if (fixed[e]) w[(size_t)e] = g.w0[(size_t)e];
+  std::string werr;
+  if (chordal_check_weights(g.n, g.m, g.src.data(), g.dst.data(), w.data(), g.is_free.data(), &werr) != KMX_OK) {
+    if (err) *err = "the fixed edges must connect every free pose to an anchor: " + werr;
+    return KMX_EINVAL;
+  }
+  return KMX_OK;
+}
+
+// An edge's flag at both of its incidence records.
+inline void chordal_record_fixed(const ChordalGraph& g, const uint8_t* fixed, std::vector<uint8_t>* out) {
+  const size_t nrec = g.inc_edge.size();
+  out->assign(nrec, 0);
+  if (fixed)
+    for (size_t k = 0; k < nrec; ++k) (*out)[k] = fixed[g.inc_edge[k]] ? 1 : 0;
 }
 
 }  // namespace kmx

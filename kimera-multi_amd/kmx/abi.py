@@ -127,6 +127,18 @@ class ChordalParams(C.Structure):
     _fields_ = [("rtol", C.c_double), ("max_iterations", C.c_int32), ("check_every", C.c_int32)]
 
 
+class ChordalRobustParams(C.Structure):
+    """kmx_chordal_robust_params (0 in a field: the library's default)."""
+    _fields_ = [("barc", C.c_double), ("mu_init", C.c_double), ("mu_step", C.c_double),
+                ("max_updates", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ChordalRobustInfo(C.Structure):
+    """kmx_chordal_robust_info: one per block of a kmx_chordal_solve_robust."""
+    _fields_ = [("updates", C.c_int32), ("converged", C.c_int32), ("n_kept", C.c_int32), ("n_rejected", C.c_int32),
+                ("n_fractional", C.c_int32), ("reserved", C.c_int32), ("mu", C.c_double)]
+
+
 class ChordalBlockInfo(C.Structure):
     """kmx_chordal_block_info: one per block of a kmx_chordal_solve."""
     _fields_ = [("iterations_rot", C.c_int32), ("iterations_trans", C.c_int32), ("converged", C.c_int32),
@@ -294,6 +306,11 @@ def lib() -> C.CDLL:
         "kmx_chordal_solve": ([P, C.POINTER(ChordalParams), pf64, pf64, pf64, pf64, C.POINTER(ChordalBlockInfo)],
                               C.c_int),
         "kmx_chordal_get_timing": ([P, pf64], C.c_int),
+        "kmx_chordal_residuals": ([P, pf64, pf64, pf64, C.c_double, C.POINTER(C.c_uint8), pf64, pf64], C.c_int),
+        "kmx_chordal_solve_robust": ([P, C.POINTER(ChordalParams), C.POINTER(ChordalRobustParams),
+                                      C.POINTER(C.c_uint8), pf64, pf64, pf64, pf64, pf64,
+                                      C.POINTER(ChordalBlockInfo), C.POINTER(ChordalRobustInfo)], C.c_int),
+        "kmx_chordal_get_robust_stats": ([P, pf64], C.c_int),
     })
     for name, (argt, rest) in sig.items():
         if not hasattr(L, name):

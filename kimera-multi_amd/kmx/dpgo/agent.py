@@ -159,7 +159,9 @@ class PGOAgent:
         relaxation over the robot's own measurements (kmx.dpgo.init);
         "chordal_gpu" solves the same relaxation on the device, started from
         the odometry chain (an L2 method either way: outlier loop closures at
-        weight 1 can make it worse than the odometry chain).
+        weight 1 can make it worse than the odometry chain);
+        "robust_chordal_gpu" wraps the device's solve in GNC-TLS over the
+        private loop closures (kmx_chordal_solve_robust), which rejects them.
         neighbor_global_poses: {(robot, pose): (R, t)} of neighbours already in
         the global frame -> the local trajectory is aligned to it by robust
         single-pose averaging over the shared loop closures (kmx.dpgo.init;
@@ -210,6 +212,24 @@ class PGOAgent:
                 Rs, ts = chordal_initialization_gpu(
                     self.n, [(m.p1, m.p2, m.R, m.t, m.kappa, m.tau, m.weight) for m in own], R_init=R0, t_init=t0,
                     device=self._device)
+            elif self.params.localInitializationMethod == "robust_chordal_gpu":
+                # GNC-TLS around the device's chordal solve; the odometry keeps its weight
+                from .init import robust_chordal_initialization_gpu
+                own = self.odometry + self.private_lcs
+                R0, t0 = self._odometry_chain()
+                # fixed: what the caller marked, and the edges of the odometry chain itself (a loop
+                # closure between consecutive poses is filed under odometry, but is no part of it)
+                step = {}
+                for m in sorted(self.odometry, key=lambda m: not m.fixedWeight):
+                    step.setdefault(m.p1, m)
+                chain = {id(m) for m in step.values()}
+                Rs, ts, _, _, _, ri = robust_chordal_initialization_gpu(
+                    self.n, [(m.p1, m.p2, m.R, m.t, m.kappa, m.tau, m.weight) for m in own],
+                    [bool(m.fixedWeight) or id(m) in chain for m in own],
+                    R_init=R0, t_init=t0, barc=self.params.robustCostParams.GNCBarc, device=self._device,
+                    return_info=True)
+                if ri["n_kept"] < self.params.robustInitMinInliers:  # too few inliers to trust: the odometry chain
+                    Rs, ts = R0, t0
             elif self.params.localInitializationMethod == "odometry":
                 Rs, ts = self._odometry_chain()
             else:

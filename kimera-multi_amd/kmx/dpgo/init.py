@@ -219,7 +219,7 @@ def chordal_initialization_gpu(n: int, edges, anchor: int = 0, R_init=None, t_in
 
     Like the host function this is an L2 method: loop closures that are
     outliers pull at full weight, and the result can then be worse than the
-    odometry chain."""
+    odometry chain; robust_chordal_initialization_gpu is the robust form."""
     from .chordal import ChordalSolver
     src, dst, R, t, kap, tau, w = _edge_arrays(edges)
     s = ChordalSolver(device)
@@ -239,7 +239,8 @@ def chordal_initialization_team(g, weights=None, *, device: int = 0, return_info
     odometry chain g.init_R / g.init_t relative to its pose 0. weights: per
     edge of g ([g.m]; None: g.weight). Returns (list of R [n_a,3,3], list of
     t [n_a,3]) per robot, and the per-robot solver info with return_info.
-    An L2 method: see chordal_initialization_gpu."""
+    An L2 method: see chordal_initialization_gpu; under outliers use
+    robust_chordal_initialization_team."""
     from .chordal import ChordalSolver
     n_poses = np.asarray(g.n_poses, np.int64)
     ptr = np.concatenate([[0], np.cumsum(n_poses)])
@@ -264,3 +265,164 @@ def chordal_initialization_team(g, weights=None, *, device: int = 0, return_info
     Rl = [Rs[ptr[a]:ptr[a + 1]] for a in range(g.n_robots)]
     tl = [ts[ptr[a]:ptr[a + 1]] for a in range(g.n_robots)]
     return (Rl, tl, info) if return_info else (Rl, tl)
+
+
+# ---- robust chordal initialisation: GNC-TLS around the chordal solve
+
+def measurement_errors(src, dst, R, t, kappa, tau, Rs, ts):
+    """dpgo's computeMeasurementError [U] for every edge at the poses (Rs, ts):
+    r^2 = kappa |R_j - R_i R_ij|_F^2 + tau |t_j - t_i - R_i t_ij|^2."""
+    dR = Rs[dst] - np.einsum("eab,ebc->eac", Rs[src], R)
+    dt = ts[dst] - ts[src] - np.einsum("eab,eb->ea", Rs[src], t)
+    return kappa * (dR ** 2).sum((1, 2)) + tau * (dt ** 2).sum(1)
+
+
+def gnc_tls_factor(r2, mu: float, c2: float):
+    """The GNC-TLS factor of every residual for one mu (Yang et al. 2020,
+    "Graduated Non-Convexity for Robust Spatial Perception"): 1 for
+    r^2 <= mu/(mu+1) c^2, 0 for r^2 >= (mu+1)/mu c^2, sqrt(c^2 mu (mu+1) / r^2)
+    - mu in between. Returns (g, fractional mask); the operations are in the
+    order chordal.hip states them."""
+    r2 = np.asarray(r2, np.float64)
+    lo, hi = mu / (mu + 1.0) * c2, (mu + 1.0) / mu * c2
+    one, zero = r2 <= lo, (r2 >= hi) & ~(r2 <= lo)
+    frac = ~one & ~zero
+    g = np.where(one, 1.0, 0.0)
+    g[frac] = np.sqrt(c2 * mu * (mu + 1.0) / r2[frac]) - mu
+    return g, frac
+
+
+def robust_chordal_initialization(n: int, edges, fixed, anchor: int = 0, *, barc: float = 5.0, mu_init: float = 0.0,
+                                  mu_step: float = 1.4, max_updates: int = 100, return_info: bool = False):
+    """Robust local chordal initialisation of one robot's trajectory: GNC-TLS
+    around chordal_initialization (dpgo's robust local initialisation [U: dpgo
+    is not vendored; restated from the published GNC algorithm]). This is the
+    host mirror of kmx_chordal_solve_robust (chordal.hip): the
+    same rule around the host's direct solve, the reference of the device's
+    tests.
+
+    edges as chordal_initialization's; fixed [m]: the edges that keep their
+    weight (the odometry; they must connect every pose to the anchor by
+    themselves). Every other edge of weight w0 > 0 enters a solve with w0 g:
+      1. solve at g = 1; r^2 of every edge (measurement_errors).
+      2. mu_0 = mu_init, or (mu_init = 0) c^2 / (2 max r^2 - c^2) over the
+         counted edges (Yang et al. 2020); with 2 max r^2 <= c^2 nothing can be
+         an outlier: done, 0 updates.
+      3. g = gnc_tls_factor(r^2, mu). Done (converged) when every g is 0 or 1
+         and none differs from the g of the last solve.
+      4. Otherwise solve with w0 g (an update), new r^2, mu <- mu mu_step, and
+         back to 3; after max_updates updates it stops as it is.
+    Returns (R [n,3,3], t [n,3], g [m], updates), and with return_info a dict
+    (converged, mu, n_kept, n_rejected, n_fractional) as a fifth value."""
+    src, dst, Rm, tm, kap, tau, w0 = _edge_arrays(edges)
+    m = src.shape[0]
+    fixed = np.asarray(fixed).astype(bool).reshape(m)
+    counted = ~fixed & (w0 > 0)
+    c2 = float(barc) * float(barc)
+    E = list(edges)
+
+    def solve(g):
+        w = w0 * g
+        return chordal_initialization(n, [(e[0], e[1], e[2], e[3], e[4], e[5], w[k])
+                                          for k, e in enumerate(E) if w[k] > 0], anchor)
+
+    g = np.ones(m)
+    frac = np.zeros(m, bool)
+    Rs, ts = solve(g)
+    r2 = measurement_errors(src, dst, Rm, tm, kap, tau, Rs, ts)
+    mx = float(r2[counted].max()) if counted.any() else 0.0
+    updates, converged, mu = 0, False, 0.0
+    if mu_init > 0:
+        mu_next = float(mu_init)
+    elif 2.0 * mx <= c2:
+        converged, mu_next = True, 0.0
+    else:
+        mu_next = c2 / (2.0 * mx - c2)
+    while not converged:
+        mu = mu_next
+        g_new, frac = gnc_tls_factor(r2, mu, c2)
+        g_new[fixed] = 1.0
+        frac = frac & ~fixed
+        changed = bool((g_new[counted] != g[counted]).any())
+        g = g_new
+        if not frac[counted].any() and not changed:
+            converged = True
+            break
+        Rs, ts = solve(g)
+        updates += 1
+        if updates >= max_updates:
+            break
+        r2 = measurement_errors(src, dst, Rm, tm, kap, tau, Rs, ts)
+        mu_next = mu * mu_step
+    if not return_info:
+        return Rs, ts, g, updates
+    info = {"converged": converged, "mu": mu, "n_kept": int((counted & ~frac & (g == 1.0)).sum()),
+            "n_rejected": int((counted & ~frac & (g == 0.0)).sum()), "n_fractional": int((counted & frac).sum())}
+    return Rs, ts, g, updates, info
+
+
+def robust_chordal_initialization_gpu(n: int, edges, fixed, anchor: int = 0, R_init=None, t_init=None, *,
+                                      barc: float = 5.0, mu_init: float = 0.0, mu_step: float = 1.4,
+                                      max_updates: int = 100, device: int = 0, return_info: bool = False,
+                                      **solver_kw):
+    """robust_chordal_initialization on the device
+    (ChordalSolver.solve_robust, kmx_chordal_solve_robust): the same
+    arguments and the same rule, the solves by warm-started preconditioned
+    conjugate gradients, the residuals, weights, mu and the stop test on the
+    device. Returns (R, t, g, updates), and with return_info the solver's
+    info and rinfo of the one block as well. There is no CPU fallback."""
+    from .chordal import ChordalSolver
+    src, dst, R, t, kap, tau, w = _edge_arrays(edges)
+    s = ChordalSolver(device)
+    try:
+        s.set_graph(n, [0, n], src, dst, R, t, kap, tau, w, anchors=[anchor])
+        Rs, ts, g, info, rinfo = s.solve_robust(fixed, R_init, t_init, barc=barc, mu_init=mu_init, mu_step=mu_step,
+                                                max_updates=max_updates, **solver_kw)
+    finally:
+        s.close()
+    if return_info:
+        return Rs, ts, g, rinfo[0]["updates"], info[0], rinfo[0]
+    return Rs, ts, g, rinfo[0]["updates"]
+
+
+def robust_chordal_initialization_team(g, weights=None, *, min_inliers: int = 0, barc: float = 5.0,
+                                       mu_init: float = 0.0, mu_step: float = 1.4, max_updates: int = 100,
+                                       device: int = 0, return_info: bool = False, **solver_kw):
+    """Robust chordal initialisation of every robot of the team graph g in one
+    batch on the device: blocks, anchors and the odometry start as in
+    chordal_initialization_team, fixed = g.fixed (the odometry), every robot
+    with a mu, an update count and a stop test of its own. A robot that keeps
+    fewer than min_inliers loop closures gets its odometry chain (dpgo's
+    robustInitMinInliers [U]). Returns (list of R, list of t, list of g over
+    the robot's private edges in g's order), and the per-robot info and rinfo
+    with return_info."""
+    from .chordal import ChordalSolver
+    n_poses = np.asarray(g.n_poses, np.int64)
+    ptr = np.concatenate([[0], np.cumsum(n_poses)])
+    own = np.nonzero(g.r1 == g.r2)[0]
+    w = np.asarray(g.weight if weights is None else weights, np.float64)
+    if w.shape != (g.m,):
+        raise ValueError(f"weights: expected shape ({g.m},), got {w.shape}")
+    off = ptr[g.r1[own]]
+    R0, t0 = [], []
+    for a in range(g.n_robots):
+        Ra, ta = np.asarray(g.init_R[a], np.float64), np.asarray(g.init_t[a], np.float64)
+        R0.append(np.einsum("ij,njk->nik", Ra[0].T, Ra))
+        t0.append((ta - ta[0]) @ Ra[0])
+    n = int(ptr[-1])
+    s = ChordalSolver(device)
+    try:
+        s.set_graph(n, ptr, off + g.p1[own], off + g.p2[own], g.R[own], g.t[own], g.kappa[own], g.tau[own], w[own],
+                    anchors=ptr[:-1][n_poses > 0])
+        Rs, ts, gf, info, rinfo = s.solve_robust(
+            np.asarray(g.fixed)[own] != 0, np.concatenate(R0).reshape(n, 3, 3), np.concatenate(t0).reshape(n, 3),
+            barc=barc, mu_init=mu_init, mu_step=mu_step, max_updates=max_updates, **solver_kw)
+    finally:
+        s.close()
+    Rl, tl, gl = [], [], []
+    for a in range(g.n_robots):
+        keep = rinfo[a]["n_kept"] >= min_inliers
+        Rl.append(Rs[ptr[a]:ptr[a + 1]] if keep else R0[a])
+        tl.append(ts[ptr[a]:ptr[a + 1]] if keep else t0[a])
+        gl.append(gf[g.r1[own] == a])
+    return (Rl, tl, gl, info, rinfo) if return_info else (Rl, tl, gl)

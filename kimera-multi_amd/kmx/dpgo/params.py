@@ -84,7 +84,10 @@ class PGOAgentParameters:
     acceleration: bool = False             # Nesterov-accelerated RBCD (dpgo acceleration; concurrent schedule)
     restartInterval: int = 30              # acceleration restart period in rounds (dpgo restartInterval [U])
     tileIncidences: int = 0                # kmx: incidences per workgroup tile (0: from the handle's problem)
-    localInitializationMethod: str = "odometry"  # dpgo local initialisation: "odometry", "chordal" (host) or "chordal_gpu" [U default]
+    # dpgo local initialisation [U default]: "odometry", "chordal" (host), "chordal_gpu", or
+    # "robust_chordal_gpu" (GNC-TLS around the device's chordal solve)
+    localInitializationMethod: str = "odometry"
+    robustInitMinInliers: int = 0          # robust_chordal_gpu: below this many kept loop closures, the odometry chain [U]
 
     def to_c(self) -> PgoParams:
         lo, rc = self.localOptimizationParams, self.robustCostParams

@@ -259,7 +259,9 @@ def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, ran
     default) or "chordal_gpu" (kmx.dpgo.init.chordal_initialization_team: the
     chordal relaxation over its private measurements, one batch on the device;
     an L2 method, so outlier loop closures at weight 1 can make it worse than
-    the odometry chain). Returns stage timings and metrics (identical on every
+    the odometry chain) or "robust_chordal_gpu"
+    (robust_chordal_initialization_team: GNC-TLS around that solve, decided on
+    the device, which rejects outlier loop closures). Returns stage timings and metrics (identical on every
     rank)."""
     import time
 
@@ -303,6 +305,11 @@ def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, ran
     elif local_init == "chordal_gpu":
         from .dpgo.init import chordal_initialization_team
         Rl, tl = chordal_initialization_team(g, device=device)
+        own0 = {a: (Rl[a], tl[a]) for a in range(g.n_robots)}
+    elif local_init == "robust_chordal_gpu":
+        from .dpgo.init import robust_chordal_initialization_team
+        Rl, tl, _ = robust_chordal_initialization_team(g, device=device, barc=params.robustCostParams.GNCBarc,
+                                                       min_inliers=params.robustInitMinInliers)
         own0 = {a: (Rl[a], tl[a]) for a in range(g.n_robots)}
     else:
         raise ValueError(f"unknown local_init {local_init!r}")

@@ -133,6 +133,132 @@ def optimiser_gain(g, robust: bool, max_rounds: int):
     return out
 
 
+def robust_device(s, fixed, R0, t0, **kw):
+    t = time.perf_counter()
+    R, tt, g, info, rinfo = s.solve_robust(fixed, R0, t0, **kw)
+    wall = time.perf_counter() - t
+    st = s.robust_stats()
+    return dict(st, wall_ms=1e3 * wall, updates=max(r["updates"] for r in rinfo),
+                updates_per_block=[r["updates"] for r in rinfo], all_converged=all(r["converged"] for r in rinfo),
+                kept=sum(r["n_kept"] for r in rinfo), rejected=sum(r["n_rejected"] for r in rinfo)), g
+
+
+def robust_host_driven(s, args, fixed, R0, t0, *, barc=5.0, mu_step=1.4, max_updates=100):
+    """The same loop through the entry points the library had before
+    kmx_chordal_solve_robust: solve, the residuals and weights in numpy,
+    set_weights (which runs the host's connectivity check and uploads), solve
+    again from the last poses. Per block mu and stop test as on the device; a
+    block that is done keeps its g, but its CGs start again in every solve
+    (the API cannot freeze it)."""
+    from kmx.dpgo.init import gnc_tls_factor, measurement_errors
+    src, dst, w0 = np.asarray(args["src"]), np.asarray(args["dst"]), np.asarray(args["weight"], np.float64)
+    ptr = np.asarray(args["block_ptr"])
+    nb = ptr.shape[0] - 1
+    blk = np.searchsorted(ptr, src, side="right") - 1
+    counted = ~fixed & (w0 > 0)
+    c2 = barc * barc
+    t_start = time.perf_counter()
+    s.set_weights(w0)
+    R, t, _ = s.solve(R0, t0)
+    r2 = measurement_errors(src, dst, args["R"], args["t"], args["kappa"], args["tau"], R, t)
+    mx = np.zeros(nb)
+    np.maximum.at(mx, blk[counted], r2[counted])
+    done = 2.0 * mx <= c2
+    mu = np.where(done, 1.0, c2 / np.where(done, 1.0, 2.0 * mx - c2))
+    g = np.ones(src.shape[0])
+    updates = np.zeros(nb, np.int64)
+    solves = 1
+    while not done.all() and solves <= max_updates:
+        g_new = g.copy()
+        stop = np.zeros(nb, bool)
+        for b in np.nonzero(~done)[0]:
+            sel = (blk == b) & ~fixed
+            gb, frac = gnc_tls_factor(r2[sel], mu[b], c2)
+            stop[b] = not frac[counted[sel]].any() and np.array_equal(gb[counted[sel]], g[sel][counted[sel]])
+            g_new[sel] = gb
+        g = g_new
+        done |= stop
+        if done.all():
+            break
+        s.set_weights(w0 * g)
+        R, t, _ = s.solve(R, t)
+        solves += 1
+        updates[~done] += 1
+        r2 = measurement_errors(src, dst, args["R"], args["t"], args["kappa"], args["tau"], R, t)
+        mu[~done] *= mu_step
+    wall = time.perf_counter() - t_start
+    s.set_weights(w0)
+    return {"wall_ms": 1e3 * wall, "updates": int(updates.max()), "solves": solves}, g
+
+
+def robust_part(g, label, reps=5, host_reps=5):
+    """(R1) / (R2): solve_robust with both warm starts and the host-driven loop, alternating, one warm-up each."""
+    from kmx.dpgo.chordal import ChordalSolver
+    args, R0, t0 = team_arrays(g)
+    own = np.nonzero(g.r1 == g.r2)[0]
+    fixed = np.asarray(g.fixed)[own] != 0
+    outl = np.asarray(g.outlier)[own]
+    s = ChordalSolver()
+    runs = {"unprojected": [], "projected": [], "host_driven": []}
+    try:
+        s.set_graph(**args)
+        for k in range(max(reps, host_reps) + 1):
+            for name in runs:
+                if name == "host_driven":
+                    if k > host_reps:
+                        continue
+                    r, gg = robust_host_driven(s, args, fixed, R0, t0)
+                else:
+                    if k > reps:
+                        continue
+                    r, gg = robust_device(s, fixed, R0, t0, start_projected=name == "projected")
+                r["outliers_kept"] = int((gg[outl] > 0).sum())
+                r["inliers_dropped"] = int((gg[~outl & ~fixed] == 0).sum())
+                if k:  # the first is the warm-up
+                    runs[name].append(r)
+    finally:
+        s.close()
+    out = {"poses": args["n_poses"], "edges": int(own.shape[0]), "outliers": int(outl.sum()),
+           "loop_closures": int((~fixed).sum())}
+    for name, rr in runs.items():
+        med = {k: statistics.median(r[k] for r in rr) for k in rr[0] if not isinstance(rr[0][k], (list, bool))}
+        med.update({k: rr[0][k] for k in rr[0] if isinstance(rr[0][k], (list, bool))})
+        if "gnc_passes" in med:
+            med["gnc_pass_and_decision_us"] = 1e3 * med["gnc_ms"] / max(med["gnc_passes"], 1)
+        out[name] = med
+    out["host_driven_over_device"] = out["host_driven"]["wall_ms"] / out["unprojected"]["wall_ms"]
+    print(label, json.dumps(out), flush=True)
+    return out
+
+
+def robust_optimiser_row(g, max_rounds):
+    """§14's table, the third GNC-TLS row: start robust_chordal_initialization_team."""
+    from kmx import pipeline as PL
+    from kmx.dpgo.driver import RBCDDriver
+    from kmx.dpgo.init import robust_chordal_initialization_team
+    from kmx.dpgo.params import PGOAgentParameters
+    from kmx.synth import lift, lifting_matrix
+    P = PGOAgentParameters(r=5)
+    P.maxNumIters = max_rounds
+    Y = lifting_matrix(P.r, seed=1)
+    t = time.perf_counter()
+    Rl, tl, gl, _, rinfo = robust_chordal_initialization_team(g, return_info=True)
+    t_local = time.perf_counter() - t
+    own = {a: (Rl[a], tl[a]) for a in range(g.n_robots)}
+    traj0, _ = PL.global_init(g, own)
+    drv = RBCDDriver(P, g)
+    drv.initialize({a: lift(traj0[a][0], traj0[a][1], Y) for a in drv.robots})
+    rounds = drv.run(max_rounds=max_rounds, check_every=10)
+    final = {a: PL.rounded(drv.iterate_of(a), Y) for a in drv.robots}
+    out = {"local_init_s": t_local, "updates_per_robot": [r["updates"] for r in rinfo],
+           "cost_round_0": team_cost(g, traj0), "ate_round_0_m": PL.ate_rmse(g, traj0), "rounds_to_stop": rounds,
+           "hit_round_limit": rounds >= max_rounds, "cost_final_weight_1": team_cost(g, final),
+           "ate_final_m": PL.ate_rmse(g, final)}
+    drv.solver.close()
+    print("(d) robust robust_chordal_gpu", json.dumps(out), flush=True)
+    return out
+
+
 def kernel_stats(path):
     """Per-kernel totals of the k_ch_* kernels from a rocprofv3 kernel-stats CSV."""
     out = {}
@@ -156,15 +282,35 @@ def main():
     ap.add_argument("--kernel-stats", default=None, help="rocprofv3 kernel-stats CSV of a --profile-run to merge")
     ap.add_argument("--max-rounds", type=int, default=1500)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "chordal.json"))
+    ap.add_argument("--robust", default=None, metavar="PARTS",
+                    help="measure kmx_chordal_solve_robust instead (letters of 1: (R1), 2: (R2), d: the optimiser row) "
+                         "and write profiles/chordal_robust.json")
     a = ap.parse_args()
     from kmx.dpgo.init import chordal_initialization
     from kmx.synth import make_pose_graph
+    if a.robust is not None and a.out == str(ROOT / "profiles" / "chordal.json"):
+        a.out = str(ROOT / "profiles" / "chordal_robust.json")
     outp = Path(a.out)
     res = json.loads(outp.read_text()) if outp.exists() else {}  # parts run apart are merged
 
     def save():
         outp.parent.mkdir(parents=True, exist_ok=True)
         outp.write_text(json.dumps(res, indent=1) + "\n")
+
+    if a.robust is not None:
+        if "1" in a.robust:
+            res["R1_20k_one_robot_20pct_outliers"] = robust_part(
+                make_pose_graph(1, 20000, 100000, outlier_frac=0.2, f_inter=0, seed=1), "(R1)")
+            save()
+        if "2" in a.robust:
+            res["R2_configs4_team_with_outliers"] = robust_part(
+                make_pose_graph(8, 160_000, 800_000, f_inter=0, seed=0), "(R2)")
+            save()
+        if "d" in a.robust:
+            res["d_optimiser_gnc_tls_20pct_outliers_robust_chordal"] = robust_optimiser_row(
+                make_pose_graph(6, 6000, 30000), a.max_rounds)
+            save()
+        return
 
     if a.kernel_stats:
         ks = kernel_stats(a.kernel_stats)

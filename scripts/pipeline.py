@@ -28,9 +28,10 @@ def main():
     ap.add_argument("--sigma-r", type=float, default=0.002, help="odometry rotation noise per keyframe (rad)")
     ap.add_argument("--sigma-t", type=float, default=0.02, help="odometry translation noise per keyframe (m)")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--local-init", choices=("odometry", "chordal_gpu"), default="odometry",
+    ap.add_argument("--local-init", choices=("odometry", "chordal_gpu", "robust_chordal_gpu"), default="odometry",
                     help="each robot's initialisation in its own frame: its odometry chain, or the chordal "
-                         "relaxation on the device (L2: the intra-robot outliers pull at full weight)")
+                         "relaxation on the device (L2: the intra-robot outliers pull at full weight), or "
+                         "that relaxation inside GNC-TLS on the device (rejects them)")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
