@@ -43,6 +43,7 @@
 #include <algorithm>
 #include <chrono>
 #include <thread>
+#include <type_traits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -137,7 +138,6 @@ struct Params {
   int gnc_on, inner_iters, max_updates, n_ext;
   int rgd;          // KMX_METHOD_RGD: one preconditioned gradient step per block update
   double rgd_step;
-  int early_stop;   // RM_CONSUMER k_hess: the stop decision before the gather (else after)
 };
 
 // One tile's description, read by a single 32-B scalar load at the start of
@@ -283,13 +283,18 @@ __device__ __forceinline__ void store4(double* p, const double v[4]) {
 // Symmetric 4x4 blocks (Q's diagonal blocks, the preconditioner) are stored
 // as their upper triangle, row by row: 10 doubles, five 16-B loads.
 constexpr int SYM4 = 10;
-__device__ __forceinline__ void load_sym4(const double* p, double M[16]) {
-  const double2* p2 = reinterpret_cast<const double2*>(p);
+// (the five parts as loaded, for a caller that keeps them raw until use)
+__device__ __forceinline__ void expand_sym4(const double2 p2[5], double M[16]) {
   const double2 a = p2[0], b = p2[1], c = p2[2], e = p2[3], f = p2[4];
   M[0] = a.x; M[1] = M[4] = a.y; M[2] = M[8] = b.x; M[3] = M[12] = b.y;
   M[5] = c.x; M[6] = M[9] = c.y; M[7] = M[13] = e.x;
   M[10] = e.y; M[11] = M[14] = f.x;
   M[15] = f.y;
+}
+__device__ __forceinline__ void load_sym4(const double* p, double M[16]) {
+  const double2* p2 = reinterpret_cast<const double2*>(p);
+  const double2 v[5] = {p2[0], p2[1], p2[2], p2[3], p2[4]};
+  expand_sym4(v, M);
 }
 // S = sym(Y^T G_Y) stored as its 6 upper entries
 __device__ __forceinline__ void load_sym3(const double* p, double S[9]) {
@@ -327,11 +332,27 @@ struct Rec {
   static constexpr int Q = RW / 2;        // 16-B parts in registers
   static constexpr int GS = RW == 10 ? 8 : 16;  // doubles per record in HBM
   static constexpr int WK = RW == 10 ? 6 : 12;  // index of w kappa (w tau follows)
-  __device__ static __forceinline__ void load(const Dev& d, size_t k, double2 q[Q]) {
+  static constexpr int QS = RW == 10 ? 4 : Q;   // 16-B parts of the record as stored
+  // The load in two halves, for a gather that fetches the word with the other
+  // endpoint a chunk ahead of the record (hinc_gather_src's PF): the record as
+  // stored, the compact record's 4-B word (rec_o), and the register form of
+  // the two. The full record holds the other endpoint itself: no word.
+  __device__ static __forceinline__ void load_stored(const Dev& d, size_t k, double2 a[QS]) {
+    const double2* p2 = reinterpret_cast<const double2*>(d.rec + (size_t)GS * k);
+#pragma unroll
+    for (int i = 0; i < QS; ++i) a[i] = p2[i];
+  }
+  __device__ static __forceinline__ unsigned load_word(const Dev& d, size_t k) {
+    static_assert(RW == 10, "compact records only");
+    return (unsigned)d.rec_o[k];
+  }
+  __device__ static __forceinline__ int other_of(unsigned word) {
+    static_assert(RW == 10, "compact records only");
+    return (int)(word << 3) >> 3;
+  }
+  __device__ static __forceinline__ void expand(const double2 a[QS], unsigned raw, double2 q[Q]) {
     if constexpr (RW == 10) {
-      const double2* p2 = reinterpret_cast<const double2*>(d.rec + (size_t)GS * k);
-      const double2 a0 = p2[0], a1 = p2[1], a2 = p2[2], a3 = p2[3];  // (qa, qb) (qc, t0) (t1, t2) (wk, +-wt)
-      const unsigned raw = (unsigned)d.rec_o[k];
+      const double2 a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];  // (qa, qb) (qc, t0) (t1, t2) (wk, +-wt)
       const int other = (int)(raw << 3) >> 3;
       const unsigned big = raw >> 29;
       const double qa = a0.x, qb = a0.y, qc = a1.x;
@@ -346,10 +367,16 @@ struct Rec {
       const long long bits = (long long)(unsigned)other | (std::signbit(wt) ? (1ll << 63) : 0ll);
       q[4] = make_double2(std::fabs(wt), __longlong_as_double(bits));
     } else {
-      const double2* q2 = reinterpret_cast<const double2*>(d.rec + (size_t)GS * k);
 #pragma unroll
-      for (int i = 0; i < Q; ++i) q[i] = q2[i];
+      for (int i = 0; i < Q; ++i) q[i] = a[i];
     }
+  }
+  __device__ static __forceinline__ void load(const Dev& d, size_t k, double2 q[Q]) {
+    double2 a[QS];
+    load_stored(d, k, a);
+    unsigned word = 0;
+    if constexpr (RW == 10) word = load_word(d, k);
+    expand(a, word, q);
   }
   // the stored w tau of an incidence (compact: its sign is the tail flag)
   __device__ static __forceinline__ double wt_word(double wt, bool tail) {
@@ -618,6 +645,9 @@ static_assert(SCR_BYTES <= SmemHG<3>::x_off, "scratch");
 struct NoPre {
   __device__ bool operator()() const { return true; }
 };
+struct NoEpi {
+  __device__ void operator()() const {}
+};
 // `pre` runs once the first chunk's records are in flight, before any row is
 // gathered (workgroup-uniform; false: leave without gathering).
 // REC_FIRST: the first chunk's records are issued before the tile's CSR
@@ -626,9 +656,26 @@ struct NoPre {
 // would spill)
 // DIAG = false: the caller applies the diagonal block itself (k_step, whose
 // epilogue loads the own row and D_i with the rest of its rows in one batch).
-template <int R, int RW, bool REC_FIRST, typename Src, typename Pre, bool DIAG = true, int W = WAVES>
+// PF: the next chunk's neighbour rows are issued with its records, once this
+// chunk's contributions are in LDS, so both fly across the hand-off and the
+// pose sums. A row's address comes from the word with the other endpoint,
+// which is therefore fetched one chunk further ahead (one register; the same
+// clamp as the records, so it stays inside the tile's range or the pad
+// record). k_hess takes it for the compact records (HessPF below); the full
+// record carries the other endpoint inside itself and keeps the rows' loads
+// at the top of the chunk (with them prefetched k_hess<5, 16, .> spills).
+// The gradient gather (hinc_grad) has the same loop; there the prefetch fits
+// without scratch but did not shorten k_grad.
+// `epi` runs exactly once in a gather that `pre` let through: on the tile's
+// last chunk in place of a next chunk's loads (the last chunk is peeled out
+// of the loop, so what `epi` loads is not live around the loop), or at once
+// on a tile without incidences. k_hess issues its epilogue's loads there;
+// none of their addresses depends on the gather.
+template <int R, int RW, bool REC_FIRST, typename Src, typename Pre, bool DIAG = true, int W = WAVES,
+          bool PF = false, typename Epi = NoEpi>
 __device__ __forceinline__ bool hinc_gather_src(const Dev& d, const Lane& L, Src& src, double acc[4], char* smem,
-                                                Pre&& pre) {
+                                                Pre&& pre, Epi&& epi = Epi{}) {
+  static_assert(!PF || RW == 10, "the row prefetch reads rec_o ahead: compact records only");
   using SM = SmemH<R, W>;
   using RC = Rec<RW>;
   constexpr int CH = SM::CH;
@@ -640,22 +687,38 @@ __device__ __forceinline__ bool hinc_gather_src(const Dev& d, const Lane& L, Src
   const int lt = min(tid, CH - 1);
   acc[0] = acc[1] = acc[2] = acc[3] = 0.0;
   // clamped, unconditional record loads (the pad record keeps an empty tile
-  // at the end of the array inside it)
-  auto ld = [&](int c0, double2* q) { RC::load(d, (size_t)(K0 + max(min(c0 + lt, n - 1), 0)), q); };
-  double2 q[RC::Q];
-  if constexpr (REC_FIRST) ld(0, q);
+  // at the end of the array inside it); the record stays as stored until the
+  // chunk is computed
+  auto at = [&](int c0) { return (size_t)(K0 + max(min(c0 + lt, n - 1), 0)); };
+  double2 qs[RC::QS];
+  unsigned wo = 0, wo_next = 0;  // the word with the other endpoint: this chunk's, the next one's
+  auto ld = [&](int c0) {
+    RC::load_stored(d, at(c0), qs);
+    if constexpr (RW == 10 && !PF) wo = RC::load_word(d, at(c0));
+  };
+  if constexpr (REC_FIRST) ld(0);
   if (tid <= np) sptr[tid] = d.inc_ptr[p0 + tid] - K0;
-  if constexpr (!REC_FIRST) ld(0, q);
+  if constexpr (!REC_FIRST) ld(0);
+  if constexpr (PF) {
+    wo = RC::load_word(d, at(0));
+    wo_next = RC::load_word(d, at(CH));
+  }
   __syncthreads();  // sptr
   if (!pre()) return false;
-  for (int c0 = 0; c0 < n; c0 += CH) {
+  double2 vr[2 * R];
+  if constexpr (PF) {
+    if (n > 0) src.nbr(RC::other_of(wo), vr);
+  }
+  auto chunk = [&](const int c0, auto last_c) __attribute__((always_inline)) {
+    constexpr bool LAST = decltype(last_c)::value;
+    double2 q[RC::Q];
+    RC::expand(qs, wo, q);
     Edge E;
     RC::edge(q, E);
     const int2 in = RC::inc(q);
     const int o = in.x;
     const bool tail = (in.y >> 31) & 1;
-    double2 vr[2 * R];
-    src.nbr(o, vr);
+    if constexpr (!PF) src.nbr(o, vr);
     if (tid < CH && c0 + tid < n) {
       const double wk = (o >= 0) ? E.wk : 0.0, wt = (o >= 0) ? E.wt : 0.0;
 #pragma unroll
@@ -675,10 +738,20 @@ __device__ __forceinline__ bool hinc_gather_src(const Dev& d, const Lane& L, Src
         store4(Cs + (tid * R + a) * 4, h);
       }
     }
-    // the next chunk's records, issued once this chunk's rows are consumed, stay
-    // in flight across the LDS hand-off and the pose sums
+    // the next chunk's records (PF: and its rows), issued once this chunk's
+    // rows are consumed, stay in flight across the LDS hand-off and the pose
+    // sums; the last chunk has no next one and issues the caller's loads
     asm volatile("" ::: "memory");
-    ld(c0 + CH, q);
+    if constexpr (LAST) {
+      epi();
+    } else {
+      ld(c0 + CH);
+      if constexpr (PF) {
+        wo = wo_next;
+        src.nbr(RC::other_of(wo), vr);
+        wo_next = RC::load_word(d, at(c0 + 2 * CH));
+      }
+    }
     lds_barrier();
     if (L.valid) {
       const int j0 = max(sptr[pl], c0) - c0, j1 = min(sptr[pl + 1], c0 + CH) - c0;
@@ -690,6 +763,17 @@ __device__ __forceinline__ bool hinc_gather_src(const Dev& d, const Lane& L, Src
       }
     }
     lds_barrier();
+  };
+  // a gather with neither prefetched rows nor a hook keeps the plain loop (its
+  // last chunk then issues a clamped record load nobody reads; peeled, k_eval
+  // takes more scratch)
+  if constexpr (PF || !std::is_same_v<std::decay_t<Epi>, NoEpi>) {
+    int c0 = 0;
+    for (; c0 + CH < n; c0 += CH) chunk(c0, std::false_type{});
+    if (n > 0) chunk(c0, std::true_type{});
+    else epi();
+  } else {
+    for (int c0 = 0; c0 < n; c0 += CH) chunk(c0, std::false_type{});
   }
   if (DIAG && L.valid) {
     double vs[4];
@@ -733,11 +817,12 @@ struct PlainRows {
 #endif
   }
 };
-template <int R, int RW, bool REC_FIRST = false, bool DIAG = true, typename Pre = NoPre>
+template <int R, int RW, bool REC_FIRST = false, bool DIAG = true, bool PF = false, typename Pre = NoPre,
+          typename Epi = NoEpi>
 __device__ __forceinline__ bool hinc_gather(const Dev& d, const Lane& L, const double* V, double acc[4],
-                                            char* smem, Pre&& pre = Pre{}) {
+                                            char* smem, Pre&& pre = Pre{}, Epi&& epi = Epi{}) {
   PlainRows<R> src{V};
-  return hinc_gather_src<R, RW, REC_FIRST, PlainRows<R>, Pre&, DIAG, WAVES>(d, L, src, acc, smem, pre);
+  return hinc_gather_src<R, RW, REC_FIRST, PlainRows<R>, Pre&, DIAG, WAVES, PF, Epi&>(d, L, src, acc, smem, pre, epi);
 }
 
 // Gradient and cost, incidence-parallel. A lane evaluates its whole incidence
@@ -1497,14 +1582,55 @@ __device__ __forceinline__ void trial_rows(const Dev& d, const Lane& L, size_t o
 // <delta, P_Y(Hdelta^)> for a tangent delta (Y^T delta skew, Y sym(.) S
 // symmetric). k_update, which loads Y anyway, projects; this kernel then
 // reads no X row (16 MB per launch at configs[3]: VERDICT r4 item 2).
+// Which k_hess instantiations prefetch the next chunk's rows (hinc_gather_src's
+// PF); every one takes the epilogue batch on the last chunk. Compact records
+// only (see hinc_gather_src), and not the launched form at r < 5: its 86-92
+// VGPRs give five workgroups per CU there, with the rows in flight four.
 template <int R, int RW, int RM>
-__device__ __forceinline__ void body_hess(const Dev& d, int first_launch, int slot, HostStatus* hs,
+struct HessPF {
+  static constexpr bool rows = RW == 10 && (R >= 5 || RM == RM_CONSUMER);
+};
+// GRAD, EARLY (consumer form; the launched form has one body, <false, false>):
+// whether this is the host's launch 0 of a tCG loop, and whether the stop
+// decision runs before the gather or after it. The host knows both when it
+// enqueues, and a body that carries both robot sums and both gathers does not
+// fit 128 VGPRs next to the prefetched rows.
+template <int R, int RW, int RM, bool GRAD, bool EARLY>
+__device__ __forceinline__ void body_hess(const Dev& d, int gated, int slot, HostStatus* hs,
                                           unsigned long long seq, char* smem) {
+  static_assert(RM == RM_CONSUMER || (!GRAD && !EARLY), "the launched form has one body");
   const Lane L = lane_map<R>(d);
   int tcg_iter;
   double beta;
   double y[4] = {0, 0, 0, 0}, zs[4] = {0, 0, 0, 0}, H[4];
   const size_t o = (size_t)L.pose * 4 * R + 4 * L.a;
+  // every row the epilogue needs in one batch: the own z row, D_i - S_i (the
+  // diagonal block with the tangent correction -z S folded in; its five parts
+  // stay as loaded until use), delta_old and H delta_old. No address depends
+  // on the gather or on the decision, only on tcg_iter, so the gather issues
+  // the batch on the tile's last chunk (hinc_gather_src's `epi`) and it flies
+  // under the last LDS hand-off and pose sums.
+  const int dhn = d.dhn;
+  double dold[4] = {0, 0, 0, 0}, hold[4] = {0, 0, 0, 0};
+  double2 dg[5];
+  bool first;
+  auto epi = [&]() {
+    if (L.valid) {
+#if KMX_HESS_PROBE & 2  // traffic attribution build: no own-row / diagonal-block loads
+      for (int k = 0; k < 4; ++k) zs[k] = 1e-3 * k;
+      for (int c = 0; c < 5; ++c) dg[c] = make_double2(c == 0 || c == 2 ? 1.0 : 0.0, c >= 3 ? 1.0 : 0.0);  // I
+#else
+      load4(d.z + o, zs);
+      const double2* p2 = reinterpret_cast<const double2*>(d.hDS + SYM4 * (size_t)L.pose);
+#pragma unroll
+      for (int c = 0; c < 5; ++c) dg[c] = p2[c];
+#endif
+      if (!first) {
+        load4(d.dh + (size_t)((tcg_iter - 1) % dhn) * d.vec + o, dold);
+        load4(d.hd + o, hold);
+      }
+    }
+  };
   if constexpr (RM == RM_CONSUMER) {
     // the previous step's k_update partials give this robot's control step
     // after the update (stop test, beta); the partial loads are in flight with
@@ -1520,19 +1646,20 @@ __device__ __forceinline__ void body_hess(const Dev& d, int first_launch, int sl
     // (its lane 0 reads it after these in-order LDS writes of its own wave)
     if (writer && threadIdx.x < (int)(sizeof(Ctl) / 8))
       reinterpret_cast<double*>(&cs)[threadIdx.x] = reinterpret_cast<const double*>(&c0)[threadIdx.x];
-    // first (the host's launch 0 of a tCG loop): a robot in it is at
+    // GRAD (the host's launch 0 of a tCG loop): a robot in it is at
     // PH_START, the first step of the tCG, whose gradient reduction (k_grad's
     // partials) this launch also consumes in place of a k_reduce launch; later
-    // launches find it in PH_TCG. The robot sums' loads go out before the
-    // state arrives.
-    const bool grad = (first_launch & 1) != 0;
-    const bool upd = !grad;
-    RobotSum<2> rs;  // (four tiles per thread here: spills at 128 VGPRs)
-    RobotSum<3> rg;
-    if (upd) rs.issue(d.part_u, 2, L.rt0, L.rt1);
-    if (grad) rg.issue(d.part, NPART, L.rt0, L.rt1);
+    // launches find it in PH_TCG. With the early decision the robot sums'
+    // loads go out before the state arrives; with the late one they go out
+    // with the epilogue's batch (at kernel entry they would be live across
+    // the whole gather).
+    using RS = std::conditional_t<GRAD, RobotSum<3>, RobotSum<2>>;
+    const double* const part = GRAD ? d.part : d.part_u;
+    constexpr int stride = GRAD ? NPART : 2;
+    RS rs;  // (four tiles per thread here: spills at 128 VGPRs)
+    if constexpr (EARLY) rs.issue(part, stride, L.rt0, L.rt1);
     const int ph0 = c0.phase;  // written by an earlier launch: uniform
-    const bool active = ph0 == (grad ? PH_START : PH_TCG);  // uniform: a tile never straddles robots
+    const bool active = ph0 == (GRAD ? PH_START : PH_TCG);  // uniform: a tile never straddles robots
     auto idle = [&]() {
       if (writer && threadIdx.x == 0) {
         d.ctl2[L.l] = c0;
@@ -1541,13 +1668,15 @@ __device__ __forceinline__ void body_hess(const Dev& d, int first_launch, int sl
     };
     // early (below): the phase test waits in the decision, so the first
     // records load with the state instead of after it
-    // gated (first_launch & 2, a launch the host expects to find robots
-    // stopped): the phase test before the first records are issued, so a
-    // launch with nothing to do reads its control words and leaves
-    if (!active && (!d.p.early_stop || (first_launch & 2))) {
+    // gated (a launch the host expects to find robots stopped): the phase
+    // test before the first records are issued, so a launch with nothing to
+    // do reads its control words and leaves
+    if (!active && (!EARLY || gated)) {
       idle();
       return;
     }
+    tcg_iter = GRAD ? 0 : c0.tcg_iter;
+    first = (tcg_iter == 0) || (KMX_HESS_PROBE & 4);  // (probe 4: no delta_old / Hdelta_old traffic)
     UpdStep u{0, 0, 0.0};
     // the decision runs while the first chunk's records are in flight and
     // before any row is gathered: a robot whose tCG stops here (or whose
@@ -1559,15 +1688,14 @@ __device__ __forceinline__ void body_hess(const Dev& d, int first_launch, int sl
         return false;
       }
       double tot[NPART] = {0.0, 0.0, 0.0, 0.0};
-      if (upd) rs.finish(d.part_u, 2, rl, tot);
-      if (grad) rg.finish(d.part, NPART, rl, tot);
+      rs.finish(part, stride, rl, tot);
       // every thread evaluates the decision; the first tile's thread 0 also
       // updates the robot's state (on an LDS copy: a private one would live in
       // scratch) and publishes it
-      if (upd) u = upd_step(c0.mode, c0.r_stop, c0.lin_stop, c0.z_r, c0.tcg_iter, tot[0], tot[1], d.p);
-      if (grad) u.done = sqrt(tot[1]) < d.p.gn_tol ? 1 : 0;  // control_on's RED_GRAD test
+      if constexpr (GRAD) u.done = sqrt(tot[1]) < d.p.gn_tol ? 1 : 0;  // control_on's RED_GRAD test
+      else u = upd_step(c0.mode, c0.r_stop, c0.lin_stop, c0.z_r, c0.tcg_iter, tot[0], tot[1], d.p);
       if (writer && threadIdx.x == 0) {
-        if (upd || grad) control_on(cs, d, L.l, grad ? RED_GRAD : RED_UPDATE, tot, R, true);
+        control_on(cs, d, L.l, GRAD ? RED_GRAD : RED_UPDATE, tot, R, true);
         d.ctl2[L.l] = cs;
         if (hs) post_status(hs, L.l, seq, cs.phase == PH_TCG);
       }
@@ -1576,14 +1704,17 @@ __device__ __forceinline__ void body_hess(const Dev& d, int first_launch, int sl
     // early (small problems): decide before the gather; otherwise after it,
     // speculatively, so the robot sums' latency hides behind the gather
     bool go;
-    if (d.p.early_stop) {
-      go = hinc_gather<R, RW, false, false>(d, L, d.z, H, smem, decide);
+    if constexpr (EARLY) {
+      go = hinc_gather<R, RW, false, false, HessPF<R, RW, RM>::rows>(d, L, d.z, H, smem, decide, epi);
     } else {
-      hinc_gather<R, RW, false, false>(d, L, d.z, H, smem);
+      auto epi_late = [&]() {
+        epi();
+        rs.issue(part, stride, L.rt0, L.rt1);
+      };
+      hinc_gather<R, RW, false, false, HessPF<R, RW, RM>::rows>(d, L, d.z, H, smem, NoPre{}, epi_late);
       go = decide();
     }
     if (!go) return;
-    tcg_iter = grad ? 0 : c0.tcg_iter;
     beta = u.beta;
   } else {
     // the phase test runs once the first chunk's records are in flight (a
@@ -1594,31 +1725,16 @@ __device__ __forceinline__ void body_hess(const Dev& d, int first_launch, int sl
     const int ph = c.phase;
     tcg_iter = c.tcg_iter;
     beta = c.beta;
-    // gated (first_launch & 2, see the consumer form): no record is fetched
-    // before the phase test
-    if ((first_launch & 2) && ph != PH_TCG) return;
-    if (!hinc_gather<R, RW, true, false>(d, L, d.z, H, smem, [&]() { return ph == PH_TCG; })) return;
+    first = (tcg_iter == 0) || (KMX_HESS_PROBE & 4);
+    // gated (see the consumer form): no record is fetched before the phase test
+    if (gated && ph != PH_TCG) return;
+    if (!hinc_gather<R, RW, true, false, HessPF<R, RW, RM>::rows>(d, L, d.z, H, smem,
+                                                                  [&]() { return ph == PH_TCG; }, epi))
+      return;
   }
-  const bool first = (tcg_iter == 0) || (KMX_HESS_PROBE & 4);  // (probe 4: no delta_old / Hdelta_old traffic)
-  asm volatile("" ::: "memory");  // keep the epilogue loads below the gather loop (VGPR pressure)
-  // every row the epilogue needs in one batch, one round trip after the gather:
-  // the own z row, D_i - S_i (the diagonal block with the tangent correction
-  // -z S folded in), delta_old and H delta_old
-  const int dhn = d.dhn;
-  double dold[4] = {0, 0, 0, 0}, hold[4] = {0, 0, 0, 0};
   if (L.valid) {
     double Dg[16];
-#if KMX_HESS_PROBE & 2  // traffic attribution build: no own-row / diagonal-block loads
-    for (int k = 0; k < 4; ++k) zs[k] = 1e-3 * k;
-    for (int c = 0; c < 16; ++c) Dg[c] = (c % 5 == 0) ? 1.0 : 0.0;
-#else
-    load4(d.z + o, zs);
-    load_sym4(d.hDS + SYM4 * (size_t)L.pose, Dg);
-#endif
-    if (!first) {
-      load4(d.dh + (size_t)((tcg_iter - 1) % dhn) * d.vec + o, dold);
-      load4(d.hd + o, hold);
-    }
+    expand_sym4(dg, Dg);
 #pragma unroll
     for (int c = 0; c < 4; ++c)  // (hinc_gather_src's DIAG term, same expression)
       H[c] += zs[0] * Dg[4 * c] + zs[1] * Dg[4 * c + 1] + zs[2] * Dg[4 * c + 2] + zs[3] * Dg[4 * c + 3];
@@ -2264,11 +2380,11 @@ __global__ __launch_bounds__(BLOCK, LB<R>::w) void k_grad(Dev d, int gated) {
   KMX_SMEM;
   body_grad<R, RW, RM>(d, gated, smem);
 }
-template <int R, int RW, int RM>
-__global__ __launch_bounds__(BLOCK, LB<R>::w) void k_hess(Dev d, int first, int slot, HostStatus* hs,
+template <int R, int RW, int RM, bool GRAD, bool EARLY>
+__global__ __launch_bounds__(BLOCK, LB<R>::w) void k_hess(Dev d, int gated, int slot, HostStatus* hs,
                                                           unsigned long long seq) {
   KMX_SMEM;
-  body_hess<R, RW, RM>(d, first, slot, hs, seq, smem);
+  body_hess<R, RW, RM, GRAD, EARLY>(d, gated, slot, hs, seq, smem);
 }
 template <int R, int RM>
 __global__ __launch_bounds__(BLOCK) void k_update(Dev d, HostStatus* hs, unsigned long long seq, int slot) {
@@ -2887,7 +3003,10 @@ struct kmx_pgo {
   // generations of workgroups, each waiting for its robot's sums)
   int rm = RM_LAUNCH;
   int rm_forced = -1;
+  // consumer-form k_hess: the stop decision before the gather (small problems)
+  // or after it; KMX_HESS_DECIDE forces one (0 after, 1 before)
   int early_stop = 1;
+  int decide_forced = -1;
   static constexpr int RM_CONSUMER_MAX_POSES = 80000;
   bool poll_timeout = false;
   // timing
@@ -3065,7 +3184,6 @@ void sync_params(kmx_pgo* h) {
   p.n_ext = h->n_ext;
   p.rgd = h->P.method == KMX_METHOD_RGD ? 1 : 0;
   p.rgd_step = h->P.rgd_stepsize;
-  p.early_stop = h->early_stop;
   h->dv.ext = h->d_ext;
 }
 
@@ -3199,6 +3317,32 @@ void enqueue_grad_t(kmx_pgo* h, int gated = 0) {
   if (!fold_grad<RM>(h)) red_t<R, RM>(h, RED_GRAD);
 }
 
+// One k_hess launch. fl: bit 0, the host's launch 0 of a tCG loop; bit 1,
+// gated. The consumer form has an instantiation per (launch 0, decision
+// position); e0 / e1 (both or neither) take the dispatch's own start / end
+// timestamps.
+template <int R, int RW, int RM>
+void launch_hess(const kmx_pgo* h, dim3 grid, hipStream_t st, const Dev& dv, int fl, int slot, HostStatus* hs,
+                 unsigned long long seq, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+  const dim3 blk(BLOCK);
+  const int gated = (fl & 2) ? 1 : 0;
+  auto go = [&](auto kern) {
+    if (e0)
+      hipExtLaunchKernelGGL(kern, grid, blk, SmemH<R>::bytes, st, e0, e1, 0u, dv, gated, slot, hs, seq);
+    else
+      hipLaunchKernelGGL(kern, grid, blk, SmemH<R>::bytes, st, dv, gated, slot, hs, seq);
+  };
+  if constexpr (RM == RM_CONSUMER) {
+    const bool grad = (fl & 1) != 0, early = h->early_stop != 0;
+    if (grad && early) go(k_hess<R, RW, RM, true, true>);
+    else if (grad) go(k_hess<R, RW, RM, true, false>);
+    else if (early) go(k_hess<R, RW, RM, false, true>);
+    else go(k_hess<R, RW, RM, false, false>);
+  } else {
+    go(k_hess<R, RW, RM, false, false>);
+  }
+}
+
 template <int R, int RW, int RM>
 void enqueue_tcg_t(kmx_pgo* h) {
   const dim3 grid(h->ntiles), blk(BLOCK);
@@ -3266,12 +3410,7 @@ void enqueue_tcg_t(kmx_pgo* h) {
     const int fl = (j == 0 ? 1 : 0) | (gate ? 2 : 0);
     if constexpr (RM == RM_CONSUMER) {
       // k_hess reports the stop test of the previous step's update
-      if (slot >= 0)  // the events take the dispatch's own start / end timestamps
-        hipExtLaunchKernelGGL((k_hess<R, RW, RM>), grid, blk, SmemH<R>::bytes, h->stream, e0, e1, 0u, h->dv,
-                              fl, slot, hs, seq);
-      else
-        hipLaunchKernelGGL((k_hess<R, RW, RM>), grid, blk, SmemH<R>::bytes, h->stream, h->dv, fl, slot,
-                           hs, seq);
+      launch_hess<R, RW, RM>(h, grid, h->stream, h->dv, fl, slot, hs, seq, e0, e1);
       hipLaunchKernelGGL((k_update<R, RM>), grid, blk, SmemU::bytes, h->stream, h->dv, nullptr, 0ull, slot);
       if (poll && j > 0 && !wait_running(h, seq, 0, h->dv.L)) {
         steps = j + 1;
@@ -3280,11 +3419,7 @@ void enqueue_tcg_t(kmx_pgo* h) {
       }
       continue;
     }
-    if (slot >= 0)
-      hipExtLaunchKernelGGL((k_hess<R, RW, RM>), grid, blk, SmemH<R>::bytes, h->stream, e0, e1, 0u, h->dv, fl, slot,
-                            (HostStatus*)nullptr, 0ull);
-    else
-      hipLaunchKernelGGL((k_hess<R, RW, RM>), grid, blk, SmemH<R>::bytes, h->stream, h->dv, fl, slot, nullptr, 0ull);
+    launch_hess<R, RW, RM>(h, grid, h->stream, h->dv, fl, slot, nullptr, 0ull, e0, e1);
     red_t<R, RM>(h, RED_HESS, nullptr, 0, slot);
     hipLaunchKernelGGL((k_update<R, RM>), grid, blk, SmemU::bytes, h->stream, h->dv, nullptr, seq, -1);
     red_t<R, RM>(h, RED_UPDATE, hs, seq, -1, nullptr);
@@ -3385,12 +3520,11 @@ void enqueue_round_groups_t(kmx_pgo* h, const unsigned char* d_active) {
         const dim3 grid(q[g].d.gnt);
         if constexpr (cons) {
           // k_hess reports the stop test of the previous step's update
-          hipLaunchKernelGGL((k_hess<R, RW, RM>), grid, blk, SmemH<R>::bytes, q[g].s, q[g].d, fl, -1, hs, seq[g]);
+          launch_hess<R, RW, RM>(h, grid, q[g].s, q[g].d, fl, -1, hs, seq[g]);
           hipLaunchKernelGGL((k_update<R, RM>), grid, blk, SmemU::bytes, q[g].s, q[g].d, (HostStatus*)nullptr, 0ull,
                              -1);
         } else {
-          hipLaunchKernelGGL((k_hess<R, RW, RM>), grid, blk, SmemH<R>::bytes, q[g].s, q[g].d, fl, -1,
-                             (HostStatus*)nullptr, 0ull);
+          launch_hess<R, RW, RM>(h, grid, q[g].s, q[g].d, fl, -1, nullptr, 0ull);
           red_g<R>(q[g], RED_HESS);
           hipLaunchKernelGGL((k_update<R, RM>), grid, blk, SmemU::bytes, q[g].s, q[g].d, (HostStatus*)nullptr,
                              seq[g], -1);
@@ -3575,6 +3709,7 @@ extern "C" int kmx_pgo_create(const kmx_pgo_params* params, int device, kmx_pgo*
     const int m = std::atoi(v);
     h->rm_forced = m == 0 ? RM_LAUNCH : m == 2 ? RM_CONSUMER : -1;  // 1 and 3 (tickets, half) were removed
   }
+  if (const char* v = std::getenv("KMX_HESS_DECIDE")) h->decide_forced = std::atoi(v) != 0 ? 1 : 0;
   if (const char* v = std::getenv("KMX_HESS_GATE")) h->hess_gate = std::atoi(v) != 0;
   if (const char* v = std::getenv("KMX_TCG_GROUPS")) {
     const int g = std::atoi(v);
@@ -3690,7 +3825,8 @@ extern "C" int kmx_pgo_set_graph(kmx_pgo* h, int n_robots, const int32_t* n_pose
   h->nloc = nloc;
   h->rm = h->rm_forced >= 0 ? h->rm_forced : (nloc <= kmx_pgo::RM_CONSUMER_MAX_POSES ? RM_CONSUMER : RM_LAUNCH);
   if (onesync(h)) h->rm = RM_CONSUMER;  // its decisions are taken by every workgroup
-  h->early_stop = nloc <= kmx_pgo::RM_CONSUMER_MAX_POSES ? 1 : 0;  // decide before the gather on small problems
+  // decide before the gather on small problems
+  h->early_stop = h->decide_forced >= 0 ? h->decide_forced : (nloc <= kmx_pgo::RM_CONSUMER_MAX_POSES ? 1 : 0);
   const int L = (int)h->robots.size();
   KMX_CHECK(L > 0, KMX_EINVAL, "no local robot");
   KMX_CHECK(L <= 1024, KMX_EUNSUP, "at most 1024 local robots per handle");
