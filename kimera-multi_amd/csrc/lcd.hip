@@ -425,6 +425,44 @@ __device__ void svd3(const double E[9], double U[9], double s[3], double V[9]) {
     for (int r = 0; r < 3; ++r) U[r * 3 + c] = u[c][r];
 }
 
+// svd3's U is orthonormal only where E has rank >= 2 (u2 = E v2 / |E v2| is
+// rounding noise or 0 where s2 is). The 3D-3D and PnP fits form R = V U^T from
+// rank-deficient cross-covariances too (collinear or coincident points) and
+// complete U first (oracle complete_u, line by line): u1 kept (e_x for E = 0),
+// u2 its component orthogonal to u1 (where that vanishes, the coordinate axis
+// least aligned with u1), u3 = u1 x u2. A U whose first two columns are
+// orthogonal to 1e-10 is returned untouched, bit for bit; a non-finite one too.
+__device__ void complete_u(double U[9]) {
+  double u0[3] = {U[0], U[3], U[6]}, u1[3] = {U[1], U[4], U[7]}, u2[3];
+  const double n0 = dot3(u0, u0), n1 = dot3(u1, u1);
+  double d = dot3(u0, u1);
+  const double chk = n0 + n1 + d;
+  if (chk != chk) return;
+  if (n0 > 0.0 && n1 > 0.0 && fabs(d) <= 1e-10) return;
+  if (!(n0 > 0.0)) {
+    u0[0] = 1.0; u0[1] = 0.0; u0[2] = 0.0;
+    d = u1[0];
+  }
+  double w[3] = {u1[0] - d * u0[0], u1[1] - d * u0[1], u1[2] - d * u0[2]};
+  double nw = sqrt(dot3(w, w));
+  if (!(nw > 1e-8)) {
+    int k = 0;
+    double m = fabs(u0[0]);
+    if (fabs(u0[1]) < m) { k = 1; m = fabs(u0[1]); }
+    if (fabs(u0[2]) < m) k = 2;
+    const double c = k == 0 ? u0[0] : (k == 1 ? u0[1] : u0[2]);
+    for (int r = 0; r < 3; ++r) w[r] = ((r == k) ? 1.0 : 0.0) - c * u0[r];
+    nw = sqrt(dot3(w, w));
+  }
+  for (int r = 0; r < 3; ++r) u1[r] = w[r] / nw;
+  cross3(u0, u1, u2);
+  for (int r = 0; r < 3; ++r) {
+    U[r * 3 + 0] = u0[r];
+    U[r * 3 + 1] = u1[r];
+    U[r * 3 + 2] = u2[r];
+  }
+}
+
 __device__ double poly_eval(const double* c, int deg, double z) {
   double v = c[deg];
   for (int i = deg - 1; i >= 0; --i) v = v * z + c[i];
@@ -586,6 +624,7 @@ __device__ double epnp_R_t(const double* pw, const double* uv, const double* alp
       for (int b = 0; b < 3; ++b) H[a * 3 + b] += (pc[3 * i + a] - c0[a]) * (pw[3 * i + b] - w0[b]);
   double U[9], sv[3], Vm[9];
   svd3(H, U, sv, Vm);
+  complete_u(U);
   if (det3(Vm) < 0.0)
     for (int a = 0; a < 3; ++a) U[a * 3 + 2] = -U[a * 3 + 2];
   for (int a = 0; a < 3; ++a)
@@ -804,6 +843,7 @@ __device__ void refit_3d3d(int n, Fetch&& fetch, double R[9], double t[3]) {
   }
   double U[9], sv[3], V[9];
   svd3(H, U, sv, V);
+  complete_u(U);
   for (int a = 0; a < 3; ++a)
     for (int b = 0; b < 3; ++b) R[a * 3 + b] = V[a * 3 + 0] * U[b * 3 + 0] + V[a * 3 + 1] * U[b * 3 + 1] + V[a * 3 + 2] * U[b * 3 + 2];
   if (det3(R) < 0.0) {
@@ -2571,6 +2611,7 @@ __device__ __noinline__ void ransac_tail(int c, WS& w, double* F1, double* F2, c
       }
       double U[9], sv[3], V[9], Rr[9];
       svd3(H, U, sv, V);
+      complete_u(U);
       for (int a = 0; a < 3; ++a)
         for (int b = 0; b < 3; ++b)
           Rr[a * 3 + b] = V[a * 3 + 0] * U[b * 3 + 0] + V[a * 3 + 1] * U[b * 3 + 1] + V[a * 3 + 2] * U[b * 3 + 2];
@@ -3174,6 +3215,7 @@ __device__ void arun_model(const double* sq, const double* sm, double R[9], doub
   }
   double U[9], sv[3], V[9];
   svd3(H, U, sv, V);
+  complete_u(U);
   for (int a = 0; a < 3; ++a)
     for (int b = 0; b < 3; ++b) R[a * 3 + b] = V[a * 3 + 0] * U[b * 3 + 0] + V[a * 3 + 1] * U[b * 3 + 1] + V[a * 3 + 2] * U[b * 3 + 2];
   if (det3(R) < 0.0) {

@@ -249,6 +249,45 @@ static void svd3(const double E[9], double U[9], double s[3], double V[9]) {
     for (int r = 0; r < 3; ++r) U[r * 3 + c] = u[c][r];
 }
 
+/* svd3's U is orthonormal only where E has rank >= 2: u2 = E v2 / |E v2| is
+ * rounding noise (or 0) where s2 is, and then neither orthogonal to u1 nor
+ * of any meaning. The 3D-3D and PnP fits meet such cross-covariances
+ * (collinear or coincident points) and form R = V U^T from them, so they
+ * complete U to an orthonormal basis first: u1 kept (e_x for E = 0), u2 its
+ * component orthogonal to u1 (where that vanishes, the coordinate axis
+ * least aligned with u1), u3 = u1 x u2. A U whose first two columns are
+ * orthogonal to 1e-10 is returned untouched, bit for bit; a non-finite one too. */
+static void complete_u(double U[9]) {
+  double u0[3] = {U[0], U[3], U[6]}, u1[3] = {U[1], U[4], U[7]}, u2[3];
+  const double n0 = dot3(u0, u0), n1 = dot3(u1, u1);
+  double d = dot3(u0, u1);
+  const double chk = n0 + n1 + d;
+  if (chk != chk) return;
+  if (n0 > 0.0 && n1 > 0.0 && fabs(d) <= 1e-10) return;
+  if (!(n0 > 0.0)) {
+    u0[0] = 1.0; u0[1] = 0.0; u0[2] = 0.0;
+    d = u1[0];
+  }
+  double w[3] = {u1[0] - d * u0[0], u1[1] - d * u0[1], u1[2] - d * u0[2]};
+  double nw = sqrt(dot3(w, w));
+  if (!(nw > 1e-8)) {
+    int k = 0;
+    double m = fabs(u0[0]);
+    if (fabs(u0[1]) < m) { k = 1; m = fabs(u0[1]); }
+    if (fabs(u0[2]) < m) k = 2;
+    const double c = k == 0 ? u0[0] : (k == 1 ? u0[1] : u0[2]);
+    for (int r = 0; r < 3; ++r) w[r] = ((r == k) ? 1.0 : 0.0) - c * u0[r];
+    nw = sqrt(dot3(w, w));
+  }
+  for (int r = 0; r < 3; ++r) u1[r] = w[r] / nw;
+  cross3(u0, u1, u2);
+  for (int r = 0; r < 3; ++r) {
+    U[r * 3 + 0] = u0[r];
+    U[r * 3 + 1] = u1[r];
+    U[r * 3 + 2] = u2[r];
+  }
+}
+
 /* ------------------------------------------------ 5-point (Nister 2004) -- */
 /* Polynomials in (x, y, z): degree-1 terms [x, y, z, 1]; degree-2 terms in
  * the order D2 below; degree-3 terms in the column order MONO of the 10x20
@@ -1193,6 +1232,7 @@ static double epnp_R_t(int n, const double* pw, const double* uv, const double* 
       for (int b = 0; b < 3; ++b) H[a * 3 + b] += (pc[3 * i + a] - c0[a]) * (pw[3 * i + b] - w0[b]);
   double U[9], sv[3], Vm[9];
   svd3(H, U, sv, Vm);
+  complete_u(U);
   /* svd3's U is right-handed (u3 = u1 x u2): for a proper rotation the third
    * left vector carries det(V) (Umeyama: R = U diag(1, 1, det U det V) V^T) */
   if (det3(Vm) < 0.0)
@@ -1507,6 +1547,7 @@ static void arun_model(const double* Pq, const double* Pm, const int32_t* smp, d
   }
   double U[9], sv[3], V[9];
   svd3(H, U, sv, V);
+  complete_u(U);
   for (int a = 0; a < 3; ++a)
     for (int b = 0; b < 3; ++b) R[a * 3 + b] = V[a * 3 + 0] * U[b * 3 + 0] + V[a * 3 + 1] * U[b * 3 + 1] + V[a * 3 + 2] * U[b * 3 + 2];
   if (det3(R) < 0.0) {
@@ -1557,6 +1598,7 @@ static void refit_3d3d(int n, const double* Pq, const double* Pm, const uint8_t*
   }
   double U[9], sv[3], V[9];
   svd3(H, U, sv, V);
+  complete_u(U);
   for (int a = 0; a < 3; ++a)
     for (int b = 0; b < 3; ++b) R[a * 3 + b] = V[a * 3 + 0] * U[b * 3 + 0] + V[a * 3 + 1] * U[b * 3 + 1] + V[a * 3 + 2] * U[b * 3 + 2];
   if (det3(R) < 0.0) {
