@@ -443,7 +443,10 @@ __device__ __forceinline__ double incidence_row(const Edge& E, bool self_tail, c
 // lanes of one wave exchange data (in-order LDS queue; no workgroup barrier).
 // LDS = false: 6 shuffle sums, each chained to the previous one (empty asm) so
 // only one sum's R shuffles are in flight (VGPR pressure).
-template <int R, bool LDS = false>
+// FL (LDS form): the group members whose read-back is in flight at a time.
+constexpr int GSYM_FLIGHT = 2;
+constexpr int GSYM_ALL = 8;  // >= R: no bound (k_eval, the parity primitive, which runs at 128 VGPRs either way)
+template <int R, bool LDS = false, int FL = GSYM_FLIGHT>
 __device__ __forceinline__ void group_symYtG(const double y[4], const double G[4], int base, double S[9],
                                              double* scr = nullptr) {
   if constexpr (LDS) {
@@ -459,10 +462,23 @@ __device__ __forceinline__ void group_symYtG(const double y[4], const double G[4
     asm volatile("" ::: "memory");
     const double* grp = scr + 6 * ((threadIdx.x & ~63u) + base);
     double t[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    // FL members' values in flight at a time (12 VGPRs each; all R at once
+    // set the register count of the element-wise kernels); the adds keep their
+    // order m = 0 .. R - 1
+    if constexpr (FL >= R) {
 #pragma unroll
-    for (int m = 0; m < R; ++m)
+      for (int m = 0; m < R; ++m)
 #pragma unroll
-      for (int j = 0; j < 6; ++j) t[j] += grp[6 * m + j];
+        for (int j = 0; j < 6; ++j) t[j] += grp[6 * m + j];
+    } else {
+#pragma unroll
+      for (int m = 0; m < R; ++m) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) t[j] += grp[6 * m + j];
+        if ((m + 1) % FL == 0 && m + 1 < R)
+          asm volatile("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5])::"memory");
+      }
+    }
     asm volatile("" ::: "memory");
     __builtin_amdgcn_wave_barrier();
     int j = 0;
@@ -489,11 +505,11 @@ __device__ __forceinline__ void group_symYtG(const double y[4], const double G[4
 }
 
 // Tangent projection of row V at Y (group-cooperative): V_Y - Y sym(Y^T V_Y).
-template <int R, bool LDS = false>
+template <int R, bool LDS = false, int FL = GSYM_FLIGHT>
 __device__ __forceinline__ void group_proj(const double y[4], const double V[4], int base, double out[4],
                                            double* scr = nullptr) {
   double S[9];
-  group_symYtG<R, LDS>(y, V, base, S, scr);
+  group_symYtG<R, LDS, FL>(y, V, base, S, scr);
 #pragma unroll
   for (int c = 0; c < 3; ++c) out[c] = V[c] - (y[0] * S[0 * 3 + c] + y[1] * S[1 * 3 + c] + y[2] * S[2 * 3 + c]);
   out[3] = V[3];
@@ -501,7 +517,7 @@ __device__ __forceinline__ void group_proj(const double y[4], const double V[4],
 
 // Preconditioner: P_Y(V Pinv_i) (block-Jacobi on Q's 4x4 diagonal blocks).
 // Pre (LDS form only, has_pre): the pose's block, already loaded by the caller.
-template <int R, bool LDS = false>
+template <int R, bool LDS = false, int FL = GSYM_FLIGHT>
 __device__ __forceinline__ void group_precon(const Dev& d, int pose, bool valid, const double y[4],
                                              const double V[4], int base, double out[4], double* scr = nullptr,
                                              const double* Pre = nullptr, bool has_pre = false) {
@@ -523,19 +539,19 @@ __device__ __forceinline__ void group_precon(const Dev& d, int pose, bool valid,
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int k = 0; k < 4; ++k) buf[k] = (i == 0) ? V[0] * P[k] : buf[k] + V[i] * P[4 * i + k];
-  group_proj<R, LDS>(y, buf, base, out, scr);
+  group_proj<R, LDS, FL>(y, buf, base, out, scr);
 }
 
 // Riemannian Hessian row of V given the Euclidean Hessian row H:
 // P_Y(H_Y - V_Y S) ; p-part H_p.
-template <int R, bool LDS = false>
+template <int R, bool LDS = false, int FL = GSYM_FLIGHT>
 __device__ __forceinline__ void group_rhess(const double y[4], const double V[4], const double H[4],
                                             const double S[9], int base, double out[4], double* scr = nullptr) {
   double buf[4];
 #pragma unroll
   for (int k = 0; k < 3; ++k) buf[k] = H[k] - (V[0] * S[0 * 3 + k] + V[1] * S[1 * 3 + k] + V[2] * S[2 * 3 + k]);
   buf[3] = H[3];
-  group_proj<R, LDS>(y, buf, base, out, scr);
+  group_proj<R, LDS, FL>(y, buf, base, out, scr);
 }
 
 // QF retraction (modified Gram-Schmidt over the 3 columns, positive diagonal).
@@ -1185,6 +1201,21 @@ __device__ void control_on(Ctl& c, const Dev& d, int l, int kind, const double* 
   control_core(c, d, l, kind, tot, R_, side);
 }
 
+// The robot's state from a workgroup's LDS copy to global memory, one 8-byte
+// word per lane of wave 0's first 32 (k_reduce's write-back). A single thread
+// that assigns the struct holds its 256 B in 64 VGPRs at once, which set the
+// consumer k_update's register count. `retracted`: the copy with that flag set.
+__device__ __forceinline__ void ctl_publish(Ctl* dst, const Ctl& cs, bool retracted) {
+  constexpr int CW = sizeof(Ctl) / 8;
+  constexpr int RWORD = offsetof(Ctl, retracted) / 8;
+  static_assert(CW <= 64 && offsetof(Ctl, retracted) % 8 == 0, "one word per lane; retracted is a low half");
+  if (threadIdx.x < CW) {
+    double w = reinterpret_cast<const double*>(&cs)[threadIdx.x];
+    if (retracted && threadIdx.x == RWORD) w = __hiloint2double(__double2hiint(w), 1);
+    reinterpret_cast<double*>(dst)[threadIdx.x] = w;
+  }
+}
+
 // RM_LAUNCH: one workgroup per robot reduces the robot's tile partials in
 // tile order and runs the control logic (after k_update it also reports the
 // robot's tCG progress to the host).
@@ -1796,8 +1827,6 @@ __device__ __forceinline__ void body_update(const Dev& d, HostStatus* hs, unsign
   double coef;
   const size_t o = (size_t)L.pose * 4 * R + 4 * L.a;
   double rr[4] = {0, 0, 0, 0}, y[4] = {0, 0, 0, 0}, hdl[4] = {0, 0, 0, 0};
-  double Pm[16];
-  bool pre = false;
   if constexpr (RM == RM_CONSUMER) {
     // this step's k_hess partials: the control step after the Hess-vec (alpha
     // or the boundary tau) on a private copy, with the step's vector loads in
@@ -1826,13 +1855,10 @@ __device__ __forceinline__ void body_update(const Dev& d, HostStatus* hs, unsign
           eta_rows<false>(d, L.l, o2, cq.tcg_iter, 0.0, et);
         }
         trial_rows<R>(d, L, o2, x, gg, rr2, et, smem);
-        if (writer && threadIdx.x == 0) {
-          cout[L.l] = cq;
-          cout[L.l].retracted = 1;
-        }
+        if (writer) ctl_publish(cout + L.l, cs, true);
         return;
       }
-      if (writer && threadIdx.x == 0) cout[L.l] = cq;
+      if (writer) ctl_publish(cout + L.l, cs, false);
       return;
     }
     const bool first0 = cq.tcg_iter == 0;  // the control step makes it 1
@@ -1842,22 +1868,26 @@ __device__ __forceinline__ void body_update(const Dev& d, HostStatus* hs, unsign
       load4(d.hd + o, hdl);
       load4((first0 ? d.g : d.r) + o, rr);
       load4(d.X + o, y);  // the projection of H delta, and the precon of interior steps
-      if (d.p.use_precond) {  // the preconditioner block too: no load after the decision
-        load_sym4(d.Pinv + SYM4 * (size_t)L.pose, Pm);
-      }
+      // (the preconditioner block loads in group_precon, after the projection:
+      // held from here it is 20 VGPRs across the projection's read-back, 86
+      // against 66 in all, and the round is slower for it)
     }
     double tot[NPART] = {0.0, 0.0, 0.0, 0.0};
     rs.finish(d.part_h, 2, rl, tot);
     const HessStep hsx = hess_step(cq.z_r, cq.e_Pe, cq.e_Pd, cq.d_Pd, cq.Delta, tot[0]);
-    if (writer && threadIdx.x == 0) {  // the state update, on an LDS copy
-      control_on(cs, d, L.l, RED_HESS, tot, R, true);
-      cout[L.l] = cs;
-      if (slot >= 0) atomicAdd(d.hv_launch + slot, 1);
+    if (writer && threadIdx.x < 64) {  // the state update, on an LDS copy, by wave 0
+      if (threadIdx.x == 0) {
+        control_on(cs, d, L.l, RED_HESS, tot, R, true);
+        if (slot >= 0) atomicAdd(d.hv_launch + slot, 1);
+      }
+      // lane 0's LDS writes, then the wave's reads (in-order LDS queue)
+      __builtin_amdgcn_wave_barrier();
+      asm volatile("" ::: "memory");
+      ctl_publish(cout + L.l, cs, false);
     }
     tcg_iter = cq.tcg_iter + 1;
     mode = hsx.boundary ? MODE_BOUNDARY : MODE_INTERIOR;
     coef = hsx.coef;
-    pre = L.valid;
   } else {
     const Ctl& c = d.ctl[L.l];
     if (c.phase != PH_TCG) {  // not in tCG: the robot's first tile reports it
@@ -1885,8 +1915,7 @@ __device__ __forceinline__ void body_update(const Dev& d, HostStatus* hs, unsign
   }
   double vals[2] = {0.0, 0.0}, zr[4] = {0, 0, 0, 0};
   if (interior) {  // uniform per robot
-    group_precon<R, true>(d, L.pose, L.valid, y, rr, L.base, zr, reinterpret_cast<double*>(smem),
-                          Pm, pre);
+    group_precon<R, true>(d, L.pose, L.valid, y, rr, L.base, zr, reinterpret_cast<double*>(smem));
     if (L.valid) {
       vals[0] = rr[0] * rr[0] + rr[1] * rr[1] + rr[2] * rr[2] + rr[3] * rr[3];
       vals[1] = zr[0] * rr[0] + zr[1] * rr[1] + zr[2] * rr[2] + zr[3] * rr[3];
@@ -2818,7 +2847,7 @@ __global__ __launch_bounds__(BLOCK, LB<R>::w) void k_eval(Dev d, int robot, int 
       load4(V + o, v);
     }
     double S[9];
-    group_symYtG<R, true>(y, G, L.base, S, scr);
+    group_symYtG<R, true, GSYM_ALL>(y, G, L.base, S, scr);
     if (mode == KMX_EVAL_RGRAD) {
       for (int c = 0; c < 3; ++c) res[c] = G[c] - (y[0] * S[0 * 3 + c] + y[1] * S[1 * 3 + c] + y[2] * S[2 * 3 + c]);
       res[3] = G[3];
@@ -2827,9 +2856,9 @@ __global__ __launch_bounds__(BLOCK, LB<R>::w) void k_eval(Dev d, int robot, int 
       __syncthreads();  // the scratch reads are done before the next gather reuses the LDS
       double H[4];
       hinc_gather<R, RW>(d, L, V, H, smem);
-      group_rhess<R, true>(y, v, H, S, L.base, res, scr);
+      group_rhess<R, true, GSYM_ALL>(y, v, H, S, L.base, res, scr);
     } else if (mode == KMX_EVAL_PRECON) {
-      group_precon<R, true>(d, L.pose, L.valid, y, v, L.base, res, scr);
+      group_precon<R, true, GSYM_ALL>(d, L.pose, L.valid, y, v, L.base, res, scr);
     } else if (mode == KMX_EVAL_RETRACT) {
       group_retract<R>(y, v, L.base, res);
       for (int k = 0; k < 4; ++k) v[k] = 0.0;
