@@ -20,11 +20,10 @@
 //   * Edge data: one 64-B compact record per incidence in CSR order (three
 //     components of R's unit quaternion, t, w kappa, +-w tau — the sign bit is
 //     the tail flag) plus a 4-B word (Dev::rec_o): its other endpoint and, in
-//     bits 29-31, the index of the quaternion's dropped largest component;
-//     68 B per incidence
-//     (struct Rec<10>); or a 128-B record with the full rotation when some
-//     measurement is not a rotation to 1e-12 (Rec<16>). The gathers are
-//     incidence-parallel:
+//     bits 29-31, the index of the quaternion's dropped largest component,
+//     which the device rebuilds: 68 B per incidence (struct Rec<10>); or a
+//     128-B record with the full rotation when some measurement is not a
+//     rotation to 1e-12 (Rec<16>). The gathers are incidence-parallel:
 //     one lane per incidence evaluates its block against the neighbour's whole
 //     r x 4 row and parks the r contribution rows in LDS; the (pose, row) lanes
 //     then add their pose's contributions in CSR (= increasing edge id) order.
@@ -2918,7 +2917,6 @@ struct kmx_pgo {
   double* d_coefh = nullptr;  // [L][tcg_max]
   double* d_part_f = nullptr;  // [ntiles][8] one-sync tCG partials (P.tcg_form)
   int ctl_par = 0;             // one-sync tCG: the state after the last tCG loop is in ctl2 (odd step count)
-  bool tcg_stopped = false;    // consumer tCG loop saw every robot stop (each was retracted by its k_update)
   double *d_S = nullptr, *d_Pinv = nullptr, *d_hD = nullptr, *d_hDS = nullptr, *d_pub = nullptr, *d_part = nullptr;
   Ctl* d_ctl = nullptr;
   Ctl* d_ctl2 = nullptr;
@@ -2967,8 +2965,7 @@ struct kmx_pgo {
   double *d_xsbuf = nullptr, *d_xrbuf = nullptr;
   long long xn_send = 0, xn_recv = 0;
   std::vector<long long> xs_cnt, xr_cnt, xs_off, xr_off;  // per peer, in doubles (rows * 4r + 1 status)
-  int blind_left = 0;
-  static constexpr int BLIND_SLACK = 2, BLIND_WINDOW = 8;
+  static constexpr int BLIND_SLACK = 2, BLIND_WINDOW = 8;  // the window's state: Group::blind_left
   // Robot groups (KMX_TCG_GROUPS = 1, 2 or 4; default 2): between a round's
   // k_begin and its final k_commit a robot's launches read only its own rows
   // and the public table, which changes only in that k_commit (DESIGN.md
@@ -2987,13 +2984,17 @@ struct kmx_pgo {
   struct Group {
     int l0 = 0, l1 = 0;  // local robots [l0, l1)
     int t0 = 0, nt = 0;  // their tiles [t0, t0 + nt)
-    int blind_left = 0;  // the group's own adaptive polling state
+    int blind_left = 0;  // the chain's own adaptive polling state
   };
   int groups_req = 2;
   std::vector<Group> grp;  // the cut of the current graph (one group: no fork)
+  // The single chain: every local robot and every tile on the handle's
+  // stream. Its adaptive polling state is its own, apart from grp[0]'s.
+  Group all;
   // The grouped round's reduction form (KMX_GROUP_RED = 0 launched, 2
-  // consumer): which of the two forms below the groups' chains take; `rm`
-  // still decides whether groups are in effect and the single chain's form.
+  // consumer): which instantiation of enqueue_round_t the groups' chains
+  // take; `rm` still decides whether groups are in effect and the single
+  // chain's form.
   // On one chain the consumer form only ties at 100k poses (above); on two
   // chains it drops 22 of a chain's 45 launches and the other group's
   // workgroups fill part of the waits for the robot sums: configs[3]
@@ -3109,51 +3110,47 @@ int dalloc(T** p, size_t count) {
   return 0;
 }
 
+// hipFree and null every buffer of a list: a buffer is named once here
+// besides its allocation.
+template <typename... T>
+void free_all(T*&... p) {
+  (((p ? (void)hipFree(p) : (void)0), p = nullptr), ...);
+}
+
 void free_xchg(kmx_pgo* h) {
-  void* ptrs[] = {h->d_xs_slots, h->d_xr_slots, h->d_xs_seg, h->d_xr_seg, h->d_xs_rseg, h->d_xr_rseg,
-                  h->d_xsbuf, h->d_xrbuf};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
-  h->d_xs_slots = h->d_xr_slots = h->d_xs_seg = h->d_xr_seg = h->d_xs_rseg = h->d_xr_rseg = nullptr;
-  h->d_xsbuf = h->d_xrbuf = nullptr;
+  free_all(h->d_xs_slots, h->d_xr_slots, h->d_xs_seg, h->d_xr_seg, h->d_xs_rseg, h->d_xr_rseg, h->d_xsbuf,
+           h->d_xrbuf);
   h->xchg = false;
 }
 
 void free_dev(kmx_pgo* h) {
-  void* ptrs[] = {h->d_tile, h->d_rtile0, h->d_inc_ptr, h->d_rec, h->d_rec_o, h->d_ekappa,
-                  h->d_etau, h->d_ew, h->d_eipos, h->d_vec, h->d_S, h->d_Pinv, h->d_hD, h->d_hDS, h->d_pub, h->d_part,
-                  h->d_ctl, h->d_cnt, h->d_m_robot, h->d_n_robot, h->d_pub_src, h->d_own_src,
-                  h->d_pose_slot, h->d_gnc_edge, h->d_gnc_ends, h->d_sh_edge, h->d_sh_idx, h->d_osh_edge,
-                  h->d_osh_idx, h->d_relc, h->d_gnc, h->d_ext, h->d_active, h->d_scratch, h->d_hv_launch,
-                  h->d_accV, h->d_accY, h->d_ctl2, h->d_part_h,
-                  h->d_part_u, h->d_coefh, h->d_part_f};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  h->d_tile = nullptr;
-  h->d_rtile0 = h->d_inc_ptr = nullptr;
-  h->d_rec = h->d_ekappa = h->d_etau = h->d_ew = nullptr;
-  h->d_rec_o = nullptr;
-  h->d_eipos = nullptr;
-  h->d_vec = h->d_S = h->d_Pinv = h->d_hD = h->d_hDS = h->d_pub = h->d_part = nullptr;
-  h->d_ctl = nullptr;
-  h->d_cnt = nullptr;
-  h->d_m_robot = nullptr;
-  h->d_n_robot = h->d_pub_src = h->d_own_src = h->d_pose_slot = h->d_gnc_edge = nullptr;
-  h->d_gnc_ends = nullptr;
-  h->d_sh_edge = h->d_sh_idx = h->d_osh_edge = h->d_osh_idx = nullptr;
-  h->d_relc = nullptr;
-  h->d_gnc = nullptr;
-  h->d_ext = nullptr;
+  free_all(h->d_tile, h->d_rtile0, h->d_inc_ptr, h->d_rec, h->d_rec_o, h->d_ekappa, h->d_etau, h->d_ew, h->d_eipos,
+           h->d_vec, h->d_S, h->d_Pinv, h->d_hD, h->d_hDS, h->d_pub, h->d_part, h->d_ctl, h->d_cnt, h->d_m_robot,
+           h->d_n_robot, h->d_pub_src, h->d_own_src, h->d_pose_slot, h->d_gnc_edge, h->d_gnc_ends, h->d_sh_edge,
+           h->d_sh_idx, h->d_osh_edge, h->d_osh_idx, h->d_relc, h->d_gnc, h->d_ext, h->d_active, h->d_scratch,
+           h->d_hv_launch, h->d_accV, h->d_accY, h->d_ctl2, h->d_part_h, h->d_part_u, h->d_coefh, h->d_part_f);
   h->ext_cap = 0;
-  h->d_active = nullptr;
-  h->d_scratch = nullptr;
   h->scratch_cap = 0;
-  h->d_hv_launch = nullptr;
-  h->d_accV = h->d_accY = nullptr;
-  h->d_ctl2 = nullptr;
-  h->d_coefh = nullptr;
-  h->d_part_h = h->d_part_u = nullptr;
-  h->d_part_f = nullptr;
+}
+
+// The kernels' compile-time sizes from the handle's run-time ones: f is
+// called with a std::integral_constant of the lifted rank r (3..8) or of the
+// record width in doubles (10 / 16).
+template <typename F>
+void with_r(int r, F&& f) {
+  switch (r) {
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+  }
+}
+template <typename F>
+void with_rw(int rw, F&& f) {
+  if (rw == 10) f(std::integral_constant<int, 10>{});
+  else f(std::integral_constant<int, 16>{});
 }
 
 hipEvent_t next_event(kmx_pgo* h) {
@@ -3225,14 +3222,11 @@ void enqueue_publish(kmx_pgo* h) {
                      h->d_pub + (size_t)h->first_owned * ps, h->d_pub_src + h->first_owned, (int)h->n_owned, ps);
 }
 
-template <int RW>
-void enqueue_precond_t(kmx_pgo* h, int gated) {
-  const int blocks = std::max(1, std::min(gated ? 256 : 1024, (h->nloc + 127) / 128));
-  hipLaunchKernelGGL(k_precond<RW>, dim3(blocks), dim3(128), 0, h->stream, h->dv, gated);
-}
 void enqueue_precond(kmx_pgo* h, int gated) {
-  if (h->rw == 10) enqueue_precond_t<10>(h, gated);
-  else enqueue_precond_t<16>(h, gated);
+  const int blocks = std::max(1, std::min(gated ? 256 : 1024, (h->nloc + 127) / 128));
+  with_rw(h->rw, [&](auto RW) {
+    hipLaunchKernelGGL(k_precond<RW()>, dim3(blocks), dim3(128), 0, h->stream, h->dv, gated);
+  });
 }
 
 // Round begin (mode BEGIN_ROUND) and/or GNC update, then the gated
@@ -3247,17 +3241,13 @@ bool enqueue_begin(kmx_pgo* h, const unsigned char* d_active, int mode, bool def
   if (!may_fire) mode |= BEGIN_SOLO;  // no weight update possible: one block, no preconditioner rebuild
   // a capped grid: when the schedule does not fire, the launch costs its dispatch
   const unsigned grid = may_fire ? 1 + (unsigned)std::min(256, std::max(1, (h->n_gnc + 255) / 256)) : 1;
-  if (done) {
-    if (h->rw == 10)
-      hipExtLaunchKernelGGL(k_begin<10>, dim3(grid), dim3(256), 0, h->stream, nullptr, done, 0u, h->dv, d_active, mode,
-                            h->P.r);
+  with_rw(h->rw, [&](auto RW) {
+    if (done)
+      hipExtLaunchKernelGGL(k_begin<RW()>, dim3(grid), dim3(256), 0, h->stream, nullptr, done, 0u, h->dv, d_active,
+                            mode, h->P.r);
     else
-      hipExtLaunchKernelGGL(k_begin<16>, dim3(grid), dim3(256), 0, h->stream, nullptr, done, 0u, h->dv, d_active, mode,
-                            h->P.r);
-  } else if (h->rw == 10)
-    hipLaunchKernelGGL(k_begin<10>, dim3(grid), dim3(256), 0, h->stream, h->dv, d_active, mode, h->P.r);
-  else
-    hipLaunchKernelGGL(k_begin<16>, dim3(grid), dim3(256), 0, h->stream, h->dv, d_active, mode, h->P.r);
+      hipLaunchKernelGGL(k_begin<RW()>, dim3(grid), dim3(256), 0, h->stream, h->dv, d_active, mode, h->P.r);
+  });
   if (may_fire && !defer) enqueue_precond(h, 1);
   return may_fire && defer;
 }
@@ -3284,42 +3274,73 @@ bool wait_running(kmx_pgo* h, unsigned long long seq, int l0, int l1) {
   return running;
 }
 
-template <int R, int RM>
-void red_t(kmx_pgo* h, int kind, HostStatus* hs = nullptr, unsigned long long seq = 0, int slot = -1,
-           const double* src = nullptr) {
-  hipLaunchKernelGGL(k_reduce, dim3(h->dv.L), dim3(RBLOCK), 0, h->stream, h->dv, 0, kind, R, hs, seq, slot, src);
-}
-
-// Robot groups in effect for the next round (kmx_pgo::grp; 1: today's single
-// launch chain).
+// Launch chains of the next round. More than one (the robot groups,
+// kmx_pgo::grp) for RM_LAUNCH and RTR only; the timed replay (its events want
+// launches that do not overlap), RGD and the one-sync tCG run on the single
+// chain (kmx_pgo::all), and enqueue_round_t relies on that: its event slots,
+// its RGD step and its k_step loop know one chain only.
 int groups_in_effect(const kmx_pgo* h) {
   if (h->timing || h->rm != RM_LAUNCH || h->P.method != KMX_METHOD_RTR || onesync(h)) return 1;
   return std::max<int>(1, (int)h->grp.size());
 }
 
-// One group's view of the round: its stream and a Dev whose launches cover
-// the group's tiles; k_reduce over the group's robots.
-struct GroupLaunch {
+// One launch chain of a round: a Dev whose launches cover the chain's tiles,
+// its stream, its robots (k_reduce's first robot and grid) and its polling
+// state.
+struct Chain {
   Dev d;
   hipStream_t s;
   int l0, nl;
+  kmx_pgo::Group* st;
 };
-GroupLaunch group_launch(kmx_pgo* h, int g) {
-  const kmx_pgo::Group& G = h->grp[g];
-  GroupLaunch q{h->dv, g == 0 ? h->stream : h->gstream[g - 1], G.l0, G.l1 - G.l0};
+Chain make_chain(kmx_pgo* h, kmx_pgo::Group& G, hipStream_t s) {
+  Chain q{h->dv, s, G.l0, G.l1 - G.l0, &G};
   q.d.gt0 = G.t0;
   q.d.gnt = G.nt;
   return q;
 }
+// done: an event that completes with this dispatch
 template <int R>
-void red_g(const GroupLaunch& q, int kind, HostStatus* hs = nullptr, unsigned long long seq = 0,
-           hipEvent_t done = nullptr) {
-  if (done)  // the event completes with this dispatch
-    hipExtLaunchKernelGGL(k_reduce, dim3(q.nl), dim3(RBLOCK), 0, q.s, nullptr, done, 0u, q.d, q.l0, kind, R, hs, seq, -1,
-                          (const double*)nullptr);
+void red(const Chain& q, int kind, HostStatus* hs = nullptr, unsigned long long seq = 0, int slot = -1,
+         hipEvent_t done = nullptr) {
+  if (done)
+    hipExtLaunchKernelGGL(k_reduce, dim3(q.nl), dim3(RBLOCK), 0, q.s, nullptr, done, 0u, q.d, q.l0, kind, R, hs, seq,
+                          slot, (const double*)nullptr);
   else
-    hipLaunchKernelGGL(k_reduce, dim3(q.nl), dim3(RBLOCK), 0, q.s, q.d, q.l0, kind, R, hs, seq, -1,
+    hipLaunchKernelGGL(k_reduce, dim3(q.nl), dim3(RBLOCK), 0, q.s, q.d, q.l0, kind, R, hs, seq, slot,
                        (const double*)nullptr);
+}
+
+// A timed launch's slot of Dev::hv_launch and the events that take the
+// dispatch's own start / end timestamps (none while timing is off or the
+// slots are used up).
+struct Timed {
+  int slot = -1;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+};
+Timed next_timed(kmx_pgo* h) {
+  Timed t;
+  if (h->timing && h->ev_used / 2 < (size_t)HV_SLOTS) {
+    t.slot = (int)(h->ev_used / 2);
+    t.e0 = next_event(h);
+    t.e1 = next_event(h);
+  }
+  return t;
+}
+
+// Whether a chain's next tCG loop polls or goes blind, and what a loop that
+// enqueued `steps` steps means for the next ones (see kmx_pgo::poll_auto).
+bool tcg_polls(kmx_pgo* h, kmx_pgo::Group& st) {
+  if (!(h->poll && h->hstat)) return false;
+  if (h->poll_auto && st.blind_left > 0) {
+    --st.blind_left;
+    return false;
+  }
+  return true;
+}
+void tcg_polled(const kmx_pgo* h, kmx_pgo::Group& st, bool poll, int steps) {
+  if (poll && h->poll_auto && steps + kmx_pgo::BLIND_SLACK >= h->P.tcg_max_iterations)
+    st.blind_left = kmx_pgo::BLIND_WINDOW;
 }
 
 // The parts of a round: gradient, tCG (host-polled steps), trial point and
@@ -3338,12 +3359,6 @@ bool fold_grad(const kmx_pgo* h) {
 template <int RM>
 bool fold_cost(const kmx_pgo* h) {
   return RM == RM_CONSUMER && (h->P.rtr_iterations == 1 || h->P.method == KMX_METHOD_RGD);
-}
-
-template <int R, int RW, int RM>
-void enqueue_grad_t(kmx_pgo* h, int gated = 0) {
-  hipLaunchKernelGGL((k_grad<R, RW, RM>), dim3(h->ntiles), dim3(BLOCK), SmemHG<R>::bytes, h->stream, h->dv, gated);
-  if (!fold_grad<RM>(h)) red_t<R, RM>(h, RED_GRAD);
 }
 
 // One k_hess launch. fl: bit 0, the host's launch 0 of a tCG loop; bit 1,
@@ -3372,226 +3387,164 @@ void launch_hess(const kmx_pgo* h, dim3 grid, hipStream_t st, const Dev& dv, int
   }
 }
 
+// The tCG loops of G chains: each step is (k_hess, k_update), with their
+// k_reduce launches in the launched form, enqueued launch by launch across
+// the chains so no stream runs dry while the host serves another. The loops
+// poll per chain: a chain whose robots have all left tCG is no longer
+// enqueued while the others go on. stopped[g]: the polled loop saw chain g's
+// robots stop.
 template <int R, int RW, int RM>
-void enqueue_tcg_t(kmx_pgo* h) {
-  const dim3 grid(h->ntiles), blk(BLOCK);
-  // tCG: each step is (k_hess, k_update); with polling, exactly one step
-  // stays queued beyond the last one known to be needed
-  unsigned long long prev = 0;
-  // this loop polled or blind (see kmx_pgo::poll_auto)
-  bool poll = h->poll && h->hstat;
-  if (poll && h->poll_auto && h->blind_left > 0) {
-    --h->blind_left;
-    poll = false;
-  }
+void enqueue_tcg_t(kmx_pgo* h, const Chain* q, int G, bool* stopped) {
+  constexpr bool cons = RM == RM_CONSUMER;
+  const dim3 blk(BLOCK);
   const int tmax = h->P.tcg_max_iterations;
-  int steps = tmax;  // steps enqueued by a polled loop
-  h->tcg_stopped = false;
-  if constexpr (RM == RM_CONSUMER) {
-    if (onesync(h)) {
-      // one k_step per step: launch j applies step j-1's decision (which it
-      // reports at its start) and runs Hess-vec j; launch tmax only decides.
-      // A polled loop waits for launch j's report while launch j still
-      // gathers, so the next launch is queued before the GPU runs dry.
-      int J = tmax + 1;
-      for (int j = 0; j <= tmax; ++j) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        int slot = -1;
-        if (h->timing && h->ev_used / 2 < (size_t)HV_SLOTS) {
-          slot = (int)(h->ev_used / 2);
-          e0 = next_event(h);
-          e1 = next_event(h);
-        }
-        poll = poll && h->poll;
-        const unsigned long long seq = poll ? ++h->seq : 0;
-        HostStatus* hs = poll ? h->hstat : nullptr;
-        const Ctl* cin = (j & 1) ? h->d_ctl2 : h->d_ctl;
-        Ctl* cout = (j & 1) ? h->d_ctl : h->d_ctl2;
-        if (slot >= 0)  // the events take the dispatch's own start / end timestamps
-          hipExtLaunchKernelGGL((k_step<R, RW>), grid, blk, SmemF<R>::bytes, h->stream, e0, e1, 0u, h->dv, cin,
-                                cout, j, slot, hs, seq);
-        else
-          hipLaunchKernelGGL((k_step<R, RW>), grid, blk, SmemF<R>::bytes, h->stream, h->dv, cin, cout, j,
-                             slot, hs, seq);
-        if (poll && j > 0 && !wait_running(h, seq, 0, h->dv.L)) {
-          J = j + 1;
-          break;
-        }
-      }
-      h->ctl_par = J & 1;
-      steps = J - 1;
-      if (poll && h->poll_auto && steps + kmx_pgo::BLIND_SLACK >= tmax) h->blind_left = kmx_pgo::BLIND_WINDOW;
-      return;
-    }
+  bool poll[kmx_pgo::MAX_GROUPS], live[kmx_pgo::MAX_GROUPS];
+  unsigned long long prev[kmx_pgo::MAX_GROUPS], seq[kmx_pgo::MAX_GROUPS];
+  int steps[kmx_pgo::MAX_GROUPS];  // steps enqueued by a polled loop
+  for (int g = 0; g < G; ++g) {
+    poll[g] = tcg_polls(h, *q[g].st);
+    live[g] = true;
+    prev[g] = seq[g] = 0;
+    steps[g] = tmax;
   }
   for (int j = 0; j < tmax; ++j) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int slot = -1;
-    if (h->timing && h->ev_used / 2 < (size_t)HV_SLOTS) {
-      slot = (int)(h->ev_used / 2);
-      e0 = next_event(h);
-      e1 = next_event(h);
-    }
-    poll = poll && h->poll;  // a poll timeout inside wait_running switches to blind
-    const unsigned long long seq = poll ? ++h->seq : 0;
-    HostStatus* hs = poll ? h->hstat : nullptr;
-    const bool gate = j > 0 && h->hess_gate;
-    const int fl = (j == 0 ? 1 : 0) | (gate ? 2 : 0);
-    if constexpr (RM == RM_CONSUMER) {
-      // k_hess reports the stop test of the previous step's update
-      launch_hess<R, RW, RM>(h, grid, h->stream, h->dv, fl, slot, hs, seq, e0, e1);
-      hipLaunchKernelGGL((k_update<R, RM>), grid, blk, SmemU::bytes, h->stream, h->dv, nullptr, 0ull, slot);
-      if (poll && j > 0 && !wait_running(h, seq, 0, h->dv.L)) {
-        steps = j + 1;
-        h->tcg_stopped = true;
-        break;
+    bool any = false;
+    for (int g = 0; g < G; ++g) {
+      if (!live[g]) continue;
+      any = true;
+      const Timed t = next_timed(h);  // timing runs one chain (groups_in_effect)
+      poll[g] = poll[g] && h->poll;   // a poll timeout inside wait_running switches to blind
+      seq[g] = poll[g] ? ++h->seq : 0;
+      HostStatus* hs = poll[g] ? h->hstat : nullptr;
+      const int fl = (j == 0 ? 1 : 0) | (j > 0 && h->hess_gate ? 2 : 0);
+      const dim3 grid(q[g].d.gnt);
+      if constexpr (cons) {
+        // k_hess reports the stop test of the previous step's update
+        launch_hess<R, RW, RM>(h, grid, q[g].s, q[g].d, fl, t.slot, hs, seq[g], t.e0, t.e1);
+        hipLaunchKernelGGL((k_update<R, RM>), grid, blk, SmemU::bytes, q[g].s, q[g].d, (HostStatus*)nullptr, 0ull,
+                           t.slot);
+      } else {
+        launch_hess<R, RW, RM>(h, grid, q[g].s, q[g].d, fl, t.slot, nullptr, 0ull, t.e0, t.e1);
+        red<R>(q[g], RED_HESS, nullptr, 0, t.slot);
+        hipLaunchKernelGGL((k_update<R, RM>), grid, blk, SmemU::bytes, q[g].s, q[g].d, (HostStatus*)nullptr, seq[g],
+                           -1);
+        red<R>(q[g], RED_UPDATE, hs, seq[g]);
       }
-      continue;
     }
-    launch_hess<R, RW, RM>(h, grid, h->stream, h->dv, fl, slot, nullptr, 0ull, e0, e1);
-    red_t<R, RM>(h, RED_HESS, nullptr, 0, slot);
-    hipLaunchKernelGGL((k_update<R, RM>), grid, blk, SmemU::bytes, h->stream, h->dv, nullptr, seq, -1);
-    red_t<R, RM>(h, RED_UPDATE, hs, seq, -1, nullptr);
-    if (poll) {
-      if (j > 0 && !wait_running(h, prev, 0, h->dv.L)) {
-        steps = j + 1;
-        break;
+    if (!any) break;
+    for (int g = 0; g < G; ++g) {
+      if (!live[g] || !poll[g]) continue;
+      // consumer: this step's k_hess reports (its k_update is queued behind
+      // it); launched: exactly one step stays queued beyond the last one
+      // known to be needed
+      if (j > 0 && !wait_running(h, cons ? seq[g] : prev[g], q[g].l0, q[g].l0 + q[g].nl)) {
+        steps[g] = j + 1;
+        live[g] = false;
+        stopped[g] = true;
       }
-      prev = seq;
+      prev[g] = seq[g];
     }
   }
-  if (poll && h->poll_auto && steps + kmx_pgo::BLIND_SLACK >= tmax) h->blind_left = kmx_pgo::BLIND_WINDOW;
+  for (int g = 0; g < G; ++g) tcg_polled(h, *q[g].st, poll[g], steps[g]);
 }
 
-// after the tCG loop (or the RGD step): trial point and its cost
-template <int R, int RW, int RM>
-void enqueue_trial_t(kmx_pgo* h, bool rgd) {
-  const dim3 grid(h->ntiles), blk(BLOCK);
-  // RM_CONSUMER: the last step's update has no k_hess after it; k_retract
-  // reduces it
-  // one-sync form: each k_step that ended a robot's tCG also formed its trial
-  // point, so there is no k_retract; k_cost takes the state from where the
-  // tCG left it
-  const bool os = RM == RM_CONSUMER && !rgd && onesync(h);
-  const Ctl* src = os && h->ctl_par ? h->d_ctl2 : h->d_ctl;
-  // consumer form: the k_update after the k_hess that stopped a robot formed
-  // its trial point; k_retract (fold 2) decides and retracts the robots still
-  // in tCG at the cap, and is not needed when the polled loop saw every robot
-  // stop
-  const bool cons = RM == RM_CONSUMER && !rgd;
-  if (!os && !(cons && h->tcg_stopped))
-    hipLaunchKernelGGL((k_retract<R>), grid, blk, SmemU::bytes, h->stream, h->dv, cons ? 2 : 0, (const Ctl*)h->d_ctl);
-  hipLaunchKernelGGL((k_cost<R, RW, RM>), grid, blk, SmemC<R>::bytes, h->stream, h->dv, src);
-  if (!fold_cost<RM>(h)) red_t<R, RM>(h, RED_COST);
+// The one-sync tCG loop (one chain): one k_step per step. Launch j applies
+// step j-1's decision (which it reports at its start) and runs Hess-vec j;
+// launch tmax only decides. A polled loop waits for launch j's report while
+// launch j still gathers, so the next launch is queued before the GPU runs
+// dry. The state ping-pongs between ctl and ctl2; kmx_pgo::ctl_par says where
+// the loop left it.
+template <int R, int RW>
+void enqueue_tcg_onesync_t(kmx_pgo* h, const Chain& q) {
+  const dim3 grid(q.d.gnt), blk(BLOCK);
+  const int tmax = h->P.tcg_max_iterations;
+  bool poll = tcg_polls(h, *q.st);
+  int J = tmax + 1;
+  for (int j = 0; j <= tmax; ++j) {
+    const Timed t = next_timed(h);
+    poll = poll && h->poll;
+    const unsigned long long seq = poll ? ++h->seq : 0;
+    HostStatus* hs = poll ? h->hstat : nullptr;
+    const Ctl* cin = (j & 1) ? h->d_ctl2 : h->d_ctl;
+    Ctl* cout = (j & 1) ? h->d_ctl : h->d_ctl2;
+    if (t.e0)
+      hipExtLaunchKernelGGL((k_step<R, RW>), grid, blk, SmemF<R>::bytes, q.s, t.e0, t.e1, 0u, q.d, cin, cout, j,
+                            t.slot, hs, seq);
+    else
+      hipLaunchKernelGGL((k_step<R, RW>), grid, blk, SmemF<R>::bytes, q.s, q.d, cin, cout, j, t.slot, hs, seq);
+    if (poll && j > 0 && !wait_running(h, seq, q.l0, q.l0 + q.nl)) {
+      J = j + 1;
+      break;
+    }
+  }
+  h->ctl_par = J & 1;
+  tcg_polled(h, *q.st, poll, J - 1);
 }
 
-// The round with robot groups (kmx_pgo::grp, RTR): k_begin on
-// the handle's stream, then every group's chain on its own stream, enqueued
-// launch by launch across the groups so no stream runs dry while the host
-// serves another, and the final k_commit of all robots behind the join (it
-// writes the public rows the other groups' k_grad / k_cost read). The tCG
-// loop polls per group: a group whose robots have all left tCG is no longer
-// enqueued while the others go on.
-// RM: the grouped round's reduction form (kmx_pgo::grm). RM_LAUNCH: every
-// group's chain carries its k_reduce launches. RM_CONSUMER: no k_reduce in a
-// chain, as the single-chain consumer form (enqueue_tcg_t, enqueue_trial_t):
-// the gradient's sums go into the group's first k_hess, k_update and k_hess
-// reduce each other's partials, k_retract (fold 2) takes the last update's
-// and the final all-robot k_commit the trial cost's (one RTR iteration; with
-// more, each group keeps its RED_COST k_reduce and its own non-final commit).
+// One round over G >= 1 launch chains (groups_in_effect), all of form RM.
+// k_begin on the handle's stream; then per chain, on its stream, k_grad, the
+// tCG loop, k_retract, k_cost and the non-final k_commit over the chain's
+// tiles; then the final k_commit of all robots on the handle's stream (it
+// writes the public rows the other chains' k_grad / k_cost read).
+// G = 1 is kmx_pgo::all on the handle's stream: no event, no wait. G > 1 are
+// the robot groups, group g > 0 on a stream of its own. Fork: the begin
+// launch's own completion is the event the side streams wait for. Join: each
+// side stream's last launch (the trial cost's k_reduce, or k_cost itself
+// where the final commit takes its sums) carries the event the final commit
+// waits for. Neither puts a marker on the stream it is recorded on, so group
+// 0's k_grad follows k_begin directly.
+// RM_LAUNCH: every chain carries its k_reduce launches. RM_CONSUMER: none
+// (fold_grad, fold_cost above): k_update and k_hess reduce each other's
+// partials, and with more than one RTR iteration each chain keeps its
+// RED_COST k_reduce and its own non-final commit.
 template <int R, int RW, int RM>
-void enqueue_round_groups_t(kmx_pgo* h, const unsigned char* d_active) {
+void enqueue_round_t(kmx_pgo* h, const unsigned char* d_active, int G) {
   constexpr bool cons = RM == RM_CONSUMER;
-  const int G = (int)h->grp.size();
   const dim3 blk(BLOCK);
-  // fork: the begin launch's own completion is the event the side streams wait
-  // for, and join: each side stream's last launch (the trial cost's k_reduce,
-  // or k_cost itself where the final commit takes its sums) carries the event
-  // the final commit waits for. Neither puts a marker on the stream it is
-  // recorded on, so group 0's k_grad follows k_begin directly.
-  const bool pend = enqueue_begin(h, d_active, BEGIN_ROUND, true, h->ev_fork);
-  GroupLaunch q[kmx_pgo::MAX_GROUPS];
-  for (int g = 0; g < G; ++g) q[g] = group_launch(h, g);
+  // one chain only (groups_in_effect): the RGD step and the one-sync tCG
+  const bool rgd = h->P.method == KMX_METHOD_RGD, os = cons && onesync(h);
+  // the round's first k_grad runs the gated preconditioner rebuild (there is
+  // one: set_graph refuses a graph without tiles)
+  const bool pend = enqueue_begin(h, d_active, BEGIN_ROUND, true, G > 1 ? h->ev_fork : nullptr);
+  Chain q[kmx_pgo::MAX_GROUPS];
+  if (G == 1) q[0] = make_chain(h, h->all, h->stream);
+  else
+    for (int g = 0; g < G; ++g) q[g] = make_chain(h, h->grp[g], g == 0 ? h->stream : h->gstream[g - 1]);
   // (an event call's error is left to the caller's hipGetLastError, as a launch's)
   for (int g = 1; g < G; ++g) (void)hipStreamWaitEvent(q[g].s, h->ev_fork, 0);
-  const int iters = h->P.rtr_iterations, tmax = h->P.tcg_max_iterations;
-  const bool fcost = fold_cost<RM>(h);
+  const int iters = rgd ? 1 : h->P.rtr_iterations;
+  const bool fgrad = fold_grad<RM>(h), fcost = fold_cost<RM>(h);
   for (int it = 0; it < iters; ++it) {
     for (int g = 0; g < G; ++g) {
       hipLaunchKernelGGL((k_grad<R, RW, RM>), dim3(q[g].d.gnt), blk, SmemHG<R>::bytes, q[g].s, q[g].d,
                          it == 0 && pend ? 1 : 0);
-      if (!fold_grad<RM>(h)) red_g<R>(q[g], RED_GRAD);
+      if (!fgrad) red<R>(q[g], RED_GRAD);
     }
-    // tCG, as enqueue_tcg_t's loop of the same form, with each group's own polling state
-    bool poll[kmx_pgo::MAX_GROUPS], live[kmx_pgo::MAX_GROUPS], stopped[kmx_pgo::MAX_GROUPS];
-    unsigned long long prev[kmx_pgo::MAX_GROUPS], seq[kmx_pgo::MAX_GROUPS];
-    int steps[kmx_pgo::MAX_GROUPS];
-    for (int g = 0; g < G; ++g) {
-      poll[g] = h->poll && h->hstat;
-      if (poll[g] && h->poll_auto && h->grp[g].blind_left > 0) {
-        --h->grp[g].blind_left;
-        poll[g] = false;
-      }
-      live[g] = true;
-      stopped[g] = false;
-      prev[g] = seq[g] = 0;
-      steps[g] = tmax;
+    bool stopped[kmx_pgo::MAX_GROUPS] = {};
+    if constexpr (cons) {
+      if (os) enqueue_tcg_onesync_t<R, RW>(h, q[0]);
     }
-    for (int j = 0; j < tmax; ++j) {
-      bool any = false;
-      for (int g = 0; g < G; ++g) {
-        if (!live[g]) continue;
-        any = true;
-        poll[g] = poll[g] && h->poll;  // a poll timeout inside wait_running switches to blind
-        seq[g] = poll[g] ? ++h->seq : 0;
-        HostStatus* hs = poll[g] ? h->hstat : nullptr;
-        const int fl = (j == 0 ? 1 : 0) | (j > 0 && h->hess_gate ? 2 : 0);
-        const dim3 grid(q[g].d.gnt);
-        if constexpr (cons) {
-          // k_hess reports the stop test of the previous step's update
-          launch_hess<R, RW, RM>(h, grid, q[g].s, q[g].d, fl, -1, hs, seq[g]);
-          hipLaunchKernelGGL((k_update<R, RM>), grid, blk, SmemU::bytes, q[g].s, q[g].d, (HostStatus*)nullptr, 0ull,
-                             -1);
-        } else {
-          launch_hess<R, RW, RM>(h, grid, q[g].s, q[g].d, fl, -1, nullptr, 0ull);
-          red_g<R>(q[g], RED_HESS);
-          hipLaunchKernelGGL((k_update<R, RM>), grid, blk, SmemU::bytes, q[g].s, q[g].d, (HostStatus*)nullptr,
-                             seq[g], -1);
-          red_g<R>(q[g], RED_UPDATE, hs, seq[g]);
-        }
-      }
-      if (!any) break;
-      for (int g = 0; g < G; ++g) {
-        if (!live[g] || !poll[g]) continue;
-        // consumer: this step's k_hess reports (its k_update is queued behind
-        // it); launched: one step stays queued beyond the last one known to
-        // be needed
-        if (j > 0 && !wait_running(h, cons ? seq[g] : prev[g], h->grp[g].l0, h->grp[g].l1)) {
-          steps[g] = j + 1;
-          live[g] = false;
-          stopped[g] = true;  // consumer: each robot was retracted by the k_update after its last k_hess
-        }
-        prev[g] = seq[g];
-      }
-    }
-    for (int g = 0; g < G; ++g)
-      if (poll[g] && h->poll_auto && steps[g] + kmx_pgo::BLIND_SLACK >= tmax)
-        h->grp[g].blind_left = kmx_pgo::BLIND_WINDOW;
+    if (!rgd && !os) enqueue_tcg_t<R, RW, RM>(h, q, G, stopped);
+    // one-sync: each k_step that ended a robot's tCG also formed its trial
+    // point, so there is no k_retract; k_cost takes the state from where the
+    // tCG left it
+    const Ctl* src = os && h->ctl_par ? h->d_ctl2 : h->d_ctl;
     for (int g = 0; g < G; ++g) {
       const dim3 grid(q[g].d.gnt);
       const bool last = it + 1 == iters;
       hipEvent_t join = g > 0 && last ? h->ev_join[g - 1] : nullptr;
-      // consumer: k_retract (fold 2) decides and retracts the robots still in
-      // tCG at the cap; not needed when the polled loop saw the group's robots stop
-      if (!(cons && stopped[g]))
-        hipLaunchKernelGGL((k_retract<R>), grid, blk, SmemU::bytes, q[g].s, q[g].d, cons ? 2 : 0,
+      // consumer tCG: the k_update after the k_hess that stopped a robot
+      // formed its trial point; k_retract (fold 2) reduces the last update,
+      // decides and retracts the robots still in tCG at the cap, and is not
+      // needed when the polled loop saw the chain's robots stop
+      if (!os && !(cons && stopped[g]))
+        hipLaunchKernelGGL((k_retract<R>), grid, blk, SmemU::bytes, q[g].s, q[g].d, cons && !rgd ? 2 : 0,
                            (const Ctl*)h->d_ctl);
       if (fcost && join)  // the side stream's last dispatch: the join event completes with it
-        hipExtLaunchKernelGGL((k_cost<R, RW, RM>), grid, blk, SmemC<R>::bytes, q[g].s, nullptr, join, 0u, q[g].d,
-                              (const Ctl*)h->d_ctl);
+        hipExtLaunchKernelGGL((k_cost<R, RW, RM>), grid, blk, SmemC<R>::bytes, q[g].s, nullptr, join, 0u, q[g].d, src);
       else
-        hipLaunchKernelGGL((k_cost<R, RW, RM>), grid, blk, SmemC<R>::bytes, q[g].s, q[g].d, (const Ctl*)h->d_ctl);
-      if (!fcost) red_g<R>(q[g], RED_COST, nullptr, 0, join);
+        hipLaunchKernelGGL((k_cost<R, RW, RM>), grid, blk, SmemC<R>::bytes, q[g].s, q[g].d, src);
+      if (!fcost) red<R>(q[g], RED_COST, nullptr, 0, -1, join);
       if (!last)  // the next RTR iteration starts from the accepted point: the robot's own X only
         hipLaunchKernelGGL((k_commit<R>), grid, blk, 0, q[g].s, q[g].d, 0, 0);
     }
@@ -3600,51 +3553,21 @@ void enqueue_round_groups_t(kmx_pgo* h, const unsigned char* d_active) {
   hipLaunchKernelGGL((k_commit<R>), dim3(h->ntiles), blk, 0, h->stream, h->dv, fcost ? 1 : 0, 1);
 }
 
-template <int R, int RW, int RM>
-void enqueue_round_t(kmx_pgo* h, const unsigned char* d_active) {
-  if constexpr (RM == RM_LAUNCH) {
-    if (groups_in_effect(h) > 1) {
-      if (h->grm == RM_CONSUMER) enqueue_round_groups_t<R, RW, RM_CONSUMER>(h, d_active);
-      else enqueue_round_groups_t<R, RW, RM_LAUNCH>(h, d_active);
-      return;
-    }
-  }
-  // no tiles: nothing would run the deferred rebuild
-  const bool pend = enqueue_begin(h, d_active, BEGIN_ROUND, h->ntiles > 0);
-  const bool rgd = h->P.method == KMX_METHOD_RGD;
-  const int iters = rgd ? 1 : h->P.rtr_iterations;
-  for (int it = 0; it < iters; ++it) {
-    enqueue_grad_t<R, RW, RM>(h, it == 0 && pend ? 1 : 0);
-    if (!rgd) enqueue_tcg_t<R, RW, RM>(h);
-    enqueue_trial_t<R, RW, RM>(h, rgd);
-    if (it + 1 < iters)  // the next RTR iteration starts from the accepted point
-      hipLaunchKernelGGL((k_commit<R>), dim3(h->ntiles), dim3(BLOCK), 0, h->stream, h->dv, 0, 0);
-  }
-  hipLaunchKernelGGL((k_commit<R>), dim3(h->ntiles), dim3(BLOCK), 0, h->stream, h->dv, fold_cost<RM>(h) ? 1 : 0, 1);
-}
-
-template <int R>
-void enqueue_round_r(kmx_pgo* h, const unsigned char* d_active) {
-  if (h->rm == RM_CONSUMER) {
-    if (h->rw == 10) enqueue_round_t<R, 10, RM_CONSUMER>(h, d_active);
-    else enqueue_round_t<R, 16, RM_CONSUMER>(h, d_active);
-  } else {
-    if (h->rw == 10) enqueue_round_t<R, 10, RM_LAUNCH>(h, d_active);
-    else enqueue_round_t<R, 16, RM_LAUNCH>(h, d_active);
-  }
-}
-
 // One RBCD round for the robots whose d_active flag is set; it starts with
-// the scheduled GNC decision when the handle's schedule is enabled.
+// the scheduled GNC decision when the handle's schedule is enabled. The
+// robot groups take their own reduction form (kmx_pgo::grm).
 void enqueue_round(kmx_pgo* h, const unsigned char* d_active) {
-  switch (h->P.r) {
-    case 3: enqueue_round_r<3>(h, d_active); break;
-    case 4: enqueue_round_r<4>(h, d_active); break;
-    case 5: enqueue_round_r<5>(h, d_active); break;
-    case 6: enqueue_round_r<6>(h, d_active); break;
-    case 7: enqueue_round_r<7>(h, d_active); break;
-    default: enqueue_round_r<8>(h, d_active); break;
-  }
+  const int G = groups_in_effect(h);
+  const int rm = G > 1 ? h->grm : h->rm;
+  // (the form outside the record width: the kernels' instantiations then
+  // stand in the code object in the order they were measured in)
+  with_r(h->P.r, [&](auto R) {
+    constexpr int r = decltype(R)::value;
+    if (rm == RM_CONSUMER)
+      with_rw(h->rw, [&](auto RW) { enqueue_round_t<r, RW(), RM_CONSUMER>(h, d_active, G); });
+    else
+      with_rw(h->rw, [&](auto RW) { enqueue_round_t<r, RW(), RM_LAUNCH>(h, d_active, G); });
+  });
 }
 
 // Acceleration (oracle orc_pgo_accel_pre / _post): gamma' = (1 + sqrt(1 +
@@ -3654,14 +3577,9 @@ double accel_gamma_next(const kmx_pgo* h) {
   return (1.0 + std::sqrt(1.0 + 4.0 * N * N * h->acc_gamma * h->acc_gamma)) / (2.0 * N);
 }
 void launch_accel(kmx_pgo* h, double c, int mode) {
-  const dim3 grid(h->ntiles), blk(BLOCK);
-  switch (h->P.r) {
-#define KMX_ACC(RR) \
-  case RR: hipLaunchKernelGGL(k_accel<RR>, grid, blk, 0, h->stream, h->dv, h->d_accV, h->d_accY, c, mode); break;
-    KMX_ACC(3) KMX_ACC(4) KMX_ACC(5) KMX_ACC(6) KMX_ACC(7)
-    default: hipLaunchKernelGGL(k_accel<8>, grid, blk, 0, h->stream, h->dv, h->d_accV, h->d_accY, c, mode); break;
-#undef KMX_ACC
-  }
+  with_r(h->P.r, [&](auto R) {
+    hipLaunchKernelGGL(k_accel<R()>, dim3(h->ntiles), dim3(BLOCK), 0, h->stream, h->dv, h->d_accV, h->d_accY, c, mode);
+  });
 }
 // Y for the upcoming round (X := Y, owned public rows := Y); once per round.
 void enqueue_accel_pre(kmx_pgo* h) {
@@ -3689,14 +3607,11 @@ void accel_reset(kmx_pgo* h) {
   h->acc_ready = h->acc_started = false;
 }
 
-template <int RW>
-void enqueue_apply_weights_t(kmx_pgo* h) {
-  if (h->mloc > 0)
-    hipLaunchKernelGGL(k_apply_weights<RW>, dim3((h->mloc + 255) / 256), dim3(256), 0, h->stream, h->dv, h->mloc);
-}
 void enqueue_apply_weights(kmx_pgo* h) {
-  if (h->rw == 10) enqueue_apply_weights_t<10>(h);
-  else enqueue_apply_weights_t<16>(h);
+  if (h->mloc > 0)
+    with_rw(h->rw, [&](auto RW) {
+      hipLaunchKernelGGL(k_apply_weights<RW()>, dim3((h->mloc + 255) / 256), dim3(256), 0, h->stream, h->dv, h->mloc);
+    });
   enqueue_precond(h, 0);
 }
 
@@ -3798,7 +3713,7 @@ extern "C" int kmx_pgo_set_tcg_poll(kmx_pgo* h, int mode) {
   KMX_CHECK(mode >= -1 && mode <= 1, KMX_EINVAL, "mode is -1 (adaptive), 0 (blind) or 1 (polled)");
   h->poll = mode != 0;
   h->poll_auto = mode == -1;
-  h->blind_left = 0;
+  h->all.blind_left = 0;
   for (auto& g : h->grp) g.blind_left = 0;
   return KMX_OK;
 }
@@ -4102,6 +4017,9 @@ extern "C" int kmx_pgo_set_graph(kmx_pgo* h, int n_robots, const int32_t* n_pose
       q.t0 = rt0[q.l0];
       q.nt = rt0[q.l1] - rt0[q.l0];
     }
+    // the single chain (its polling state outlives the graph, as the handle's poll mode)
+    h->all.l0 = 0; h->all.l1 = L;
+    h->all.t0 = 0; h->all.nt = h->ntiles;
     // the grouped round's reduction form (kmx_pgo::grm)
     int most = 0;
     for (int l = 0; l < L; ++l) most = std::max(most, rt0[l + 1] - rt0[l]);
@@ -4900,22 +4818,13 @@ extern "C" int kmx_pgo_eval(kmx_pgo* h, int robot, int mode, const double* V, do
   const size_t o = (size_t)h->loff[l] * ps;
   KMX_HIP(hipMemsetAsync(h->d_scratch, 0, sizeof(double) * vec * 2, h->stream));
   if (V) KMX_HIP(hipMemcpyAsync(dV + o, V, sizeof(double) * n * ps, hipMemcpyHostToDevice, h->stream));
-#define KMX_EVAL_LAUNCH(RR)                                                                                      \
-  if (h->rw == 10)                                                                                               \
-    hipLaunchKernelGGL((k_eval<RR, 10>), dim3(h->ntiles), dim3(BLOCK), SmemE<RR>::bytes, h->stream, h->dv, l, mode, \
-                       (const double*)dV, dO);                                                                   \
-  else                                                                                                           \
-    hipLaunchKernelGGL((k_eval<RR, 16>), dim3(h->ntiles), dim3(BLOCK), SmemE<RR>::bytes, h->stream, h->dv, l, mode, \
-                       (const double*)dV, dO);
-  switch (h->P.r) {
-    case 3: KMX_EVAL_LAUNCH(3) break;
-    case 4: KMX_EVAL_LAUNCH(4) break;
-    case 5: KMX_EVAL_LAUNCH(5) break;
-    case 6: KMX_EVAL_LAUNCH(6) break;
-    case 7: KMX_EVAL_LAUNCH(7) break;
-    default: KMX_EVAL_LAUNCH(8) break;
-  }
-#undef KMX_EVAL_LAUNCH
+  with_r(h->P.r, [&](auto R) {
+    with_rw(h->rw, [&](auto RW) {
+      constexpr int r = decltype(R)::value, rw = decltype(RW)::value;
+      hipLaunchKernelGGL((k_eval<r, rw>), dim3(h->ntiles), dim3(BLOCK), SmemE<r>::bytes, h->stream, h->dv, l, mode,
+                         (const double*)dV, dO);
+    });
+  });
   KMX_HIP(hipGetLastError());
   KMX_HIP(hipMemcpyAsync(out, dO + o, sizeof(double) * n * ps, hipMemcpyDeviceToHost, h->stream));
   std::vector<double> part((size_t)h->ntiles * NPART);
