@@ -30,7 +30,6 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
-#include <functional>
 #include <random>
 #include <thread>
 #include <string>
@@ -38,6 +37,7 @@
 #include <vector>
 
 #include "common.h"
+#include "lcd_host.h"
 
 namespace {
 
@@ -502,7 +502,7 @@ __device__ double model_error(const double R[9], const double t[3], const double
 // ------------------------------------------------------------- EPnP ------
 // Port of oracle/lcd_oracle.c orc_epnp for the RANSAC minimal sample (n = 6):
 // same operations in the same order, so models are bit-identical.
-constexpr int PNP_S = 6;
+using kmx::PNP_S;
 
 __device__ void jacobi_sym12(double* A, double* V) {
   constexpr int n = 12;
@@ -1649,10 +1649,8 @@ __device__ __forceinline__ int eigvec_col_real(const double mcol[10], int lane, 
 // instruction advances SG matrices (the per-element operations and their
 // order are the serial code's: bit-identical results). Counters behind the
 // choice: profiles/r03/lcd/.
-#ifndef KMX_SG
-#define KMX_SG 6
-#endif
-constexpr int SG = KMX_SG, GL = SG <= 4 ? 16 : 10;
+using kmx::SG;
+constexpr int GL = SG <= 4 ? 16 : 10;
 static_assert(SG * GL <= RS_BLOCK && GL >= 10, "groups");
 // LDS: the matrices the groups work on and their eigenvalues; rows 0-5 of each
 // action matrix and each null space (needed again by the eigenvector and
@@ -2829,7 +2827,7 @@ struct RsState {  // the serial loop's control between passes
   double best[12];
   int iterations, skipped, best_cnt, have, done, p_next;
 };
-constexpr int SPREAD_PER_NISTER = 2;  // Nister hypotheses per wave (one at a time)
+using kmx::SPREAD_PER_NISTER;
 
 // Candidate c's serial-loop state before its first range, and its wave
 // arrival counter (k_rs_hyps: the last wave of a range replays it).
@@ -3418,44 +3416,40 @@ struct kmx_lcd {
   int table_N = 0;
   int pmax = 0;
   // candidate buffers: LCD_SLOTS slots, used by successive calls in turn, so
-  // a call's kNN2 (on kstream) can run while earlier calls' RANSACs drain;
-  // d_cq .. d_order below point into the current slot
-  int cap = 0, cur = 0;  // cap: the current slot's capacity
-  // Each slot's RANSAC can run on its own stream (slot 0: the handle's
-  // stream, slot s > 0: rsx[s]) with its own work-queue counter and per-wave
-  // scratch, so the next calls' RANSACs take the CUs the previous call's
-  // drain (its last candidates, finishing alone) leaves idle.
-  struct Slot {
-    int *cq = nullptr, *cm = nullptr, *K = nullptr, *hyps = nullptr, *nrec = nullptr, *order = nullptr;
+  // a call's kNN2 (on kstream) can run while earlier calls' RANSACs drain.
+  // A slot owns its buffers; slot[cur] is the current call's.
+  struct SlotBuffers {
+    int *cq = nullptr, *cm = nullptr, *K = nullptr;
+    int *hyps = nullptr, *nrec = nullptr;  // ordered sampler: the passes each problem drew, recovery sizes
+    int* order = nullptr;                  // k_order's queue order (KMX_LCD_ORDER)
     int2* pairs = nullptr;
     kmx_lcd_result* res = nullptr;
     unsigned char* mask = nullptr;
-    double* prior = nullptr;
-    double* fbuf = nullptr;
-    int* next = nullptr;
-    int cap = 0;  // candidates the slot's buffers hold (0: not allocated yet)
+    double* prior = nullptr;  // T_prior rows (kmx_lcd_verify_matches)
+    double* fbuf = nullptr;   // [waves][6 N + STASH] compact match bearings + Stewenius stash, per k_ransac_coop wave
+    int* next = nullptr;      // k_ransac_coop's work-queue counter
+    int cap = 0;              // candidates the slot's buffers hold (0: not allocated yet)
+  };
+  // Each slot's RANSAC can run on its own stream (slot 0: the handle's
+  // stream, slot s > 0: its rsx) with its own work-queue counter and per-wave
+  // scratch, so the next calls' RANSACs take the CUs the previous call's
+  // drain (its last candidates, finishing alone) leaves idle. The stream and
+  // the events live as long as the handle; the buffers come and go (slot_free).
+  struct Slot : SlotBuffers {
+    hipStream_t rsx = nullptr;                    // the slot's RANSAC stream (slots > 0)
+    hipEvent_t ev_knn = nullptr, ev_rs = nullptr;  // its kNN2 is done; its last work is done
+    bool ev_rs_set = false;
   } slot[LCD_SLOTS];
-  hipStream_t rsx[LCD_SLOTS] = {};  // rsx[s]: slot s's RANSAC stream (s > 0)
-  bool rs_conc = true;              // KMX_LCD_RSX=0: every slot on the handle's stream (A/B switch)
-  bool rs_small = false;            // this call runs its slots' RANSACs concurrently (the size cut)
-  bool rs_on = false;               // this call's slot runs on rsx[cur]
+  int cur = 0;
+  bool rs_conc = true;    // KMX_LCD_RSX=0: every slot on the handle's stream (A/B switch)
+  bool rs_small = false;  // this call runs its slots' RANSACs concurrently (the size cut)
+  bool rs_on = false;     // this call's slot runs on its rsx
   int cus = 0;
   hipStream_t kstream = nullptr;  // kNN2 of kmx_lcd_verify / _async
-  hipEvent_t ev_knn[LCD_SLOTS] = {}, ev_rs[LCD_SLOTS] = {};
-  bool ev_rs_set[LCD_SLOTS] = {};
-  int *d_cq = nullptr, *d_cm = nullptr, *d_K = nullptr;
-  int2* d_pairs = nullptr;
-  kmx_lcd_result* d_res = nullptr;
-  unsigned char* d_mask = nullptr;
-  double* d_fbuf = nullptr;  // [slots][6 N + STASH] compact match bearings + Stewenius stash, per k_ransac_coop wave
-  int* d_next = nullptr;     // k_ransac_coop's work-queue counter
-  double* d_prior = nullptr;  // the current slot's T_prior rows (kmx_lcd_verify_matches)
   // ordered sampler (rng_stream 1): the verification thread's engine, one
-  // candidate's sample row, the passes each problem drew, recovery sizes
+  // candidate's sample row
   std::mt19937 stream_rng;
   short* d_row = nullptr;
-  int *d_hyps = nullptr, *d_nrec = nullptr;
-  int* d_order = nullptr;  // k_order's queue order (KMX_LCD_ORDER)
   // spread form (synchronous calls of <= spread_max candidates; lcd.hip k_rs_*)
   int spread_max = 8;
   int spread_cap = 0;
@@ -3508,14 +3502,24 @@ struct kmx_lcd {
 
 namespace {
 
-void sync_rsx(kmx_lcd* h) {
-  for (hipStream_t x : h->rsx)
-    if (x) (void)hipStreamSynchronize(x);
+using Slot = kmx_lcd::Slot;
+inline Slot& cur_slot(kmx_lcd* h) { return h->slot[h->cur]; }
+inline const Slot& cur_slot(const kmx_lcd* h) { return h->slot[h->cur]; }
+
+// Wait for everything the handle has in flight: its stream, the kNN2 stream
+// and every slot's RANSAC stream. The first error, all streams waited for.
+hipError_t sync_all(kmx_lcd* h) {
+  hipError_t first = hipStreamSynchronize(h->stream);
+  auto wait = [&](hipStream_t x) {
+    const hipError_t e = x ? hipStreamSynchronize(x) : hipSuccess;
+    if (first == hipSuccess) first = e;
+  };
+  wait(h->kstream);
+  for (const Slot& sl : h->slot) wait(sl.rsx);
+  return first;
 }
 void lcd_free_frames(kmx_lcd* h) {
-  if (h->stream) (void)hipStreamSynchronize(h->stream);  // a verification in flight may read the pool
-  sync_rsx(h);
-  if (h->kstream) (void)hipStreamSynchronize(h->kstream);
+  (void)sync_all(h);  // a verification in flight may read the pool
   void* p[] = {h->d_desc, h->d_bear, h->d_pts, h->d_nfeat};
   for (void* x : p)
     if (x) (void)hipFree(x);
@@ -3529,23 +3533,18 @@ void lcd_free_tables(kmx_lcd* h) {
   h->d_table = h->d_table_rec = nullptr;
   h->table_N = 0;
 }
+// The slot's buffers (the caller has waited for the work that uses them);
+// its stream and events stay.
+void slot_free(Slot& sl) {
+  void* p[] = {sl.cq, sl.cm, sl.K, sl.hyps, sl.nrec, sl.order, sl.pairs, sl.res, sl.mask, sl.prior, sl.fbuf, sl.next};
+  for (void* x : p)
+    if (x) (void)hipFree(x);
+  static_cast<kmx_lcd::SlotBuffers&>(sl) = kmx_lcd::SlotBuffers{};
+  sl.ev_rs_set = false;
+}
 void lcd_free_cand(kmx_lcd* h) {
-  if (h->stream) (void)hipStreamSynchronize(h->stream);  // in-flight calls may still use the buffers
-  sync_rsx(h);
-  if (h->kstream) (void)hipStreamSynchronize(h->kstream);
-  for (auto& sl : h->slot) {
-    void* p[] = {sl.cq, sl.cm, sl.K, sl.hyps, sl.nrec, sl.order, sl.pairs, sl.res, sl.mask, sl.prior, sl.fbuf, sl.next};
-    for (void* x : p)
-      if (x) (void)hipFree(x);
-    sl = kmx_lcd::Slot{};
-  }
-  h->d_cq = h->d_cm = h->d_K = nullptr; h->d_pairs = nullptr; h->d_res = nullptr; h->d_mask = nullptr;
-  h->d_fbuf = nullptr;
-  h->d_next = h->d_hyps = h->d_nrec = nullptr;
-  h->d_prior = nullptr;
-  h->d_order = nullptr;
-  for (bool& e : h->ev_rs_set) e = false;
-  h->cap = 0;
+  (void)sync_all(h);  // in-flight calls may still use the buffers
+  for (Slot& sl : h->slot) slot_free(sl);
   void* q[] = {h->d_st, h->d_hout, h->d_sfbuf, h->d_more, h->d_kqb, h->d_kcnt, h->d_hcnt};
   for (void* x : q)
     if (x) (void)hipFree(x);
@@ -3557,14 +3556,16 @@ void lcd_free_cand(kmx_lcd* h) {
 }
 // Pinned host + device staging of at least `bytes` (grow-only; the callers
 // are synchronous, so the previous call's copies have completed).
-int io_reserve(kmx_lcd* h, size_t bytes) {
-  if (bytes <= h->io_cap) return 0;
-  if (h->stream) KMX_HIP(hipStreamSynchronize(h->stream));
-  sync_rsx(h);
+void io_free(kmx_lcd* h) {
   if (h->h_io) (void)hipHostFree(h->h_io);
   if (h->d_io) (void)hipFree(h->d_io);
   h->h_io = nullptr; h->d_io = nullptr; h->z_io = nullptr;
   h->io_cap = 0;
+}
+int io_reserve(kmx_lcd* h, size_t bytes) {
+  if (bytes <= h->io_cap) return 0;
+  KMX_HIP(sync_all(h));
+  io_free(h);
   const size_t cap = std::max<size_t>(bytes, 256 * 1024);
   KMX_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->h_io), cap, hipHostMallocMapped | hipHostMallocCoherent));
   KMX_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->z_io), h->h_io, 0));
@@ -3608,19 +3609,12 @@ int wait_done(kmx_lcd* h, hipStream_t st, unsigned seq) {
   }
   return 0;
 }
-inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
-// The next call's slot: its buffers become d_cq .. d_order.
-void use_next_slot(kmx_lcd* h) {
-  h->cur = (h->cur + 1) % LCD_SLOTS;
-  const kmx_lcd::Slot& sl = h->slot[h->cur];
-  h->d_cq = sl.cq; h->d_cm = sl.cm; h->d_K = sl.K; h->d_hyps = sl.hyps; h->d_nrec = sl.nrec; h->d_order = sl.order;
-  h->d_pairs = sl.pairs; h->d_res = sl.res; h->d_mask = sl.mask; h->d_prior = sl.prior;
-  h->d_fbuf = sl.fbuf; h->d_next = sl.next;
-  h->cap = sl.cap;
-}
+using kmx::al16;
+// The next call's slot.
+void use_next_slot(kmx_lcd* h) { h->cur = (h->cur + 1) % LCD_SLOTS; }
 // The current slot's RANSAC stream: everything a call does on its slot's
 // buffers after the kNN2 runs there.
-// Slots s > 0 go on rsx[s] for calls of fewer than 96 candidates per CU (8
+// Slots s > 0 go on their rsx for calls of fewer than 96 candidates per CU (8
 // per resident RANSAC wave): there the previous call's drain is a large part
 // of a call and the kNN2 alone does not fill it (2k candidates, two slots:
 // 6.5 -> 3.8 ms per back-to-back call, 20k: 16.9 -> 15.1 ms); at configs[2]'s
@@ -3628,22 +3622,19 @@ void use_next_slot(kmx_lcd* h) {
 // (profiles/r04/lcd/two_stream). A larger call's kNN2 also waits for the
 // RANSAC two calls back, as with two slots: run further ahead, the kNN2s took
 // CUs from the RANSAC (four slots without it: 50k steps up to 3 % slower).
-hipStream_t rs_stream(const kmx_lcd* h) { return h->rs_on ? h->rsx[h->cur] : h->stream; }
+hipStream_t rs_stream(const kmx_lcd* h) { return h->rs_on ? cur_slot(h).rsx : h->stream; }
 // The current slot's last work may be on another stream (the choice is per
 // call): calls that write the slot's buffers from rs_stream wait for it.
 int rs_wait_slot(kmx_lcd* h) {
-  if (h->ev_rs_set[h->cur]) KMX_HIP(hipStreamWaitEvent(rs_stream(h), h->ev_rs[h->cur], 0));
+  if (cur_slot(h).ev_rs_set) KMX_HIP(hipStreamWaitEvent(rs_stream(h), cur_slot(h).ev_rs, 0));
   return 0;
 }
-void lcd_free_pairs(kmx_lcd* h) {
-  void* p[] = {h->d_row};
-  for (void* x : p)
-    if (x) (void)hipFree(x);
+// The staging areas of the small calls and the frame uploads, the completion
+// word and the ordered sampler's row.
+void lcd_free_staging(kmx_lcd* h) {
+  if (h->d_row) (void)hipFree(h->d_row);
   h->d_row = nullptr;
-  if (h->h_io) (void)hipHostFree(h->h_io);
-  if (h->d_io) (void)hipFree(h->d_io);
-  h->h_io = nullptr; h->d_io = nullptr; h->z_io = nullptr;
-  h->io_cap = 0;
+  io_free(h);
   if (h->h_fst) (void)hipHostFree(h->h_fst);
   h->h_fst = h->z_fst = nullptr;
   h->fst_cap = 0;
@@ -3651,57 +3642,12 @@ void lcd_free_pairs(kmx_lcd* h) {
   h->h_done = h->z_done = nullptr;
 }
 
-// One pass of opengv's drawIndexSample: S swaps of the persistent shuffle over
-// the problem's K indices, each by std::uniform_int_distribution<int>(0,
-// INT_MAX) over std::mt19937 (GCC-9 rejection or GCC-11 x >> 1).
-inline int sampler_draw(std::mt19937& rng, int variant) {
-  uint32_t x;
-  if (variant == KMX_RNG_GCC11) {
-    x = (uint32_t)rng() >> 1;
-  } else {
-    do x = (uint32_t)rng();
-    while (x >= 0x80000000u);
-  }
-  return (int)x;
-}
-void sample_row(std::mt19937& rng, int variant, int K, int pmax, int S, short* out) {
-  std::vector<int> sh(K);
-  for (int i = 0; i < K; ++i) sh[i] = i;
-  for (int p = 0; p < pmax; ++p) {
-    for (int i = 0; i < S; ++i) {
-      const int j = i + (int)((size_t)sampler_draw(rng, variant) % (size_t)(K - i));
-      std::swap(sh[i], sh[j]);
-    }
-    for (int i = 0; i < S; ++i) out[(size_t)p * S + i] = (short)sh[i];
-  }
-}
-
-// opengv sampler table: for every K in [S, N], the S indices drawn by each of
-// the first pmax passes (std::mt19937 seeded per problem). Rows are
-// independent, so they are built on a few host threads.
-void build_table(const kmx_lcd_params& P, int N, int pmax, std::vector<short>& tab, int S = 5) {
-  const int rows = std::max(N - S + 1, 1);
-  tab.assign((size_t)rows * pmax * S, 0);
-  const int nt = std::max(1, std::min(8, rows / 32));
-  std::vector<std::thread> th;
-  for (int t = 0; t < nt; ++t)
-    th.emplace_back([&, t] {
-      for (int K = S + t; K <= N; K += nt) {
-        std::mt19937 rng(P.ransac_seed);
-        sample_row(rng, P.rng_variant, K, pmax, S, tab.data() + (size_t)(K - S) * pmax * S);
-      }
-    });
-  for (auto& x : th) x.join();
-}
-
-bool rec_sampled(const kmx_lcd_params& P) { return P.pose_recovery_type == 1 || !P.use_1point_3d3d; }
-int rec_S(const kmx_lcd_params& P) { return P.pose_recovery_type == 1 ? PNP_S : 3; }
+using kmx::build_table, kmx::rec_S, kmx::rec_sampled, kmx::sample_row, kmx::sampler_draw;  // lcd_host.h
 
 // Sampler tables for the pool's N (kept across set_frames / add_frames with the
 // same N). The ordered sampler draws its rows per candidate instead.
 int ensure_tables(kmx_lcd* h) {
-  // every pass the serial loop can reach: (max_iter + 1) iterations + 10 * max_iter skips
-  h->pmax = h->P.ransac_max_iterations + 1 + 10 * h->P.ransac_max_iterations;
+  h->pmax = kmx::lcd_pmax(h->P);
   if (h->P.rng_stream) {
     if (!h->d_row) KMX_HIP(hipMalloc(&h->d_row, sizeof(short) * (size_t)h->pmax * PNP_S));
     return 0;
@@ -3724,8 +3670,8 @@ int ensure_tables(kmx_lcd* h) {
 // True while an earlier call may still run on some slot (an async call's
 // RANSAC or kNN2 not yet complete).
 bool slots_busy(kmx_lcd* h) {
-  for (int s = 0; s < LCD_SLOTS; ++s)
-    if (h->ev_rs_set[s] && hipEventQuery(h->ev_rs[s]) != hipSuccess) return true;
+  for (const Slot& sl : h->slot)
+    if (sl.ev_rs_set && hipEventQuery(sl.ev_rs) != hipSuccess) return true;
   return h->kstream && hipStreamQuery(h->kstream) != hipSuccess;
 }
 // The call's slot, with buffers for n candidates. Slots are allocated (and
@@ -3735,17 +3681,10 @@ bool slots_busy(kmx_lcd* h) {
 int ensure_cap(kmx_lcd* h, int n, bool async) {
   if (!async && !slots_busy(h)) h->cur = LCD_SLOTS - 1;  // use_next_slot -> slot 0
   use_next_slot(h);
-  kmx_lcd::Slot& sl = h->slot[h->cur];
+  Slot& sl = cur_slot(h);
   if (n > sl.cap) {
-    // the slot's last call may still be in flight on any stream
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    sync_rsx(h);
-    if (h->kstream) (void)hipStreamSynchronize(h->kstream);
-    void* p[] = {sl.cq, sl.cm, sl.K, sl.hyps, sl.nrec, sl.order, sl.pairs, sl.res, sl.mask, sl.prior, sl.fbuf, sl.next};
-    for (void* x : p)
-      if (x) (void)hipFree(x);
-    sl = kmx_lcd::Slot{};
-    h->ev_rs_set[h->cur] = false;
+    KMX_HIP(sync_all(h));  // the slot's last call may still be in flight on any stream
+    slot_free(sl);
     const int cap = std::max(n, 1024);
     bool ok =
            hipMalloc(&sl.fbuf, sizeof(double) * (6 * (size_t)h->N + STASH) * std::min(cap, RS_MAX_SLOTS)) ==
@@ -3764,8 +3703,6 @@ int ensure_cap(kmx_lcd* h, int n, bool async) {
       return kmx::fail(KMX_ENOMEM, "candidate buffers");
     }
     sl.cap = cap;
-    h->cur = (h->cur + LCD_SLOTS - 1) % LCD_SLOTS;
-    use_next_slot(h);  // re-point d_cq .. d_order at the new buffers
   }
   if (!h->cus) KMX_HIP(hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, h->device));
   h->rs_small = h->rs_conc && (int64_t)n < 96LL * h->cus;
@@ -3813,7 +3750,7 @@ RsParams rs_params(const kmx_lcd* h, int stages) {
   rp.algo = h->P.algorithm_2d2d;
   rp.refine = h->P.refine_pose && h->P.pose_recovery_type == 0 ? 1 : 0;
   rp.stages = stages;
-  rp.prior = h->d_prior;
+  rp.prior = cur_slot(h).prior;
   return rp;
 }
 PnpParams pnp_params(const kmx_lcd* h, int stages) {
@@ -3868,12 +3805,11 @@ int launch_ransac(kmx_lcd* h, int n, const RsParams& rp, const short* table, int
   auto kc = stew ? k_ransac_coop<4, true> : k_ransac_coop<4, false>;
   if (rp.pmax < 0) kc = k_ransac_coop<3, false>;  // never: keeps the Nister 3-wave form compiled
   // one wave per resident slot (<= RS_MAX_SLOTS: the scratch is sized for it)
-  int per_cu = 0, dev = 0, cus = 0;
+  int per_cu = 0;
   KMX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kc, RS_BLOCK, 0));
-  KMX_HIP(hipGetDevice(&dev));
-  KMX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const int slots = std::max(1, std::min({n, std::max(per_cu, 1) * cus, RS_MAX_SLOTS, h->cap}));
-  KMX_HIP(hipMemsetAsync(h->d_next, 0, sizeof(int), rs_stream(h)));
+  const Slot& sl = cur_slot(h);
+  const int waves = std::max(1, std::min({n, std::max(per_cu, 1) * h->cus, RS_MAX_SLOTS, sl.cap}));  // (ensure_cap set cus)
+  KMX_HIP(hipMemsetAsync(sl.next, 0, sizeof(int), rs_stream(h)));
   RsParams p = rp;
   if (p.prior) p.prior += (size_t)c0 * 12;
   if (p.hyps) p.hyps += c0;
@@ -3882,13 +3818,13 @@ int launch_ransac(kmx_lcd* h, int n, const RsParams& rp, const short* table, int
   const bool longest_first = ov && std::atoi(ov) == 1;
   const int* order = nullptr;
   if (longest_first && n > 1 && c0 == 0) {
-    hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, rs_stream(h), (const int*)h->d_K, n, h->N, h->d_order);
-    order = h->d_order;
+    hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, rs_stream(h), (const int*)sl.K, n, h->N, sl.order);
+    order = sl.order;
   }
-  hipLaunchKernelGGL(kc, dim3(slots), dim3(RS_BLOCK), 0, rs_stream(h), (const double*)h->d_bear,
-                     (const double*)h->d_pts, h->N, (const int*)h->d_cq + c0, (const int*)h->d_cm + c0,
-                     (const int2*)h->d_pairs + (size_t)c0 * h->N, (const int*)h->d_K + c0, table, p, h->d_res + c0,
-                     masks ? h->d_mask + (size_t)c0 * h->N : nullptr, h->d_fbuf, n, h->d_next, order);
+  hipLaunchKernelGGL(kc, dim3(waves), dim3(RS_BLOCK), 0, rs_stream(h), (const double*)h->d_bear,
+                     (const double*)h->d_pts, h->N, (const int*)sl.cq + c0, (const int*)sl.cm + c0,
+                     (const int2*)sl.pairs + (size_t)c0 * h->N, (const int*)sl.K + c0, table, p, sl.res + c0,
+                     masks ? sl.mask + (size_t)c0 * h->N : nullptr, sl.fbuf, n, sl.next, order);
   return 0;
 }
 int launch_recover(kmx_lcd* h, int n, const PnpParams& pp, const short* table, int c0) {
@@ -3896,10 +3832,11 @@ int launch_recover(kmx_lcd* h, int n, const PnpParams& pp, const short* table, i
   const size_t smem = sizeof(double) * (6 * (size_t)h->N + 64 * 12 + 12) + sizeof(int) * (64 + 64 + 4 + (size_t)h->N);
   PnpParams p = pp;
   if (p.hyps) p.hyps += c0;
+  const Slot& sl = cur_slot(h);
   hipLaunchKernelGGL(pnp ? k_recover<true> : k_recover<false>, dim3(n), dim3(RS_BLOCK), smem, rs_stream(h),
-                     (const double*)h->d_bear, (const double*)h->d_pts, h->N, (const int*)h->d_cq + c0,
-                     (const int*)h->d_cm + c0, (const int2*)h->d_pairs + (size_t)c0 * h->N, (const int*)h->d_K + c0,
-                     table, p, h->d_res + c0, h->d_mask + (size_t)c0 * h->N);
+                     (const double*)h->d_bear, (const double*)h->d_pts, h->N, (const int*)sl.cq + c0,
+                     (const int*)sl.cm + c0, (const int2*)sl.pairs + (size_t)c0 * h->N, (const int*)sl.K + c0,
+                     table, p, sl.res + c0, sl.mask + (size_t)c0 * h->N);
   return 0;
 }
 
@@ -3911,16 +3848,17 @@ int launch_recover(kmx_lcd* h, int n, const PnpParams& pp, const short* table, i
 // problem's sample row from a copy of the engine, the kernel runs that one
 // problem, and the engine then advances by the passes the serial loop drew.
 int verify_ordered(kmx_lcd* h, int n, int stages, bool masks) {
+  const Slot& sl = cur_slot(h);
   std::vector<int> K(n);
-  KMX_HIP(hipMemcpyAsync(K.data(), h->d_K, sizeof(int) * n, hipMemcpyDeviceToHost, rs_stream(h)));
+  KMX_HIP(hipMemcpyAsync(K.data(), sl.K, sizeof(int) * n, hipMemcpyDeviceToHost, rs_stream(h)));
   KMX_HIP(hipStreamSynchronize(rs_stream(h)));
   RsParams rp = rs_params(h, stages);
   rp.tab_fixed = 1;
-  rp.hyps = h->d_hyps;
-  rp.nrec = rec_sampled(h->P) ? h->d_nrec : nullptr;
+  rp.hyps = sl.hyps;
+  rp.nrec = rec_sampled(h->P) ? sl.nrec : nullptr;
   PnpParams pp = pnp_params(h, stages);
   pp.tab_fixed = 1;
-  pp.hyps = h->d_hyps;
+  pp.hyps = sl.hyps;
   const int v = h->P.rng_variant;
   std::vector<short> row((size_t)h->pmax * PNP_S);
   auto advance = [&](int passes, int S) {
@@ -3936,13 +3874,13 @@ int verify_ordered(kmx_lcd* h, int n, int stages, bool masks) {
     }
     if (int rc = launch_ransac(h, 1, rp, h->d_row, c, masks || rp.pnp)) return rc;
     int got[2] = {0, 0};
-    KMX_HIP(hipMemcpyAsync(&got[0], h->d_hyps + c, sizeof(int), hipMemcpyDeviceToHost, rs_stream(h)));
-    if (rp.nrec) KMX_HIP(hipMemcpyAsync(&got[1], h->d_nrec + c, sizeof(int), hipMemcpyDeviceToHost, rs_stream(h)));
+    KMX_HIP(hipMemcpyAsync(&got[0], sl.hyps + c, sizeof(int), hipMemcpyDeviceToHost, rs_stream(h)));
+    if (rp.nrec) KMX_HIP(hipMemcpyAsync(&got[1], sl.nrec + c, sizeof(int), hipMemcpyDeviceToHost, rs_stream(h)));
     KMX_HIP(hipStreamSynchronize(rs_stream(h)));
     if (st2d && K[c] >= 5) advance(got[0], 5);
     if (!rp.pnp || !(stages & KMX_LCD_STAGE_RECOVER)) continue;
     kmx_lcd_result r{};
-    KMX_HIP(hipMemcpyAsync(&r, h->d_res + c, sizeof(r), hipMemcpyDeviceToHost, rs_stream(h)));
+    KMX_HIP(hipMemcpyAsync(&r, sl.res + c, sizeof(r), hipMemcpyDeviceToHost, rs_stream(h)));
     KMX_HIP(hipStreamSynchronize(rs_stream(h)));
     if (r.mono_inliers < pp.min2d) continue;
     const int S = rec_S(h->P), n2 = got[1];
@@ -3954,7 +3892,7 @@ int verify_ordered(kmx_lcd* h, int n, int stages, bool masks) {
     }
     if (int rc = launch_recover(h, 1, pp, h->d_row, c)) return rc;
     int hy = 0;
-    KMX_HIP(hipMemcpyAsync(&hy, h->d_hyps + c, sizeof(int), hipMemcpyDeviceToHost, rs_stream(h)));
+    KMX_HIP(hipMemcpyAsync(&hy, sl.hyps + c, sizeof(int), hipMemcpyDeviceToHost, rs_stream(h)));
     KMX_HIP(hipStreamSynchronize(rs_stream(h)));
     if (n2 >= S) advance(hy, S);
   }
@@ -3964,16 +3902,39 @@ int verify_ordered(kmx_lcd* h, int n, int stages, bool masks) {
 // The spread form (see k_rs_hyps): hypothesis ranges of growing size on many
 // waves, the serial control replayed after each, until every candidate's loop
 // has stopped; then the candidates' results. Synchronous (the host reads
-// whether a candidate needs another range). With `copy_out` (the caller's
-// result copies) the finish is enqueued speculatively behind the first
-// range, gated on the device by the range's `more` word, with the copies
-// after it: a call whose candidates all stop inside the first range (a true
-// loop closure: ~30 of 66 or 510 hypotheses) then costs one host round trip
-// instead of two, and *copied says the results are on their way.
-constexpr int SPREAD_WAVES = 1024;  // waves of one k_rs_hyps launch at most
-// res_dst / mask_dst (zero-copy callers): where k_rs_finish writes the results
-// and masks (host-mapped memory) in place of the slot's device buffers; the
-// speculative finish then also writes the range's `more` word to h_more.
+// whether a candidate needs another range). For a small call (SmallCall) the
+// finish is enqueued speculatively behind the first range, gated on the
+// device by the range's `more` word, with the result copies after it: a call
+// whose candidates all stop inside the first range (a true loop closure: ~30
+// of 66 or 510 hypotheses) then costs one host round trip instead of two.
+using kmx::SPREAD_WAVES;
+// What kmx_lcd_verify_matches tells enqueue_ransac / ransac_spread about its
+// call (synchronous, its staging block in place), and what it hears back.
+struct SmallCall {
+  // zero-copy (spread form without PnP): k_rs_finish writes the results and
+  // masks here (mapped staging) in place of the slot's device buffers; the
+  // speculative finish then also writes the range's `more` word to h_more
+  kmx_lcd_result* res_dst = nullptr;
+  unsigned char* mask_dst = nullptr;
+  bool inited = false;  // k_scatter_pairs initialised the spread state (no k_rs_init launch)
+  size_t o_res = 0, o_mask = 0;  // copy_results' staging offsets (o_mask 0: no masks)
+  // on return
+  bool copied = false;  // the results are on their way (copied, or written in place)
+  unsigned fseq = 0;    // one zero-copy candidate: the sequence its last kernel stores to the
+                        // completion word, for wait_done (0: synchronise the stream)
+};
+// The slot's results (and masks) of n candidates to the pinned staging block.
+int copy_results(kmx_lcd* h, const Slot& sl, int n, size_t o_res, size_t o_mask) {
+  KMX_HIP(hipMemcpyAsync(h->h_io + o_res, sl.res, sizeof(kmx_lcd_result) * n, hipMemcpyDeviceToHost, rs_stream(h)));
+  if (o_mask)
+    KMX_HIP(hipMemcpyAsync(h->h_io + o_mask, sl.mask, (size_t)n * h->N, hipMemcpyDeviceToHost, rs_stream(h)));
+  return 0;
+}
+// The one place that decides the spread form: a synchronous call of at most
+// spread_max candidates with the table sampler.
+bool takes_spread(const kmx_lcd* h, int n, bool sync_call) {
+  return sync_call && !h->P.rng_stream && n > 0 && n <= h->spread_max;
+}
 // The spread form's buffers for n candidates (grow-only).
 int spread_alloc(kmx_lcd* h, int n) {
   hipStream_t st = rs_stream(h);
@@ -4006,64 +3967,46 @@ int spread_alloc(kmx_lcd* h, int n) {
   }
   return 0;
 }
-// inited: the caller's k_scatter_pairs already initialised the state (no k_rs_init launch)
-// fseq (a zero-copy call of one candidate): the sequence its last kernel
-// stores to the completion word, for the caller's wait_done (0: none).
-int ransac_spread(kmx_lcd* h, int n, int stages, bool want_masks, const std::function<int()>* copy_out = nullptr,
-                  bool* copied = nullptr, kmx_lcd_result* res_dst = nullptr, unsigned char* mask_dst = nullptr,
-                  bool inited = false, unsigned* fseq = nullptr) {
+int ransac_spread(kmx_lcd* h, int n, int stages, bool want_masks, SmallCall* sc) {
   const RsParams rp = rs_params(h, stages);
   const bool masks = want_masks || rp.pnp;
   hipStream_t st = rs_stream(h);
+  const Slot& sl = cur_slot(h);
   if (int rc = spread_alloc(h, n)) return rc;
   const bool stew = rp.algo == KMX_ALGO_STEWENIUS;
-  const int per_max = stew ? SG : SPREAD_PER_NISTER;
-  if (!inited)
+  if (!(sc && sc->inited))
     hipLaunchKernelGGL(k_rs_init, dim3((std::max(n, h->more_cap) + 63) / 64), dim3(64), 0, st, h->d_st, h->d_hcnt, n,
                        stages, h->d_more, h->more_cap);
-  int pa = 0;
-  // the first range: a true loop closure's loop (~30 iterations) in one pass;
-  // where the launch has the waves for it (one or two candidates), a whole
-  // 500-iteration loop (510) at once — one hypothesis per wave costs the
-  // same latency, and a look-alike then needs one range, not two
-  int range = (int64_t)n * 510 <= SPREAD_WAVES ? 510 : 66;
   const size_t tail_bytes = sizeof(double) * tail_lds_doubles(h->N);
   if (tail_bytes > 65536 - 16384)  // (max_feats near 1024: 75 KB, + 8.8 KB static: workspace, counts)
     KMX_HIP(hipFuncSetAttribute((const void*)k_rs_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tail_bytes));
-  const bool zc = res_dst != nullptr;
-  unsigned* z_more = zc ? h->z_more : nullptr;
-  if (fseq) *fseq = 0;
-  const bool one = zc && n == 1 && fseq;  // a one-candidate call: its finishes store the completion word
+  const bool zc = sc && sc->res_dst;
+  const bool one = zc && n == 1;  // a one-candidate call: its finishes store the completion word
   auto finish = [&](const unsigned* skip, unsigned* seq_out) {
     unsigned seq = 0;
     unsigned* done = one && seq_out ? next_done(h, &seq) : nullptr;
     if (seq_out) *seq_out = done ? seq : 0;
     hipLaunchKernelGGL(k_rs_finish, dim3(n), dim3(RS_BLOCK * RS_FIN), tail_bytes, st,
                        (const double*)h->d_bear, (const double*)h->d_pts,
-                       h->N, (const int*)h->d_cq, (const int*)h->d_cm, (const int2*)h->d_pairs, (const int*)h->d_K, rp,
-                       (const RsState*)h->d_st, zc ? res_dst : h->d_res,
-                       masks ? (zc && mask_dst ? mask_dst : h->d_mask) : nullptr, h->d_sfbuf, skip,
-                       skip && zc ? z_more : nullptr, done, seq);
+                       h->N, (const int*)sl.cq, (const int*)sl.cm, (const int2*)sl.pairs, (const int*)sl.K, rp,
+                       (const RsState*)h->d_st, zc ? sc->res_dst : sl.res,
+                       masks ? (zc && sc->mask_dst ? sc->mask_dst : sl.mask) : nullptr, h->d_sfbuf, skip,
+                       skip && zc ? h->z_more : nullptr, done, seq);
   };
-  const bool spec = copy_out && copied && !rp.pnp;
-  if (copied) *copied = false;
+  const bool spec = sc && !rp.pnp;
+  int pa = 0, range = kmx::spread_first_range(n);
   for (int it = 0; pa < h->pmax && (stages & KMX_LCD_STAGE_2D2D); ++it) {  // (recovery alone: no hypotheses)
-    // hypotheses per wave: as few as the launch's waves allow (one wave
-    // works through its hypotheses one after another; the batch of SG
-    // Stewenius hypotheses per wave only pays where waves are short)
-    const int per = std::max(1, std::min(per_max, (int)(((int64_t)n * range + SPREAD_WAVES - 1) / SPREAD_WAVES)));
-    int G = (range + per - 1) / per;
-    G = std::max(1, std::min(G, SPREAD_WAVES / n));
-    const int pb = std::min(pa + G * per, h->pmax);
-    hipLaunchKernelGGL(stew ? k_rs_hyps<true> : k_rs_hyps<false>, dim3(n * G), dim3(RS_BLOCK), 0, st,
-                       (const double*)h->d_bear, h->N, (const int*)h->d_cq, (const int*)h->d_cm,
-                       (const int2*)h->d_pairs, (const int*)h->d_K, (const short*)h->d_table, rp,
-                       h->d_st, h->d_hout, pa, pb, G, per, h->d_sfbuf, h->d_hcnt, h->d_more + it);
+    const kmx::SpreadStep s = kmx::spread_step(n, pa, range, kmx::spread_per_max(rp.algo), h->pmax);
+    hipLaunchKernelGGL(stew ? k_rs_hyps<true> : k_rs_hyps<false>, dim3(n * s.G), dim3(RS_BLOCK), 0, st,
+                       (const double*)h->d_bear, h->N, (const int*)sl.cq, (const int*)sl.cm,
+                       (const int2*)sl.pairs, (const int*)sl.K, (const short*)h->d_table, rp,
+                       h->d_st, h->d_hout, pa, s.pb, s.G, s.per, h->d_sfbuf, h->d_hcnt, h->d_more + it);
     const bool zc_more = spec && it == 0 && zc;  // the speculative finish writes the word itself
     unsigned sseq = 0;
     if (spec && it == 0) {
       finish(h->d_more, zc_more ? &sseq : nullptr);
-      if (int rc = (*copy_out)()) return rc;
+      if (!zc)
+        if (int rc = copy_results(h, sl, n, sc->o_res, sc->o_mask)) return rc;
     }
     if (!zc_more) KMX_HIP(hipMemcpyAsync(h->h_more, h->d_more + it, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     if (sseq) {  // the finish stored the more word before its completion word
@@ -4073,35 +4016,30 @@ int ransac_spread(kmx_lcd* h, int n, int stages, bool want_masks, const std::fun
     }
     if (!*h->h_more) {
       if (spec && it == 0) {
-        *copied = true;
-        if (fseq) *fseq = sseq;
+        sc->copied = true;
+        sc->fseq = sseq;
         KMX_HIP(hipGetLastError());
         return 0;
       }
       break;
     }
-    pa = pb;
-    range = pa < 510 ? 510 - pa : 1500;  // then the rest of a 500-iteration loop, then its skips
+    pa = s.pb;
+    range = kmx::spread_next_range(pa);
   }
-  finish(nullptr, fseq);
+  finish(nullptr, sc ? &sc->fseq : nullptr);
   if (rp.pnp && (stages & KMX_LCD_STAGE_RECOVER))
     if (int rc = launch_recover(h, n, pnp_params(h, stages), h->d_table_rec, 0)) return rc;
   KMX_HIP(hipGetLastError());
   return 0;
 }
 
-// Everything after the pair rows d_pairs / d_K exist: RANSAC, then recovery.
-// sync_ok: the caller synchronises on the results (kmx_lcd_verify,
-// kmx_lcd_verify_matches), so a small call may take the spread form.
-int enqueue_ransac(kmx_lcd* h, int n, int stages, bool want_masks, bool sync_ok = false,
-                   const std::function<int()>* copy_out = nullptr, bool* copied = nullptr,
-                   kmx_lcd_result* res_dst = nullptr, unsigned char* mask_dst = nullptr, bool inited = false,
-                   unsigned* fseq = nullptr) {
-  if (copied) *copied = false;
-  if (fseq) *fseq = 0;
+// Everything after the slot's pair rows (pairs / K) exist: RANSAC, then
+// recovery. sync_call: the caller synchronises on the results (kmx_lcd_verify,
+// kmx_lcd_verify_matches), so a small call takes the spread form; sc: the
+// latter's descriptor (its `copied` and `fseq` start cleared).
+int enqueue_ransac(kmx_lcd* h, int n, int stages, bool want_masks, bool sync_call = false, SmallCall* sc = nullptr) {
   if (h->P.rng_stream) return verify_ordered(h, n, stages, want_masks);
-  if (sync_ok && n > 0 && n <= h->spread_max)
-    return ransac_spread(h, n, stages, want_masks, copy_out, copied, res_dst, mask_dst, inited, fseq);
+  if (takes_spread(h, n, sync_call)) return ransac_spread(h, n, stages, want_masks, sc);
   const RsParams rp = rs_params(h, stages);
   if (int rc = launch_ransac(h, n, rp, h->d_table, 0, want_masks || rp.pnp)) return rc;
   if (rp.pnp && (stages & KMX_LCD_STAGE_RECOVER))
@@ -4112,18 +4050,28 @@ int enqueue_ransac(kmx_lcd* h, int n, int stages, bool want_masks, bool sync_ok 
 // The side stream may write the current slot once the last RANSAC that read it
 // (LCD_SLOTS calls back) is done; the candidate uploads then go on it.
 int slot_upload(kmx_lcd* h, int n, const int32_t* cq, const int32_t* cm) {
-  const int s = h->cur, s2 = (s + LCD_SLOTS - 2) % LCD_SLOTS;
-  if (h->ev_rs_set[s]) KMX_HIP(hipStreamWaitEvent(h->kstream, h->ev_rs[s], 0));
-  if (!h->rs_small && h->ev_rs_set[s2]) KMX_HIP(hipStreamWaitEvent(h->kstream, h->ev_rs[s2], 0));
-  KMX_HIP(hipMemcpyAsync(h->d_cq, cq, sizeof(int) * n, hipMemcpyHostToDevice, h->kstream));
-  KMX_HIP(hipMemcpyAsync(h->d_cm, cm, sizeof(int) * n, hipMemcpyHostToDevice, h->kstream));
+  const Slot &sl = cur_slot(h), &sl2 = h->slot[(h->cur + LCD_SLOTS - 2) % LCD_SLOTS];
+  if (sl.ev_rs_set) KMX_HIP(hipStreamWaitEvent(h->kstream, sl.ev_rs, 0));
+  if (!h->rs_small && sl2.ev_rs_set) KMX_HIP(hipStreamWaitEvent(h->kstream, sl2.ev_rs, 0));
+  KMX_HIP(hipMemcpyAsync(sl.cq, cq, sizeof(int) * n, hipMemcpyHostToDevice, h->kstream));
+  KMX_HIP(hipMemcpyAsync(sl.cm, cm, sizeof(int) * n, hipMemcpyHostToDevice, h->kstream));
   return 0;
 }
-// The kNN2 of n candidates (ids at dcq / dcm) on stream st: k_knn2, or for a
-// synchronous call of <= KS_MAX candidates the split form k_knn2s (same rows).
+// The kNN2 of n candidates on stream st: k_knn2, or for a synchronous call of
+// <= KS_MAX candidates the split form k_knn2s (same rows). KnnIo: where it
+// reads the ids and writes the rows (the slot's buffers, or mapped staging);
+// Done: the completion word its last workgroup stores (k_knn2s only).
 constexpr int KS_MAX = 64;
-int launch_knn2(kmx_lcd* h, int n, const int* dcq, const int* dcm, hipStream_t st, bool sync_call,
-                int2* pairs_dst = nullptr, int* k_dst = nullptr, unsigned* done = nullptr, unsigned seq = 0) {
+struct KnnIo {
+  const int *cq, *cm;
+  int2* pairs;
+  int* K;
+};
+struct Done {
+  unsigned* word = nullptr;
+  unsigned seq = 0;
+};
+int launch_knn2(kmx_lcd* h, int n, const KnnIo& io, hipStream_t st, bool sync_call, Done done = {}) {
   if (sync_call && h->knn_split && n <= KS_MAX) {
     if (h->kqb_N < h->N) {
       KMX_HIP(hipStreamSynchronize(st));
@@ -4140,17 +4088,15 @@ int launch_knn2(kmx_lcd* h, int n, const int* dcq, const int* dcm, hipStream_t s
     const int S = (h->N + KS_Q - 1) / KS_Q;
     const size_t smem = (size_t)h->N * 32 + sizeof(uint32_t) * 4 * KS_Q * 2 + sizeof(int) * (KNN_BLOCK + 1);
     hipLaunchKernelGGL(h->P.norm == KMX_NORM_HAMMING ? k_knn2s<true> : k_knn2s<false>, dim3(n * S), dim3(KNN_BLOCK),
-                       smem, st, (const uint32_t*)h->d_desc, (const int*)h->d_nfeat, h->N, dcq, dcm,
-                       h->P.lowe_ratio, pairs_dst ? pairs_dst : h->d_pairs, k_dst ? k_dst : h->d_K, h->d_kqb,
-                       h->d_kcnt, S, done, seq);
+                       smem, st, (const uint32_t*)h->d_desc, (const int*)h->d_nfeat, h->N, io.cq, io.cm,
+                       h->P.lowe_ratio, io.pairs, io.K, h->d_kqb, h->d_kcnt, S, done.word, done.seq);
   } else if (h->knn_q && h->P.norm == KMX_NORM_HAMMING && h->N <= KQ_BLOCK * KQ_Q) {
-    hipLaunchKernelGGL(k_knn2q<true>, dim3(n), dim3(KQ_BLOCK),
-                       (size_t)h->N * 32, st, (const uint32_t*)h->d_desc, (const int*)h->d_nfeat, h->N, dcq, dcm,
-                       h->P.lowe_ratio, pairs_dst ? pairs_dst : h->d_pairs, k_dst ? k_dst : h->d_K);
+    hipLaunchKernelGGL(k_knn2q<true>, dim3(n), dim3(KQ_BLOCK), (size_t)h->N * 32, st, (const uint32_t*)h->d_desc,
+                       (const int*)h->d_nfeat, h->N, io.cq, io.cm, h->P.lowe_ratio, io.pairs, io.K);
   } else {
     hipLaunchKernelGGL(k_knn2, dim3(n), dim3(KNN_BLOCK), (size_t)h->N * 32 + sizeof(int) * (KNN_BLOCK + 1), st,
-                       (const uint32_t*)h->d_desc, (const int*)h->d_nfeat, h->N, dcq, dcm, h->P.norm,
-                       h->P.lowe_ratio, pairs_dst ? pairs_dst : h->d_pairs, k_dst ? k_dst : h->d_K);
+                       (const uint32_t*)h->d_desc, (const int*)h->d_nfeat, h->N, io.cq, io.cm, h->P.norm,
+                       h->P.lowe_ratio, io.pairs, io.K);
   }
   return 0;
 }
@@ -4159,9 +4105,9 @@ int launch_knn2(kmx_lcd* h, int n, const int* dcq, const int* dcm, hipStream_t s
 // stream behind it: a call's kNN2 runs in the previous call's RANSAC tail
 // (the work-queue RANSAC holds every wave slot until its queue drains, so the
 // kNN2 workgroups start as its last waves leave), off the critical path.
-int enqueue_verify(kmx_lcd* h, int n, bool want_masks, bool sync_ok = false) {
+int enqueue_verify(kmx_lcd* h, int n, bool want_masks, bool sync_call = false) {
   if (n == 0) return 0;
-  const int s = h->cur;
+  Slot& sl = cur_slot(h);
   if (h->timing) {
     if (!h->ev_ok) {
       for (auto& e : h->ev) KMX_HIP(hipEventCreate(&e));
@@ -4169,22 +4115,22 @@ int enqueue_verify(kmx_lcd* h, int n, bool want_masks, bool sync_ok = false) {
     }
     KMX_HIP(hipEventRecord(h->ev[0], h->kstream));
   }
-  if (int rc = launch_knn2(h, n, h->d_cq, h->d_cm, h->kstream, sync_ok)) return rc;
+  if (int rc = launch_knn2(h, n, KnnIo{sl.cq, sl.cm, sl.pairs, sl.K}, h->kstream, sync_call)) return rc;
   if (h->timing) KMX_HIP(hipEventRecord(h->ev[1], h->kstream));
-  KMX_HIP(hipEventRecord(h->ev_knn[s], h->kstream));
-  KMX_HIP(hipStreamWaitEvent(rs_stream(h), h->ev_knn[s], 0));
-  if (int rc = enqueue_ransac(h, n, KMX_LCD_STAGE_2D2D | KMX_LCD_STAGE_RECOVER, want_masks, sync_ok)) return rc;
+  KMX_HIP(hipEventRecord(sl.ev_knn, h->kstream));
+  KMX_HIP(hipStreamWaitEvent(rs_stream(h), sl.ev_knn, 0));
+  if (int rc = enqueue_ransac(h, n, KMX_LCD_STAGE_2D2D | KMX_LCD_STAGE_RECOVER, want_masks, sync_call)) return rc;
   if (h->timing) KMX_HIP(hipEventRecord(h->ev[2], rs_stream(h)));
-  KMX_HIP(hipEventRecord(h->ev_rs[s], rs_stream(h)));
-  h->ev_rs_set[s] = true;
+  KMX_HIP(hipEventRecord(sl.ev_rs, rs_stream(h)));
+  sl.ev_rs_set = true;
   KMX_HIP(hipGetLastError());
   return 0;
 }
 // Calls that work on the current slot from the handle's stream only (match,
 // verify_matches): they end with its RANSAC-done event too.
 int mark_slot(kmx_lcd* h) {
-  KMX_HIP(hipEventRecord(h->ev_rs[h->cur], rs_stream(h)));
-  h->ev_rs_set[h->cur] = true;
+  KMX_HIP(hipEventRecord(cur_slot(h).ev_rs, rs_stream(h)));
+  cur_slot(h).ev_rs_set = true;
   return 0;
 }
 
@@ -4203,9 +4149,7 @@ int grow_pool(kmx_lcd* h, int need) {
       if (x) (void)hipFree(x);
     return kmx::fail(KMX_ENOMEM, "frame pool");
   }
-  KMX_HIP(hipStreamSynchronize(h->kstream));  // a kNN2 in flight may read the old pool
-  for (hipStream_t x : h->rsx)  // and the slots' RANSACs (slot 0's is on h->stream, below)
-    if (x) KMX_HIP(hipStreamSynchronize(x));
+  KMX_HIP(sync_all(h));  // a kNN2 or a RANSAC in flight may read the old pool
   if (h->F) {
     KMX_HIP(hipMemcpyAsync(desc, h->d_desc, old * 32, hipMemcpyDeviceToDevice, h->stream));
     KMX_HIP(hipMemcpyAsync(bear, h->d_bear, old * 3 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
@@ -4290,16 +4234,9 @@ int upload_frames(kmx_lcd* h, int n, const int32_t* n_feats, const uint8_t* desc
 
 extern "C" int kmx_lcd_create(const kmx_lcd_params* params, int device, kmx_lcd** out) {
   KMX_GUARD_BEGIN
-  KMX_CHECK(params && out, KMX_EINVAL, "null argument");
-  KMX_CHECK(params->norm == KMX_NORM_L1 || params->norm == KMX_NORM_HAMMING, KMX_EINVAL, "bad norm");
-  KMX_CHECK(params->rng_variant == KMX_RNG_GCC9 || params->rng_variant == KMX_RNG_GCC11, KMX_EINVAL,
-            "bad rng variant");
-  KMX_CHECK(params->ransac_randomize == 0, KMX_EUNSUP, "ransac_randomize = 1 is not reproducible; use 0");
-  KMX_CHECK(params->use_1point_3d3d == 0 || params->use_1point_3d3d == 1, KMX_EINVAL, "use_1point_3d3d is 0 or 1");
-  KMX_CHECK(params->algorithm_2d2d == KMX_ALGO_STEWENIUS || params->algorithm_2d2d == KMX_ALGO_NISTER, KMX_EUNSUP,
-            "ransac_2d2d_algorithm: 0 (Stewenius) and 1 (Nister) are built");
-  KMX_CHECK(params->ransac_max_iterations > 0, KMX_EINVAL, "ransac_max_iterations must be > 0");
-  KMX_CHECK(params->rng_stream == 0 || params->rng_stream == 1, KMX_EINVAL, "rng_stream is 0 or 1");
+  KMX_CHECK(out, KMX_EINVAL, "null argument");
+  std::string err;
+  if (int rc = kmx::lcd_check_params(params, &err)) return kmx::fail(rc, err);
   int ndev = 0;
   KMX_HIP(hipGetDeviceCount(&ndev));
   KMX_CHECK(device >= 0 && device < ndev, KMX_EINVAL, "bad HIP device ordinal");
@@ -4318,10 +4255,11 @@ extern "C" int kmx_lcd_create(const kmx_lcd_params* params, int device, kmx_lcd*
   if (const char* e = std::getenv("KMX_LCD_KNNQ")) h->knn_q = std::atoi(e) != 0;
   if (const char* e = std::getenv("KMX_LCD_SPINWAIT")) h->spin_wait = std::atoi(e) != 0;
   bool ok = hipStreamCreateWithFlags(&h->kstream, hipStreamNonBlocking) == hipSuccess;
-  for (int i = 1; i < LCD_SLOTS && ok; ++i) ok = hipStreamCreateWithFlags(&h->rsx[i], hipStreamNonBlocking) == hipSuccess;
+  for (int i = 1; i < LCD_SLOTS && ok; ++i)
+    ok = hipStreamCreateWithFlags(&h->slot[i].rsx, hipStreamNonBlocking) == hipSuccess;
   for (int i = 0; i < LCD_SLOTS && ok; ++i)
-    ok = hipEventCreateWithFlags(&h->ev_knn[i], hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&h->ev_rs[i], hipEventDisableTiming) == hipSuccess;
+    ok = hipEventCreateWithFlags(&h->slot[i].ev_knn, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&h->slot[i].ev_rs, hipEventDisableTiming) == hipSuccess;
   if (!ok) {
     kmx_lcd_destroy(h);
     return kmx::fail(KMX_EHIP, "hipStreamCreate / hipEventCreate");
@@ -4337,22 +4275,19 @@ extern "C" int kmx_lcd_create(const kmx_lcd_params* params, int device, kmx_lcd*
 extern "C" int kmx_lcd_destroy(kmx_lcd* h) {
   if (!h) return KMX_OK;
   (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  sync_rsx(h);
-  if (h->kstream) (void)hipStreamSynchronize(h->kstream);
+  (void)sync_all(h);
   lcd_free_frames(h);
   lcd_free_tables(h);
   lcd_free_cand(h);
-  lcd_free_pairs(h);
+  lcd_free_staging(h);
   if (h->ev_ok)
     for (auto e : h->ev) (void)hipEventDestroy(e);
-  for (int i = 0; i < LCD_SLOTS; ++i) {
-    if (h->ev_knn[i]) (void)hipEventDestroy(h->ev_knn[i]);
-    if (h->ev_rs[i]) (void)hipEventDestroy(h->ev_rs[i]);
+  for (Slot& sl : h->slot) {
+    if (sl.ev_knn) (void)hipEventDestroy(sl.ev_knn);
+    if (sl.ev_rs) (void)hipEventDestroy(sl.ev_rs);
+    if (sl.rsx) (void)hipStreamDestroy(sl.rsx);
   }
   if (h->kstream) (void)hipStreamDestroy(h->kstream);
-  for (hipStream_t x : h->rsx)
-    if (x) (void)hipStreamDestroy(x);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return KMX_OK;
@@ -4362,10 +4297,7 @@ extern "C" int kmx_lcd_set_stream(kmx_lcd* h, void* s) {
   KMX_GUARD_BEGIN
   KMX_CHECK(h, KMX_EINVAL, "null handle");
   KMX_HIP(hipSetDevice(h->device));
-  if (h->kstream) KMX_HIP(hipStreamSynchronize(h->kstream));
-  for (hipStream_t x : h->rsx)
-    if (x) KMX_HIP(hipStreamSynchronize(x));
-  if (h->stream) KMX_HIP(hipStreamSynchronize(h->stream));
+  KMX_HIP(sync_all(h));
   if (h->own_stream && h->stream) KMX_HIP(hipStreamDestroy(h->stream));
   h->own_stream = false;
   h->stream = reinterpret_cast<hipStream_t>(s);
@@ -4440,8 +4372,8 @@ int kmx::lcd_pool_view(kmx_lcd* h, kmx::LcdPoolView* out) {
 static int check_cands(kmx_lcd* h, int32_t n, const int32_t* cq, const int32_t* cm) {
   KMX_CHECK(h && h->d_desc && h->F > 0, KMX_ESTATE, "no frames: set_frames or add_frames first");
   KMX_CHECK(n >= 0 && (n == 0 || (cq && cm)), KMX_EINVAL, "bad candidate arrays");
-  for (int i = 0; i < n; ++i)
-    KMX_CHECK(cq[i] >= 0 && cq[i] < h->F && cm[i] >= 0 && cm[i] < h->F, KMX_EINVAL, "candidate frame id out of range");
+  std::string err;
+  if (int rc = kmx::lcd_check_cands(n, h->F, cq, cm, &err)) return kmx::fail(rc, err);
   return 0;
 }
 
@@ -4454,9 +4386,10 @@ extern "C" int kmx_lcd_verify(kmx_lcd* h, int32_t n, const int32_t* cq, const in
   if (int rc = ensure_cap(h, n, false)) return rc;
   if (int rc = slot_upload(h, n, cq, cm)) return rc;
   if (int rc = enqueue_verify(h, n, inlier_masks != nullptr, true)) return rc;
-  if (n) KMX_HIP(hipMemcpyAsync(results, h->d_res, sizeof(kmx_lcd_result) * n, hipMemcpyDeviceToHost, rs_stream(h)));
+  const Slot& sl = cur_slot(h);
+  if (n) KMX_HIP(hipMemcpyAsync(results, sl.res, sizeof(kmx_lcd_result) * n, hipMemcpyDeviceToHost, rs_stream(h)));
   if (n && inlier_masks)
-    KMX_HIP(hipMemcpyAsync(inlier_masks, h->d_mask, (size_t)n * h->N, hipMemcpyDeviceToHost, rs_stream(h)));
+    KMX_HIP(hipMemcpyAsync(inlier_masks, sl.mask, (size_t)n * h->N, hipMemcpyDeviceToHost, rs_stream(h)));
   KMX_HIP(hipStreamSynchronize(rs_stream(h)));
   return KMX_OK;
   KMX_GUARD_END
@@ -4485,32 +4418,35 @@ extern "C" int kmx_lcd_match(kmx_lcd* h, int32_t n, const int32_t* cq, const int
   // pinned staging: [cq][cm] in, [pairs][K] out. The split kNN2 (small calls)
   // reads the ids from the mapped staging and writes the rows there
   // (zero-copy); k_knn2 goes through the device buffers and copies.
-  const size_t pb = sizeof(int2) * (size_t)n * h->N, kin = al16(sizeof(int) * n), o_out = 2 * kin;
-  if (int rc = io_reserve(h, o_out + pb + kin)) return rc;
-  std::memcpy(h->h_io, cq, sizeof(int) * n);
-  std::memcpy(h->h_io + kin, cm, sizeof(int) * n);
+  const kmx::LcdMatchLayout L = kmx::lcd_match_layout(n, h->N);
+  const size_t pb = sizeof(int2) * (size_t)n * h->N;
+  if (int rc = io_reserve(h, L.total)) return rc;
+  std::memcpy(h->h_io + L.o_cq, cq, sizeof(int) * n);
+  std::memcpy(h->h_io + L.o_cm, cm, sizeof(int) * n);
+  const Slot& sl = cur_slot(h);
   const bool zc = h->knn_split && n <= KS_MAX;
-  unsigned seq = 0;
-  unsigned* done = zc && n == 1 ? next_done(h, &seq) : nullptr;  // one candidate: spin on the completion word
+  Done done;
+  if (zc && n == 1) done.word = next_done(h, &done.seq);  // one candidate: spin on the completion word
   if (zc) {
-    if (int rc = launch_knn2(h, n, (const int*)h->z_io, (const int*)(h->z_io + kin), rs_stream(h), true,
-                             (int2*)(h->z_io + o_out), (int*)(h->z_io + o_out + pb), done, seq))
-      return rc;
+    char* z = h->z_io;
+    const KnnIo io{(const int*)(z + L.o_cq), (const int*)(z + L.o_cm), (int2*)(z + L.o_pairs), (int*)(z + L.o_K)};
+    if (int rc = launch_knn2(h, n, io, rs_stream(h), true, done)) return rc;
   } else {
-    KMX_HIP(hipMemcpyAsync(h->d_io, h->h_io, 2 * kin, hipMemcpyHostToDevice, rs_stream(h)));
-    if (int rc = launch_knn2(h, n, (const int*)h->d_io, (const int*)(h->d_io + kin), rs_stream(h), true)) return rc;
-    KMX_HIP(hipMemcpyAsync(h->h_io + o_out, h->d_pairs, pb, hipMemcpyDeviceToHost, rs_stream(h)));
-    KMX_HIP(hipMemcpyAsync(h->h_io + o_out + pb, h->d_K, sizeof(int) * n, hipMemcpyDeviceToHost, rs_stream(h)));
+    KMX_HIP(hipMemcpyAsync(h->d_io, h->h_io, L.o_pairs, hipMemcpyHostToDevice, rs_stream(h)));
+    const KnnIo io{(const int*)(h->d_io + L.o_cq), (const int*)(h->d_io + L.o_cm), sl.pairs, sl.K};
+    if (int rc = launch_knn2(h, n, io, rs_stream(h), true)) return rc;
+    KMX_HIP(hipMemcpyAsync(h->h_io + L.o_pairs, sl.pairs, pb, hipMemcpyDeviceToHost, rs_stream(h)));
+    KMX_HIP(hipMemcpyAsync(h->h_io + L.o_K, sl.K, sizeof(int) * n, hipMemcpyDeviceToHost, rs_stream(h)));
   }
   KMX_HIP(hipGetLastError());
   if (int rc = mark_slot(h)) return rc;
-  if (done) {
-    if (int rc = wait_done(h, rs_stream(h), seq)) return rc;
+  if (done.word) {
+    if (int rc = wait_done(h, rs_stream(h), done.seq)) return rc;
   } else {
     KMX_HIP(hipStreamSynchronize(rs_stream(h)));
   }
-  std::memcpy(pairs_out, h->h_io + o_out, pb);
-  std::memcpy(k_out, h->h_io + o_out + pb, sizeof(int) * n);
+  std::memcpy(pairs_out, h->h_io + L.o_pairs, pb);
+  std::memcpy(k_out, h->h_io + L.o_K, sizeof(int) * n);
   return KMX_OK;
   KMX_GUARD_END
 }
@@ -4528,85 +4464,67 @@ extern "C" int kmx_lcd_verify_matches(kmx_lcd* h, int32_t n, const int32_t* cq, 
   KMX_CHECK(!need_prior || T_prior, KMX_EINVAL,
             "the 1-point 3D-3D recovery without the 2D-2D stage needs T_prior (the 2D-2D rotation)");
   if (n == 0) return KMX_OK;
-  const int64_t base = mptr[0];
-  KMX_CHECK(base >= 0, KMX_EINVAL, "mptr[0] < 0");
-  KMX_CHECK(mptr[n] == base || (iq && im), KMX_EINVAL, "null i_query / i_match with correspondences in mptr");
-  for (int i = 0; i < n; ++i) {
-    const int64_t K = mptr[i + 1] - mptr[i];
-    KMX_CHECK(K >= 0 && K <= h->N, KMX_EINVAL, "a candidate has more pairs than max_feats (or mptr decreases)");
-    const int nq = h->h_nfeat[cq[i]], nm = h->h_nfeat[cm[i]];
-    for (int64_t k = mptr[i]; k < mptr[i + 1]; ++k)
-      KMX_CHECK(iq[k] >= 0 && iq[k] < nq && im[k] >= 0 && im[k] < nm, KMX_EINVAL,
-                "correspondence index outside its frame's features");
+  {
+    std::string err;
+    if (int rc = kmx::lcd_check_csr(n, h->N, mptr, iq, im, cq, cm, h->h_nfeat.data(), &err)) return kmx::fail(rc, err);
   }
+  const int64_t base = mptr[0];
   const size_t total = (size_t)(mptr[n] - base);
   KMX_HIP(hipSetDevice(h->device));
   if (int rc = ensure_cap(h, n, false)) return rc;
   if (int rc = rs_wait_slot(h)) return rc;
-  // every input in one pinned block and one host-to-device copy:
-  // [mptr - base][cq][cm][i_query][i_match][T_prior]; k_scatter_pairs moves
-  // the candidates' ids and priors into the slot's buffers
-  const size_t o_cq = al16(sizeof(int64_t) * (n + 1)), o_cm = o_cq + al16(sizeof(int) * n),
-               o_iq = o_cm + al16(sizeof(int) * n), o_im = o_iq + al16(sizeof(int) * total),
-               o_pr = o_im + al16(sizeof(int) * total), in_bytes = o_pr + (T_prior ? sizeof(double) * 12 * n : 0);
-  const size_t rb = al16(sizeof(kmx_lcd_result) * n), out_bytes = rb + (inlier_masks ? (size_t)n * h->N : 0);
-  const size_t o_out = al16(in_bytes);  // outputs after the inputs (zero-copy kernels read and write at once)
-  if (int rc = io_reserve(h, o_out + out_bytes)) return rc;
+  // every input in one pinned block and one host-to-device copy;
+  // k_scatter_pairs moves the candidates' ids and priors into the slot's buffers
+  const kmx::LcdVerifyLayout L = kmx::lcd_verify_layout(n, h->N, total, T_prior != nullptr, inlier_masks != nullptr);
+  if (int rc = io_reserve(h, L.total)) return rc;
   {
-    int64_t* mp = reinterpret_cast<int64_t*>(h->h_io);
+    int64_t* mp = reinterpret_cast<int64_t*>(h->h_io + L.o_mptr);
     for (int i = 0; i <= n; ++i) mp[i] = mptr[i] - base;
-    std::memcpy(h->h_io + o_cq, cq, sizeof(int) * n);
-    std::memcpy(h->h_io + o_cm, cm, sizeof(int) * n);
+    std::memcpy(h->h_io + L.o_cq, cq, sizeof(int) * n);
+    std::memcpy(h->h_io + L.o_cm, cm, sizeof(int) * n);
     if (total) {
-      std::memcpy(h->h_io + o_iq, iq + base, sizeof(int) * total);
-      std::memcpy(h->h_io + o_im, im + base, sizeof(int) * total);
+      std::memcpy(h->h_io + L.o_iq, iq + base, sizeof(int) * total);
+      std::memcpy(h->h_io + L.o_im, im + base, sizeof(int) * total);
     }
-    if (T_prior) std::memcpy(h->h_io + o_pr, T_prior, sizeof(double) * 12 * n);
+    if (T_prior) std::memcpy(h->h_io + L.o_prior, T_prior, sizeof(double) * 12 * n);
   }
   // a spread-form call (small, synchronous) reads its inputs from the mapped
   // staging and, without PnP (k_recover writes through the device buffers),
   // its finish writes the results there: no copy in either direction
-  const bool spread = !h->P.rng_stream && n <= h->spread_max;
-  const bool zc_out = spread && !rs_params(h, stages).pnp;
+  const bool spread = takes_spread(h, n, true);
+  SmallCall sc;
+  sc.inited = spread;
+  sc.o_res = L.o_res;
+  sc.o_mask = inlier_masks ? L.o_mask : 0;
+  if (spread && !rs_params(h, stages).pnp) {
+    sc.res_dst = reinterpret_cast<kmx_lcd_result*>(h->z_io + L.o_res);
+    if (inlier_masks) sc.mask_dst = reinterpret_cast<unsigned char*>(h->z_io + L.o_mask);
+  }
   const char* src = spread ? h->z_io : h->d_io;
   if (spread) {
     if (int rc = spread_alloc(h, n)) return rc;
   } else {
-    KMX_HIP(hipMemcpyAsync(h->d_io, h->h_io, in_bytes, hipMemcpyHostToDevice, rs_stream(h)));
+    KMX_HIP(hipMemcpyAsync(h->d_io, h->h_io, L.in_bytes, hipMemcpyHostToDevice, rs_stream(h)));
   }
-  hipLaunchKernelGGL(k_scatter_pairs, dim3(n), dim3(256), 0, rs_stream(h), (const int64_t*)src,
-                     (const int*)(src + o_iq), (const int*)(src + o_im), h->N, h->d_pairs, h->d_K,
-                     (const int*)(src + o_cq), (const int*)(src + o_cm),
-                     T_prior ? (const double*)(src + o_pr) : nullptr, h->d_cq, h->d_cm, h->d_prior,
+  const Slot& sl = cur_slot(h);
+  hipLaunchKernelGGL(k_scatter_pairs, dim3(n), dim3(256), 0, rs_stream(h), (const int64_t*)(src + L.o_mptr),
+                     (const int*)(src + L.o_iq), (const int*)(src + L.o_im), h->N, sl.pairs, sl.K,
+                     (const int*)(src + L.o_cq), (const int*)(src + L.o_cm),
+                     T_prior ? (const double*)(src + L.o_prior) : nullptr, sl.cq, sl.cm, sl.prior,
                      spread ? h->d_st : nullptr, h->d_hcnt, stages, h->d_more, h->more_cap);
   KMX_HIP(hipGetLastError());
-  const std::function<int()> copy_out = [&]() -> int {
-    if (zc_out) return 0;
-    KMX_HIP(hipMemcpyAsync(h->h_io + o_out, h->d_res, sizeof(kmx_lcd_result) * n, hipMemcpyDeviceToHost,
-                           rs_stream(h)));
-    if (inlier_masks)
-      KMX_HIP(hipMemcpyAsync(h->h_io + o_out + rb, h->d_mask, (size_t)n * h->N, hipMemcpyDeviceToHost,
-                             rs_stream(h)));
-    return 0;
-  };
-  bool copied = false;
-  unsigned fseq = 0;  // the last kernel's completion word (one zero-copy candidate)
-  if (int rc = enqueue_ransac(h, n, stages, inlier_masks != nullptr, true, &copy_out, &copied,
-                              zc_out ? reinterpret_cast<kmx_lcd_result*>(h->z_io + o_out) : nullptr,
-                              zc_out && inlier_masks ? reinterpret_cast<unsigned char*>(h->z_io + o_out + rb) : nullptr,
-                              spread, &fseq))
-    return rc;
+  if (int rc = enqueue_ransac(h, n, stages, inlier_masks != nullptr, true, &sc)) return rc;
   KMX_HIP(hipGetLastError());
-  if (!copied)
-    if (int rc = copy_out()) return rc;
+  if (!sc.copied && !sc.res_dst)
+    if (int rc = copy_results(h, sl, n, sc.o_res, sc.o_mask)) return rc;
   if (int rc = mark_slot(h)) return rc;
-  if (fseq) {
-    if (int rc = wait_done(h, rs_stream(h), fseq)) return rc;
+  if (sc.fseq) {
+    if (int rc = wait_done(h, rs_stream(h), sc.fseq)) return rc;
   } else {
     KMX_HIP(hipStreamSynchronize(rs_stream(h)));
   }
-  std::memcpy(results, h->h_io + o_out, sizeof(kmx_lcd_result) * n);
-  if (inlier_masks) std::memcpy(inlier_masks, h->h_io + o_out + rb, (size_t)n * h->N);
+  std::memcpy(results, h->h_io + L.o_res, sizeof(kmx_lcd_result) * n);
+  if (inlier_masks) std::memcpy(inlier_masks, h->h_io + L.o_mask, (size_t)n * h->N);
   return KMX_OK;
   KMX_GUARD_END
 }
@@ -4621,10 +4539,7 @@ extern "C" int kmx_lcd_read_timing(kmx_lcd* h, double* knn_ms, double* ransac_ms
   KMX_CHECK(h && knn_ms && ransac_ms, KMX_EINVAL, "null argument");
   KMX_CHECK(h->ev_ok, KMX_ESTATE, "no evented verification yet (kmx_lcd_enable_timing)");
   KMX_HIP(hipSetDevice(h->device));
-  KMX_HIP(hipStreamSynchronize(h->kstream));
-  KMX_HIP(hipStreamSynchronize(h->stream));
-  for (hipStream_t x : h->rsx)
-    if (x) KMX_HIP(hipStreamSynchronize(x));
+  KMX_HIP(sync_all(h));
   float a = 0.f, b = 0.f;
   KMX_HIP(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
   KMX_HIP(hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
@@ -4636,10 +4551,7 @@ extern "C" int kmx_lcd_read_timing(kmx_lcd* h, double* knn_ms, double* ransac_ms
 extern "C" int kmx_lcd_sync(kmx_lcd* h) {
   KMX_CHECK(h, KMX_EINVAL, "null handle");
   KMX_HIP(hipSetDevice(h->device));
-  KMX_HIP(hipStreamSynchronize(h->kstream));
-  KMX_HIP(hipStreamSynchronize(h->stream));
-  for (hipStream_t x : h->rsx)
-    if (x) KMX_HIP(hipStreamSynchronize(x));
+  KMX_HIP(sync_all(h));
   return KMX_OK;
 }
 

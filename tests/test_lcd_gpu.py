@@ -202,6 +202,51 @@ def test_concurrent_slots_mixed_sizes(gpu, monkeypatch, env):
         assert all(np.array_equal(g[k], w[k]) for k in g)
 
 
+def test_pool_replaced_with_other_max_feats_while_slots_are_warm(gpu):
+    """A pool with another max_feats frees every slot's buffers (they are
+    sized by it) and the next calls allocate them again: after async calls
+    and a match have warmed several slots over pool A, verify, match and
+    verify_matches over pool B, and verify over A again, equal a fresh
+    detector's."""
+    A = make_lcd_pool(16, 64, seed=31)
+    B = make_lcd_pool(24, 96, seed=37)
+    p = LcdParams()
+
+    def same(got, want):
+        return len(got) == len(want) and all(np.array_equal(g[k], w[k]) for g, w in zip(got, want) for k in g)
+
+    ref = LoopClosureDetector(p)
+    ref.set_pool(B)
+    want, wm = ref.verify(B.cand_query, B.cand_match, with_masks=True)
+    wp, wk = ref.match(B.cand_query, B.cand_match)
+    corr = [(wp[i, :wk[i], 0], wp[i, :wk[i], 1]) for i in range(len(wk))]
+    wv, wvm = ref.verify_matches(B.cand_query, B.cand_match, corr, with_masks=True)
+    ref.close()
+    ref = LoopClosureDetector(p)
+    ref.set_pool(A)
+    want_a, wm_a = ref.verify(A.cand_query, A.cand_match, with_masks=True)
+    ref.close()
+
+    det = LoopClosureDetector(p)
+    det.set_pool(A)
+    for _ in range(3):
+        det.verify_async(A.cand_query, A.cand_match)
+    det.match(A.cand_query, A.cand_match)
+    det.sync()
+    det.set_pool(B)
+    got, gm = det.verify(B.cand_query, B.cand_match, with_masks=True)
+    assert np.array_equal(gm, wm) and same(got, want)
+    gp, gk = det.match(B.cand_query, B.cand_match)
+    assert np.array_equal(gk, wk)
+    assert all(np.array_equal(gp[i, :gk[i]], wp[i, :wk[i]]) for i in range(len(wk)))  # (rows past k: unspecified)
+    gv, gvm = det.verify_matches(B.cand_query, B.cand_match, corr, with_masks=True)
+    assert np.array_equal(gvm, wvm) and same(gv, wv)
+    det.set_pool(A)
+    got, gm = det.verify(A.cand_query, A.cand_match, with_masks=True)
+    assert np.array_equal(gm, wm_a) and same(got, want_a)
+    det.close()
+
+
 @pytest.mark.parametrize("norm", ["l1", "hamming"])
 def test_split_knn2_matches_oracle(gpu, monkeypatch, norm):
     """kmx_lcd_match on resident frames: the small-call kNN2 (k_knn2s, a
