@@ -16,7 +16,9 @@
 //     enqueueing tCG steps (polled, blind or adaptive, kmx_pgo_set_tcg_poll).
 //   * tCG in the linearity form: Hz by gather, delta = -z + beta delta_old,
 //     Hdelta = -Hz + beta Hdelta_old; eta = sum coef_k delta_k is folded from
-//     two kept directions every second step and finished in k_retract.
+//     two kept directions every second step and finished where the trial
+//     point is formed: k_retract, or in the consumer form the k_update that
+//     ends the robot's tCG (at the step cap: k_update_last).
 //   * Edge data: one 64-B compact record per incidence in CSR order (three
 //     components of R's unit quaternion, t, w kappa, +-w tau — the sign bit is
 //     the tail flag) plus a 4-B word (Dev::rec_o): its other endpoint and, in
@@ -991,7 +993,7 @@ __device__ __forceinline__ double inc_owner_cost(const Dev& d, const Lane& L, co
 // double-buffered (k_hess: ctl -> ctl2, k_update: ctl2 -> ctl), so no
 // workgroup reads a state another one of the same launch writes. The round's
 // other reductions are folded too (gradient -> first k_hess, last update ->
-// k_retract, trial cost -> k_commit), so a consumer-form round has no k_reduce
+// k_cost, trial cost -> k_commit), so a consumer-form round has no k_reduce
 // launch (12.5k poses 167.7 -> 161.4 us per round, profiles/r02/small_round/3_*).
 // Measured on configs[3] (profiles/r02/ab_red): at 100k poses the consumer
 // form loses (k_hess 41.2 us and k_update 22.7 us against 32.4 + 19.8 us plus
@@ -1545,23 +1547,36 @@ __device__ __forceinline__ void body_grad(const Dev& d, int gated, char* smem) {
 // first F were folded into d.eta by the Hess-vec launches), added to et. LAST:
 // the coefficient of direction T - 1 is clast (a k_step that ends the tCG
 // decided it in the same launch whose writer stores it to coefh).
+// In two halves, so that a caller that learns clast late (the last k_update)
+// has the rows in flight before it: issue() loads, finish() adds.
+struct EtaRows {
+  double dd[DHMAX][4];
+  int F;
+  __device__ __forceinline__ void issue(const Dev& d, size_t o, int T, double et[4]) {
+    const int dhn = d.dhn;
+    F = T > 0 ? (T - 1) / dhn * dhn : 0;
+    if (F > 0) load4(d.eta + o, et);
+#pragma unroll
+    for (int i = 0; i < DHMAX; ++i)
+      if (F + i < T) load4(d.dh + (size_t)i * d.vec + o, dd[i]);
+  }
+  template <bool LAST>
+  __device__ __forceinline__ void finish(const Dev& d, int l, int T, double clast, double et[4]) const {
+    const double* ch = d.coefh + (size_t)l * d.p.tcg_max;
+#pragma unroll
+    for (int i = 0; i < DHMAX; ++i)
+      if (F + i < T) {
+        const double cj = (LAST && F + i == T - 1) ? clast : ch[F + i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) et[k] += cj * dd[i][k];
+      }
+  }
+};
 template <bool LAST>
 __device__ __forceinline__ void eta_rows(const Dev& d, int l, size_t o, int T, double clast, double et[4]) {
-  const int dhn = d.dhn;
-  const int F = T > 0 ? (T - 1) / dhn * dhn : 0;
-  if (F > 0) load4(d.eta + o, et);
-  double dd[DHMAX][4];
-#pragma unroll
-  for (int i = 0; i < DHMAX; ++i)
-    if (F + i < T) load4(d.dh + (size_t)i * d.vec + o, dd[i]);
-  const double* ch = d.coefh + (size_t)l * d.p.tcg_max;
-#pragma unroll
-  for (int i = 0; i < DHMAX; ++i)
-    if (F + i < T) {
-      const double cj = (LAST && F + i == T - 1) ? clast : ch[F + i];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) et[k] += cj * dd[i][k];
-    }
+  EtaRows e;
+  e.issue(d, o, T, et);
+  e.finish<LAST>(d, l, T, clast, et);
 }
 
 // The trial point Xt = R_X(eta) of the lane's row, and the tile's partials
@@ -1818,14 +1833,27 @@ __device__ __forceinline__ void body_hess(const Dev& d, int gated, int slot, Hos
 
 // tCG step, part 2: r += coef Hdelta (eta = sum coef_k delta_k is formed in
 // k_retract); interior steps also z = precon(r) and partials <r,r>, <z,r>.
-template <int R, int RM>
+// LAST (consumer form): the update of the host's launch tcg_max - 1. A robot
+// it finds in tCG is at the step cap: its tCG ends after this update whatever
+// the stop test says, and at the cap upd_step does not read <z,r>. So this
+// instantiation forms no z (no preconditioner block, no z store, <z,r> = 0)
+// and goes on to the robot's trial point from the rows it holds: x, the
+// updated r, and this launch's coefficient as the last direction's (eta_rows'
+// clast; k_retract's arithmetic, same bits). It publishes the state with
+// `retracted` set and the phase still PH_TCG: the stop reason from ||r||^2 is
+// taken by k_cost (body_cost), so the round has no k_retract.
+template <int R, int RM, bool LAST = false>
 __device__ __forceinline__ void body_update(const Dev& d, HostStatus* hs, unsigned long long seq, int slot,
                                             char* smem) {
+  static_assert(!LAST || RM == RM_CONSUMER, "the launched form keeps k_retract");
   const Lane L = lane_map<R>(d);
   int tcg_iter, mode;
   double coef;
   const size_t o = (size_t)L.pose * 4 * R + 4 * L.a;
   double rr[4] = {0, 0, 0, 0}, y[4] = {0, 0, 0, 0}, hdl[4] = {0, 0, 0, 0};
+  double gg[4] = {0, 0, 0, 0}, et[4] = {0, 0, 0, 0};  // LAST: the trial point's g row and eta
+  EtaRows er;
+  int T = 0;
   if constexpr (RM == RM_CONSUMER) {
     // this step's k_hess partials: the control step after the Hess-vec (alpha
     // or the boundary tau) on a private copy, with the step's vector loads in
@@ -1843,8 +1871,9 @@ __device__ __forceinline__ void body_update(const Dev& d, HostStatus* hs, unsign
         // this step's k_hess ended the robot's tCG at its stop test: the trial
         // point and the model partials here (k_retract's arithmetic; every
         // coefficient was decided by an earlier launch), so a round whose
-        // robots all stop this way needs no k_retract (the host skips it, or
-        // launches it with fold = 2 for the robots still in tCG at the cap)
+        // robots all stop this way needs no k_retract (the robots still in
+        // tCG at the cap take the LAST path below, or with KMX_TCG_TAIL=0
+        // k_retract's fold 2)
         const size_t o2 = (size_t)L.pose * 4 * R + 4 * L.a;
         double x[4] = {0, 0, 0, 0}, gg[4] = {0, 0, 0, 0}, rr2[4] = {0, 0, 0, 0}, et[4] = {0, 0, 0, 0};
         if (L.valid) {
@@ -1861,6 +1890,13 @@ __device__ __forceinline__ void body_update(const Dev& d, HostStatus* hs, unsign
       return;
     }
     const bool first0 = cq.tcg_iter == 0;  // the control step makes it 1
+    if constexpr (LAST) {
+      T = cq.tcg_iter + 1;
+      if (T != d.p.tcg_max) {  // (cannot happen: a robot in tCG at the host's launch j has run j steps)
+        if (writer) ctl_publish(cout + L.l, cs, false);
+        return;
+      }
+    }
     RobotSum<1, 4> rs;
     rs.issue(d.part_h, 2, L.rt0, L.rt1);
     if (L.valid) {
@@ -1870,6 +1906,10 @@ __device__ __forceinline__ void body_update(const Dev& d, HostStatus* hs, unsign
       // (the preconditioner block loads in group_precon, after the projection:
       // held from here it is 20 VGPRs across the projection's read-back, 86
       // against 66 in all, and the round is slower for it)
+      if constexpr (LAST) {  // the trial point's rows: no address waits for the step's coefficient
+        load4(d.g + o, gg);
+        er.issue(d, o, T, et);
+      }
     }
     double tot[NPART] = {0.0, 0.0, 0.0, 0.0};
     rs.finish(d.part_h, 2, rl, tot);
@@ -1882,7 +1922,7 @@ __device__ __forceinline__ void body_update(const Dev& d, HostStatus* hs, unsign
       // lane 0's LDS writes, then the wave's reads (in-order LDS queue)
       __builtin_amdgcn_wave_barrier();
       asm volatile("" ::: "memory");
-      ctl_publish(cout + L.l, cs, false);
+      ctl_publish(cout + L.l, cs, LAST);
     }
     tcg_iter = cq.tcg_iter + 1;
     mode = hsx.boundary ? MODE_BOUNDARY : MODE_INTERIOR;
@@ -1913,6 +1953,17 @@ __device__ __forceinline__ void body_update(const Dev& d, HostStatus* hs, unsign
     }
   }
   double vals[2] = {0.0, 0.0}, zr[4] = {0, 0, 0, 0};
+  if constexpr (LAST) {
+    if (interior && L.valid) vals[0] = rr[0] * rr[0] + rr[1] * rr[1] + rr[2] * rr[2] + rr[3] * rr[3];
+    // the update's partials first: finish_tile's barrier ends every wave's use
+    // of the projection's scratch, whose start trial_rows reduces in
+    finish_tile<RED_UPDATE, 2, RM>(d, L, vals, smem + SmemU::red_off, [&]() {
+      if (L.valid) store4(d.r + o, rr);
+    });
+    if (L.valid) er.template finish<true>(d, L.l, T, coef, et);
+    trial_rows<R>(d, L, o, y, gg, rr, et, smem);
+    return;
+  }
   if (interior) {  // uniform per robot
     group_precon<R, true>(d, L.pose, L.valid, y, rr, L.base, zr, reinterpret_cast<double*>(smem));
     if (L.valid) {
@@ -2335,9 +2386,38 @@ __device__ __forceinline__ void body_cost(const Dev& d, const Ctl* src, char* sm
   const Lane L = lane_map<R>(d);
   const Ctl& c = src[L.l];
   if (src != d.ctl && threadIdx.x == 0 && L.tile == L.rt0) d.ctl[L.l] = c;
-  if (c.phase != PH_STEP) return;
+  const int ph = c.phase;
+  bool go = ph == PH_STEP;
+  if constexpr (RM == RM_CONSUMER) {
+    // A robot in PH_TCG with `retracted` set: the last k_update (body_update's
+    // LAST) found it at the step cap and formed its trial point. Its stop
+    // reason from that update's ||r||^2 is decided here, in place of a
+    // k_reduce launch, by the robot's first tile alone, which writes it into
+    // ctl in place as k_retract's fold does: the write changes only phase and
+    // tcg_stop, every other tile takes PH_TCG with `retracted` and PH_STEP
+    // alike as "a trial point to cost", and k_commit reads the state one
+    // launch later. (The one-sync form's src holds no such robot.)
+    go = go || (ph == PH_TCG && c.retracted);
+  }
+  if (!go) return;
   double cost = inc_owner_cost<R, RW>(d, L, d.Xt, d.pub, smem);
   finish_tile<RED_COST, 1, RM>(d, L, &cost, smem + SmemC<R>::red_off, []() {});
+  if constexpr (RM == RM_CONSUMER) {
+    // (after the gather, from a second read of the phase, which only this
+    // tile writes: decided before the gather it costs k_cost two registers)
+    if (L.tile == L.rt0 && c.phase == PH_TCG) {  // uniform per workgroup
+      __shared__ double rl[NPART * WAVES];
+      RobotSum<2> rs;
+      rs.issue(d.part_u, 2, L.rt0, L.rt1);
+      double tot[NPART] = {0.0, 0.0, 0.0, 0.0};
+      rs.finish(d.part_u, 2, rl, tot);
+      const UpdStep u = upd_step(c.mode, c.r_stop, c.lin_stop, c.z_r, c.tcg_iter, tot[0], tot[1], d.p);
+      if (threadIdx.x == 0) {  // (u.done: the robot is at the cap; src is d.ctl)
+        if (u.stop >= 0) d.ctl[L.l].tcg_stop = u.stop;
+        d.ctl[L.l].phase = PH_STEP;
+      }
+    }
+  }
 }
 
 // End of a round: X <- Xt where the step was accepted, and the owned public
@@ -2440,6 +2520,14 @@ __global__ __launch_bounds__(BLOCK, LB<R>::w) void k_cost(Dev d, const Ctl* src)
 template <int R>
 __global__ __launch_bounds__(BLOCK) void k_commit(Dev d, int fold, int final) {
   body_commit<R>(d, fold, final);
+}
+// The consumer form's k_update of the host's launch tcg_max - 1 (body_update's
+// LAST). A kernel of its own name, defined after the others: k_update<R, RM>
+// keeps its symbol, its registers and its place in the code object.
+template <int R>
+__global__ __launch_bounds__(BLOCK) void k_update_last(Dev d, HostStatus* hs, unsigned long long seq, int slot) {
+  KMX_SMEM;
+  body_update<R, RM_CONSUMER, true>(d, hs, seq, slot, smem);
 }
 
 // ------------------------------------------------- round begin + GNC-TLS ---
@@ -3022,6 +3110,11 @@ struct kmx_pgo {
   // stopped 0.691 / 0.691 — the state's round trip costs a gated launch less
   // than a skipped launch's record fetch costs the round.
   bool hess_gate = true;
+  // The consumer form's round tail (KMX_TCG_TAIL=0: off): the k_update at the
+  // step cap forms the trial point and k_cost takes its stop decision, so the
+  // chain has no k_retract (tail_fused). Off: the parent's launches, the
+  // in-build bitwise reference and the A/B cell.
+  bool tcg_tail = true;
   // (measured and removed: a hipStreamQuery before the status spin put a ~5 us
   // bubble before the next tCG step's first kernel, profiles/r02/ab_query)
   // reduction mode: set per graph (below) unless KMX_RED forces one (0 launch,
@@ -3350,8 +3443,9 @@ void tcg_polled(const kmx_pgo* h, kmx_pgo::Group& st, bool poll, int steps) {
 // first tCG step after it; profiles/r02/small_round/2_*) and not kept.
 // RM_CONSUMER folds the round's other reductions into the kernel after them
 // (no k_reduce launch in a round): the gradient's into the first k_hess, the
-// last tCG update's into k_retract, the trial cost's into k_commit (one RTR
-// iteration). RGD keeps the gradient's launch (no k_hess follows).
+// last tCG update's into k_cost (tail_fused; k_retract with KMX_TCG_TAIL=0),
+// the trial cost's into k_commit (one RTR iteration). RGD keeps the
+// gradient's launch (no k_hess follows).
 template <int RM>
 bool fold_grad(const kmx_pgo* h) {
   return RM == RM_CONSUMER && h->P.method != KMX_METHOD_RGD && h->P.tcg_max_iterations > 0;
@@ -3359,6 +3453,18 @@ bool fold_grad(const kmx_pgo* h) {
 template <int RM>
 bool fold_cost(const kmx_pgo* h) {
   return RM == RM_CONSUMER && (h->P.rtr_iterations == 1 || h->P.method == KMX_METHOD_RGD);
+}
+// The consumer form's standard tCG without k_retract: the k_update of launch
+// tcg_max - 1 (k_update_last) forms the trial point of the robots at the step
+// cap and k_cost takes their stop decision; a robot that stopped earlier got
+// its trial point from the k_update behind the k_hess that stopped it. A
+// chain is then 1 + 2 steps + 2 launches: gradient, steps, cost, commit.
+// Not RGD (its step is k_retract's), not the one-sync form (k_step retracts);
+// KMX_TCG_TAIL=0 keeps k_retract's fold 2 and an ordinary last k_update.
+template <int RM>
+bool tail_fused(const kmx_pgo* h) {
+  return RM == RM_CONSUMER && h->tcg_tail && h->P.method != KMX_METHOD_RGD && !onesync(h) &&
+         h->P.tcg_max_iterations > 0;
 }
 
 // One k_hess launch. fl: bit 0, the host's launch 0 of a tCG loop; bit 1,
@@ -3421,8 +3527,13 @@ void enqueue_tcg_t(kmx_pgo* h, const Chain* q, int G, bool* stopped) {
       if constexpr (cons) {
         // k_hess reports the stop test of the previous step's update
         launch_hess<R, RW, RM>(h, grid, q[g].s, q[g].d, fl, t.slot, hs, seq[g], t.e0, t.e1);
-        hipLaunchKernelGGL((k_update<R, RM>), grid, blk, SmemU::bytes, q[g].s, q[g].d, (HostStatus*)nullptr, 0ull,
-                           t.slot);
+        // the update at the step cap also forms the trial point (tail_fused)
+        if (j == tmax - 1 && tail_fused<RM>(h))
+          hipLaunchKernelGGL((k_update_last<R>), grid, blk, SmemU::bytes, q[g].s, q[g].d, (HostStatus*)nullptr, 0ull,
+                             t.slot);
+        else
+          hipLaunchKernelGGL((k_update<R, RM>), grid, blk, SmemU::bytes, q[g].s, q[g].d, (HostStatus*)nullptr, 0ull,
+                             t.slot);
       } else {
         launch_hess<R, RW, RM>(h, grid, q[g].s, q[g].d, fl, t.slot, nullptr, 0ull, t.e0, t.e1);
         red<R>(q[g], RED_HESS, nullptr, 0, t.slot);
@@ -3483,9 +3594,10 @@ void enqueue_tcg_onesync_t(kmx_pgo* h, const Chain& q) {
 
 // One round over G >= 1 launch chains (groups_in_effect), all of form RM.
 // k_begin on the handle's stream; then per chain, on its stream, k_grad, the
-// tCG loop, k_retract, k_cost and the non-final k_commit over the chain's
-// tiles; then the final k_commit of all robots on the handle's stream (it
-// writes the public rows the other chains' k_grad / k_cost read).
+// tCG loop, k_retract (none where tail_fused), k_cost and the non-final
+// k_commit over the chain's tiles; then the final k_commit of all robots on
+// the handle's stream (it writes the public rows the other chains' k_grad /
+// k_cost read).
 // G = 1 is kmx_pgo::all on the handle's stream: no event, no wait. G > 1 are
 // the robot groups, group g > 0 on a stream of its own. Fork: the begin
 // launch's own completion is the event the side streams wait for. Join: each
@@ -3534,10 +3646,12 @@ void enqueue_round_t(kmx_pgo* h, const unsigned char* d_active, int G) {
       const bool last = it + 1 == iters;
       hipEvent_t join = g > 0 && last ? h->ev_join[g - 1] : nullptr;
       // consumer tCG: the k_update after the k_hess that stopped a robot
-      // formed its trial point; k_retract (fold 2) reduces the last update,
-      // decides and retracts the robots still in tCG at the cap, and is not
-      // needed when the polled loop saw the chain's robots stop
-      if (!os && !(cons && stopped[g]))
+      // formed its trial point, and the one at the step cap that of the
+      // robots still in tCG there (tail_fused): no k_retract. With
+      // KMX_TCG_TAIL=0 k_retract (fold 2) reduces the last update, decides and
+      // retracts the robots at the cap, and is not needed when the polled
+      // loop saw the chain's robots stop
+      if (!os && !(cons && stopped[g]) && !tail_fused<RM>(h))
         hipLaunchKernelGGL((k_retract<R>), grid, blk, SmemU::bytes, q[g].s, q[g].d, cons && !rgd ? 2 : 0,
                            (const Ctl*)h->d_ctl);
       if (fcost && join)  // the side stream's last dispatch: the join event completes with it
@@ -3655,6 +3769,7 @@ extern "C" int kmx_pgo_create(const kmx_pgo_params* params, int device, kmx_pgo*
   }
   if (const char* v = std::getenv("KMX_HESS_DECIDE")) h->decide_forced = std::atoi(v) != 0 ? 1 : 0;
   if (const char* v = std::getenv("KMX_HESS_GATE")) h->hess_gate = std::atoi(v) != 0;
+  if (const char* v = std::getenv("KMX_TCG_TAIL")) h->tcg_tail = std::atoi(v) != 0;
   if (const char* v = std::getenv("KMX_TCG_GROUPS")) {
     const int g = std::atoi(v);
     h->groups_req = g >= 4 ? 4 : g >= 2 ? 2 : 1;
