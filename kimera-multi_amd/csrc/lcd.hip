@@ -3054,11 +3054,13 @@ __device__ __forceinline__ void rs_replay_c(int c, int lane, const int* Kin, con
 // Each candidate's result from its replayed loop: one workgroup of RS_FIN
 // waves per candidate. Wave 0 runs ransac_tail<true>; the 1-point
 // recovery's largest consistent set — n3^2 distance tests over the 2D-2D
-// inliers, the tail's longest loop on a lone wave — is counted by every wave:
-// wave v takes the 64 inliers i of block v % n_ib against the j of range
-// v / n_ib, adds its integer counts into LDS (any order: the same counts), and
-// wave 0 then takes the first maximum over the valid i (the serial loop's
-// pick). Waves 1.. wait at the first barrier and leave when wave 0 reached no
+// inliers, the tail's longest loop on a lone wave — is counted by every wave.
+// Up to RS_FIN blocks of 64 inliers i (n3 <= 512): wave v takes block
+// v % n_ib against the j of range v / n_ib (RS_FIN / n_ib ranges; waves past
+// n_ib * n_jc idle). More blocks than waves (n3 up to MAX_FEATS: 9..16):
+// wave v takes blocks v, v + RS_FIN, .. against every j. Each wave adds its
+// integer counts into LDS (any order: the same counts), and wave 0 then takes
+// the first maximum over the valid i (the serial loop's pick). Waves 1.. wait at the first barrier and leave when wave 0 reached no
 // count (`fin_go` < 0: no model, too few inliers, no recovery stage, PnP).
 // `skip` (the speculative finish of a spread call): the range's `more` word;
 // set, the candidates are not done and the workgroup leaves at once.
@@ -3068,30 +3070,33 @@ __device__ __forceinline__ void fin_count(const double* Tl, const unsigned char*
   const int n_ib = (n3 + RS_BLOCK - 1) / RS_BLOCK;
   if (n_ib == 0) return;
   const int n_jc = max(1, RS_FIN / n_ib);
-  const int ib = wave % n_ib, jc = wave / n_ib;
+  const int jc = wave / n_ib;
   if (jc >= n_jc) return;
   const int n3p = (n3 + 3) & ~3;  // entries n3 .. n3 + 3 are invalid padding
   const int jlen = (((n3p + n_jc - 1) / n_jc) + 3) & ~3;
   const int j0 = jc * jlen, j1 = min(n3p, j0 + jlen);
-  const int i = ib * RS_BLOCK + lane;
-  double ti[3] = {0.0, 0.0, 0.0};
-  if (i < n3)
-    for (int k = 0; k < 3; ++k) ti[k] = Tl[3 * i + k];
-  int c4[4] = {0, 0, 0, 0};
-  for (int j = j0; j < j1; j += 4) {
-    const unsigned v4 = *reinterpret_cast<const unsigned*>(vl + j);
-    // branch-free (a valid-byte test as a branch serialised the four chains)
-    double d2[4];
+  // (n_ib <= RS_FIN: one pass, block wave % n_ib; else n_jc = 1 and wave < n_ib)
+  for (int ib = wave % n_ib; ib < n_ib; ib += RS_FIN) {
+    const int i = ib * RS_BLOCK + lane;
+    double ti[3] = {0.0, 0.0, 0.0};
+    if (i < n3)
+      for (int k = 0; k < 3; ++k) ti[k] = Tl[3 * i + k];
+    int c4[4] = {0, 0, 0, 0};
+    for (int j = j0; j < j1; j += 4) {
+      const unsigned v4 = *reinterpret_cast<const unsigned*>(vl + j);
+      // branch-free (a valid-byte test as a branch serialised the four chains)
+      double d2[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const double* t = Tl + 3 * (j + u);
-      const double dx = t[0] - ti[0], dy = t[1] - ti[1], dz = t[2] - ti[2];
-      d2[u] = dx * dx + dy * dy + dz * dz;
+      for (int u = 0; u < 4; ++u) {
+        const double* t = Tl + 3 * (j + u);
+        const double dx = t[0] - ti[0], dy = t[1] - ti[1], dz = t[2] - ti[2];
+        d2[u] = dx * dx + dy * dy + dz * dz;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) c4[u] += (int)((v4 >> (8 * u)) & 1u) & (d2[u] < thr2 ? 1 : 0);
     }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) c4[u] += (int)((v4 >> (8 * u)) & 1u) & (d2[u] < thr2 ? 1 : 0);
+    if (i < n3 && j0 < j1) atomicAdd(cnt + i, (c4[0] + c4[1]) + (c4[2] + c4[3]));
   }
-  if (i < n3 && j0 < j1) atomicAdd(cnt + i, (c4[0] + c4[1]) + (c4[2] + c4[3]));
 }
 __global__ __launch_bounds__(RS_BLOCK * RS_FIN) void k_rs_finish(const double* bearings, const double* points, int N,
                                                                  const int* cq, const int* cm, const int2* pairs,

@@ -130,7 +130,10 @@ def test_spread_max_feats_1024_and_refine_off(gpu, monkeypatch, refine):
     staging then needs 75 KB of LDS: the launch raises the dynamic limit) and
     ragged frames, with refine_pose on and off (the recovery sums T_j itself,
     or re-forms it from the staged points): bit-exact against the
-    restatement."""
+    restatement. The largest recovery here has exactly 512 entries (the
+    planted pair: n_matches 716, mono_inliers 512), the last size at which
+    k_rs_finish has a wave per block of 64; sizes above 512 are in
+    tests/test_lcd_recover_gpu.py."""
     from oracle import oracle as O
     pool = make_lcd_pool(20, 1024, seed=6)
     pool.n_feats = np.array([1024, 1024, 0, 300, 4, 300, 5, 300, 9, 9, 10, 300, 300, 0, 700, 700, 1, 1, 64, 1024],
