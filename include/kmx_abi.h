@@ -105,7 +105,15 @@ typedef struct kmx_pgo_params {
 } kmx_pgo_params;
 
 /* Per-robot statistics of one RBCD round (what dpgo logs to dpgo_log_*.csv via
- * logIteration, drawio:2136-2142). */
+ * logIteration, drawio:2136-2142).
+ * A block update runs rtr_iterations RTR iterations; one whose gradient norm is
+ * below gradnorm_tol is skipped and ends the block update (tcg_stop =
+ * KMX_TCG_SKIPPED, tcg_iterations = 0, accepted = 0). rho and radius are those
+ * of the last RTR step that was taken in this block update, also when a later
+ * iteration was skipped; when the first iteration is skipped no step was
+ * taken: rho = 0 and radius = rtr_initial_radius (likewise for RGD, which has
+ * no trust region). rel_change is over the whole block update, whatever the
+ * number of iterations. */
 typedef struct kmx_iter_stats {
   int updated;          /* 1 if this robot executed a block update this round  */
   int tcg_iterations;   /* inner iterations of the last RTR iteration          */
@@ -279,7 +287,10 @@ int kmx_pgo_iterate(kmx_pgo* h, const uint8_t* active, kmx_iter_stats* stats);
  * host synchronisation; used by the benchmark. stats are not produced. When
  * refresh_local != 0 the owned public rows are published before the first
  * round (every round republishes the rows it commits): the single-device
- * exchange; otherwise the caller exchanges between rounds. */
+ * exchange; otherwise the caller exchanges between rounds. With
+ * rtr_iterations > 1 the rows are republished once, at the end of the block
+ * update, for every robot one of whose RTR iterations moved its poses, also
+ * when its last iteration was rejected or skipped. */
 int kmx_pgo_iterate_async(kmx_pgo* h, int rounds, int refresh_local);
 /* Acceleration (kmx_pgo_params.acceleration = 1, concurrent schedule only):
  * each round first forms the extrapolated point Y = Proj((1 - alpha) X +

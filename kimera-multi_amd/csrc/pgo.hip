@@ -2433,7 +2433,9 @@ __device__ __forceinline__ void body_cost(const Dev& d, const Ctl* src, char* sm
 // final = 0: between two RTR iterations of one block update — the accepted
 // trial point becomes the iterate the next iteration starts from, but the
 // public rows (the neighbours' snapshot of this round) and the round counters
-// wait for the block update's end.
+// wait for the block update's end. The final commit then publishes every
+// robot that moved in this block update, whether or not its last iteration
+// committed.
 template <int R>
 __device__ __forceinline__ void body_commit(const Dev& d, int fold, int final) {
   const Lane L = lane_map<R>(d);
@@ -2470,7 +2472,22 @@ __device__ __forceinline__ void body_commit(const Dev& d, int fold, int final) {
       d.ctl[L.l] = cs;
     }
   } else {
-    commit = d.ctl[L.l].commit != 0;
+    const Ctl& c = d.ctl[L.l];
+    commit = c.commit != 0;
+    // Several RTR iterations: a robot whose last iteration was rejected or
+    // skipped has nothing to commit, but an earlier iteration of this block
+    // update may have moved X (chg_acc > 0; the non-final commits leave the
+    // public table alone): its rows are published from X here. With one
+    // iteration chg_acc > 0 only where commit is set.
+    if (final && !commit && c.chg_acc > 0.0 && L.valid) {
+      const int s = d.pose_slot[L.pose];
+      if (s >= 0) {
+        const size_t o = (size_t)L.pose * 4 * R + 4 * L.a;
+        double v[4];
+        load4(d.X + o, v);
+        store4(d.pub + (size_t)s * 4 * R + 4 * L.a, v);
+      }
+    }
   }
   if (!commit || !L.valid) return;
   const size_t o = (size_t)L.pose * 4 * R + 4 * L.a;
@@ -2528,6 +2545,38 @@ template <int R>
 __global__ __launch_bounds__(BLOCK) void k_update_last(Dev d, HostStatus* hs, unsigned long long seq, int slot) {
   KMX_SMEM;
   body_update<R, RM_CONSUMER, true>(d, hs, seq, slot, smem);
+}
+
+// Several RTR iterations per block update: the RTR state sums the squared
+// lengths of the accepted steps (chg_acc), which is the block update's change
+// only when there is one step. After the final k_commit this kernel, one
+// workgroup per robot, takes ||X - X0||^2 over the robot's rows against the
+// round's start X0 and writes dpgo's relativeChange of the whole block update
+// into the robot's state and its team status. A fixed summation order: equal
+// bits in every form of the round.
+__global__ __launch_bounds__(BLOCK) void k_change(Dev d, const double* X0, int ps) {
+  const int l = blockIdx.x;
+  const int t0 = d.rtile0[l], t1 = d.rtile0[l + 1];
+  if (t0 == t1 || !d.ctl[l].updated) return;  // no poses, or not active this round
+  const long long n = (long long)d.n_robot[l] * ps;
+  const size_t o = (size_t)d.tile[t0].p0 * ps;
+  double s = 0.0;
+  for (long long i = threadIdx.x; i < n; i += BLOCK) {
+    const double dd = d.X[o + i] - X0[o + i];
+    s += dd * dd;
+  }
+  __shared__ double ws[WAVES];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) t += ws[w];
+    const double rel = sqrt(t / (double)d.n_robot[l]);
+    d.ctl[l].rel_change = rel;
+    d.relc[l] = rel;
+  }
 }
 
 // ------------------------------------------------- round begin + GNC-TLS ---
@@ -3140,6 +3189,9 @@ struct kmx_pgo {
   // Nesterov acceleration (P.acceleration): momentum V and this round's Y
   // (allocated only when enabled), gamma and the restart counter on the host
   double *d_accV = nullptr, *d_accY = nullptr;
+  // X at the start of the round, kept when a block update runs several RTR
+  // iterations (k_change: its relative change is against this point)
+  double* d_X0 = nullptr;
   double acc_gamma = 0.0;
   int acc_k = 0;
   bool acc_ready = false, acc_started = false;
@@ -3221,7 +3273,8 @@ void free_dev(kmx_pgo* h) {
            h->d_vec, h->d_S, h->d_Pinv, h->d_hD, h->d_hDS, h->d_pub, h->d_part, h->d_ctl, h->d_cnt, h->d_m_robot,
            h->d_n_robot, h->d_pub_src, h->d_own_src, h->d_pose_slot, h->d_gnc_edge, h->d_gnc_ends, h->d_sh_edge,
            h->d_sh_idx, h->d_osh_edge, h->d_osh_idx, h->d_relc, h->d_gnc, h->d_ext, h->d_active, h->d_scratch,
-           h->d_hv_launch, h->d_accV, h->d_accY, h->d_ctl2, h->d_part_h, h->d_part_u, h->d_coefh, h->d_part_f);
+           h->d_hv_launch, h->d_accV, h->d_accY, h->d_ctl2, h->d_part_h, h->d_part_u, h->d_coefh, h->d_part_f,
+           h->d_X0);
   h->ext_cap = 0;
   h->scratch_cap = 0;
 }
@@ -3262,6 +3315,8 @@ bool ready(kmx_pgo* h) { return h && h->d_vec != nullptr; }
 bool onesync(const kmx_pgo* h) {
   return h->P.tcg_form == KMX_TCG_FORM_ONESYNC && h->P.method == KMX_METHOD_RTR;
 }
+// Several RTR iterations per block update (RGD runs one step whatever rtr_iterations says)
+bool multi_rtr(const kmx_pgo* h) { return h->P.method == KMX_METHOD_RTR && h->P.rtr_iterations > 1; }
 int dh_count(const kmx_pgo* h) {
   return std::max(onesync(h) ? 2 : 1, std::min(h->P.tcg_max_iterations, DHMAX));
 }
@@ -3615,6 +3670,10 @@ void enqueue_round_t(kmx_pgo* h, const unsigned char* d_active, int G) {
   const dim3 blk(BLOCK);
   // one chain only (groups_in_effect): the RGD step and the one-sync tCG
   const bool rgd = h->P.method == KMX_METHOD_RGD, os = cons && onesync(h);
+  // the round's start for k_change (on the handle's stream, ahead of the begin
+  // launch the side streams wait for)
+  if (multi_rtr(h))
+    (void)hipMemcpyAsync(h->d_X0, h->dv.X, sizeof(double) * (size_t)h->dv.vec, hipMemcpyDeviceToDevice, h->stream);
   // the round's first k_grad runs the gated preconditioner rebuild (there is
   // one: set_graph refuses a graph without tiles)
   const bool pend = enqueue_begin(h, d_active, BEGIN_ROUND, true, G > 1 ? h->ev_fork : nullptr);
@@ -3665,6 +3724,8 @@ void enqueue_round_t(kmx_pgo* h, const unsigned char* d_active, int G) {
   }
   for (int g = 1; g < G; ++g) (void)hipStreamWaitEvent(h->stream, h->ev_join[g - 1], 0);
   hipLaunchKernelGGL((k_commit<R>), dim3(h->ntiles), blk, 0, h->stream, h->dv, fcost ? 1 : 0, 1);
+  if (multi_rtr(h))
+    hipLaunchKernelGGL(k_change, dim3(h->dv.L), blk, 0, h->stream, h->dv, (const double*)h->d_X0, 4 * R);
 }
 
 // One RBCD round for the robots whose d_active flag is set; it starts with
@@ -4173,6 +4234,7 @@ extern "C" int kmx_pgo_set_graph(kmx_pgo* h, int n_robots, const int32_t* n_pose
       (rc = dalloc(&h->d_hDS, (size_t)std::max(nloc, 1) * SYM4)) ||
       (rc = dalloc(&h->d_pub, (size_t)std::max<int64_t>(h->npub, 1) * ps)) ||
       (h->P.acceleration && ((rc = dalloc(&h->d_accV, vec)) || (rc = dalloc(&h->d_accY, vec)))) ||
+      (multi_rtr(h) && (rc = dalloc(&h->d_X0, vec))) ||
       (rc = dalloc(&h->d_part, (size_t)h->ntiles * NPART)) || (rc = dalloc(&h->d_ctl, L)) ||
       (rc = dalloc(&h->d_ctl2, L)) || (rc = dalloc(&h->d_part_h, (size_t)h->ntiles * 2)) ||
       (rc = dalloc(&h->d_part_u, (size_t)h->ntiles * 2)) ||

@@ -645,6 +645,7 @@ static void block_update(orc_pgo* h, int a, kmx_iter_stats* st, int inner) {
   st->updated = 1;
   st->edges = h->nredges[a];
   double Delta = h->P.rtr_initial_radius;
+  st->radius = Delta; /* no RTR step taken (skipped at once, or RGD): the initial radius, rho 0 */
   if (h->P.method == KMX_METHOD_RGD) {
     /* dpgo QuadraticOptimizer::gradientDescent (ROptMethod RGD) [U: dpgo not vendored]:
      * X <- Retr_X(-s * precon(rgrad)), always accepted; the same gradient-norm skip as RTR */

@@ -15,6 +15,7 @@ from kmx.dpgo.params import PGOAgentParameters, RobustCostType
 from kmx.dpgo.solver import BlockSolver
 from kmx.synth import lift, lifting_matrix, make_pose_graph
 from kmx.synth.pose_graph import _expm_so3
+from tests.rtr_cases import RHO_TOL
 
 pytestmark = pytest.mark.gpu
 
@@ -54,7 +55,8 @@ def _full_records(g):
     return g
 
 
-@pytest.mark.parametrize("r,records", [(3, "compact"), (5, "compact"), (8, "compact"), (5, "full")])
+@pytest.mark.parametrize("r,records", [(3, "compact"), (5, "compact"), (6, "compact"), (7, "compact"), (8, "compact"),
+                                       (5, "full")])
 def test_primitives_match_oracle(gpu, r, records):
     g, P, X0 = _setup(r=r)
     if records == "full":
@@ -167,7 +169,7 @@ def test_rounds_match_oracle(gpu, robust, records):
             assert np.abs(wg - wo).max() <= 1e-9, np.abs(wg - wo).max()
 
 
-@pytest.mark.parametrize("r", [3, 4, 8])
+@pytest.mark.parametrize("r", [3, 4, 7, 8])
 def test_rounds_match_oracle_rank(gpu, r):
     """The incidence-parallel kernels (and their LDS layouts: chunk of TP*r
     incidences, 64 // r poses per wave) at other relaxation ranks, GNC on."""
@@ -411,6 +413,9 @@ def test_round_structure_matches_oracle(gpu, monkeypatch, red, case):
         for a in range(g.n_robots):
             assert sg[a]["tcg_iterations"] == so[a]["tcg_iterations"], (it, a, sg[a], so[a])
             assert sg[a]["accepted"] == so[a]["accepted"], (it, a)
+            # the radius is a start value times 0.25, 2 and fmin: exact; rho to rtr_cases.RHO_TOL
+            assert sg[a]["radius"] == so[a]["radius"], (it, a, sg[a], so[a])
+            assert abs(sg[a]["rho"] - so[a]["rho"]) <= RHO_TOL * max(1.0, abs(so[a]["rho"])), (it, a, sg[a], so[a])
             d = np.linalg.norm((s.get_iterate(a) - o.get_iterate(a)).reshape(-1, 4 * P.r), axis=1).max()
             assert d <= 1e-6, (it, a, d)
     s.iterate_async(3, refresh_local=True)

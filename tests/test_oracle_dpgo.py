@@ -14,6 +14,7 @@ from kmx.dpgo.params import PGOAgentParameters, RobustCostType
 from kmx.synth import lift, lifting_matrix, make_pose_graph
 from kmx.synth.pose_graph import _expm_so3
 from oracle.oracle import OraclePGO
+from tests.rtr_ref import numpy_block
 
 
 def _problem(seed=0, r=5, robots=3, n=240, m=700, weights=True):
@@ -32,35 +33,6 @@ def _problem(seed=0, r=5, robots=3, n=240, m=700, weights=True):
         o.set_iterate(a, X[a])
     o.refresh()
     return g, P, o, X
-
-
-def numpy_block(g, X, a, V=None, hess=False):
-    """Independent restatement: f = 1/2 sum_e w(k|Y_j - Y_i R|^2 + t|p_j - p_i - Y_i t|^2)."""
-    off = np.concatenate([[0], np.cumsum(g.n_poses)])
-    allX = np.concatenate([X[b] for b in range(g.n_robots)])
-    Vb = X[a] if V is None else V
-    sel = (g.r1 == a) | (g.r2 == a)
-    e = np.nonzero(sel)[0]
-    gi, gj = off[g.r1[e]] + g.p1[e], off[g.r2[e]] + g.p2[e]
-    Xi, Xj = allX[gi].copy(), allX[gj].copy()
-    ti, tj = g.r1[e] == a, g.r2[e] == a
-    Xi[ti] = Vb[g.p1[e][ti]]
-    Xj[tj] = Vb[g.p2[e][tj]]
-    if hess:
-        Xi[~ti] = 0.0
-        Xj[~tj] = 0.0
-    wk = (g.weight * g.kappa)[e][:, None, None]
-    wt = (g.weight * g.tau)[e][:, None]
-    ER = Xj[:, :, :3] - Xi[:, :, :3] @ g.R[e]
-    Et = Xj[:, :, 3] - Xi[:, :, 3] - np.einsum("nac,nc->na", Xi[:, :, :3], g.t[e])
-    cost = 0.5 * (np.sum(wk * ER ** 2) + np.sum(wt * Et ** 2))
-    G = np.zeros_like(Vb)
-    np.add.at(G, (g.p2[e][tj], slice(None), slice(0, 3)), (wk * ER)[tj])
-    np.add.at(G, (g.p2[e][tj], slice(None), 3), (wt * Et)[tj])
-    gi_Y = -(wk * np.einsum("nac,nkc->nak", ER, g.R[e])) - (wt * Et)[:, :, None] * g.t[e][:, None, :]
-    np.add.at(G, (g.p1[e][ti], slice(None), slice(0, 3)), gi_Y[ti])
-    np.add.at(G, (g.p1[e][ti], slice(None), 3), -(wt * Et)[ti])
-    return cost, G
 
 
 def test_cost_grad_hess_vs_numpy():
