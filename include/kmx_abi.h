@@ -992,6 +992,103 @@ int kmx_chordal_solve_robust(kmx_chordal* h, const kmx_chordal_params* p,
  * loop (the first included), [7] 0. KMX_ESTATE before the first robust solve. */
 int kmx_chordal_get_robust_stats(kmx_chordal* h, double* out /* [8] */);
 
+/* ------------------------------------------------------------------------- */
+/* Dual optimality certificate of an RBCD solution (DESIGN.md
+ * 16): the smallest eigenvalue of S(X) = Q - Lambda(X) by Lanczos on the
+ * device. Additive to ABI 10. The graph is the TEAM graph on one device, poses
+ * flattened to 0..n-1 (no blocks: S couples robots). An edge i -> j with
+ * (R, t, kappa, tau, w) contributes, in 4x4 blocks ([rotation | translation]),
+ *   Q_ii += w [[kappa I + tau t t^T, tau t], [tau t^T, tau]]
+ *   Q_jj += w diag(kappa, kappa, kappa, tau)
+ *   Q_ij -= w [[kappa R, tau t], [0^T, tau]],   Q_ji = Q_ij^T,
+ * and Lambda_i = sym(Y_i^T (X Q)_{i,Y}) (3x3 per pose, zero on the translation
+ * entry). X is [n][r][4], the layout of kmx_pgo_get_iterate with the robots
+ * concatenated. X S is half the Riemannian gradient, so |X S|_F measures
+ * stationarity, and X is the global optimum of the rank-r relaxation (and its
+ * rounding the optimal trajectory) when S is positive semidefinite.
+ * Sums are ordered (a pose's records in edge order, a fixed tree per tile of
+ * 64 poses, one wave over the tile partials): two calls give the same bits. */
+typedef struct kmx_cert kmx_cert;
+#define KMX_CERT_UNDECIDED 0 /* max_steps reached (a result, not an error)          */
+#define KMX_CERT_CERTIFIED 1 /* rho <= eta and theta_min - rho >= -eta               */
+#define KMX_CERT_NEGATIVE 2  /* theta_min < -eta: S has an eigenvalue below -eta     */
+typedef struct {
+  double eta;          /* > 0, required: the tolerance of the decision              */
+  int32_t max_steps;   /* 0: 5000                                                   */
+  int32_t test_every;  /* the rule is applied at step counts that are multiples of
+                          it; 0: 10                                                 */
+  int32_t check_every; /* steps enqueued between two host reads; 0: 50. No effect
+                          on the result.                                            */
+  int32_t reserved;    /* 0 */
+  uint64_t seed;       /* of the start vector                                       */
+} kmx_cert_params;
+typedef struct {
+  int32_t decision;    /* KMX_CERT_*                                                */
+  int32_t steps;       /* Lanczos steps the decision was taken on                   */
+  double theta_min, theta_max; /* extreme Ritz values                              */
+  double residual;     /* rho = |beta_k s_k|: |S y - theta_min y| for the Ritz vector y */
+} kmx_cert_result;
+typedef struct {
+  double cost;          /* tr(X Q X^T) (twice kmx_pgo's cost)                       */
+  double trace_lambda;  /* tr Lambda (= cost at a stationary point)                 */
+  double stationarity;  /* |X S|_F                                                  */
+} kmx_cert_point_info;
+int kmx_cert_create(int device, kmx_cert** out);
+int kmx_cert_destroy(kmx_cert* h);
+int kmx_cert_set_stream(kmx_cert* h, void* hip_stream);
+/* Checked on the host before any device call; on failure the handle keeps its
+ * previous graph: KMX_EINVAL for an index out of range, src == dst, a value
+ * that is not finite, kappa or tau <= 0, w < 0. Edges of w == 0 contribute
+ * nothing; parallel edges, poses without edges (a zero row of S) and
+ * n_edges == 0 are legal. R is [n_edges][9] row-major, t [n_edges][3]; weight
+ * NULL: 1. A point set before is dropped. */
+int kmx_cert_set_graph(kmx_cert* h, int32_t n_poses, int64_t n_edges, const int32_t* src, const int32_t* dst,
+                       const double* R, const double* t, const double* kappa, const double* tau,
+                       const double* weight);
+/* New weights for the same edges ([n_edges]; NULL: 1); on KMX_EINVAL the
+ * previous weights stay. A point that is set is evaluated again for them. */
+int kmx_cert_set_weights(kmx_cert* h, const double* weight);
+/* The point X [n][r][4]: forms the symmetric 4x4 D_i - Lambda_i of every pose
+ * on the device. KMX_EINVAL for r outside 3..8 or a value that is not finite,
+ * KMX_ESTATE without a graph; these leave the handle as it was. A HIP failure
+ * (KMX_EHIP) after the upload has begun drops the point that was set: the
+ * device's copy is being overwritten. info_out may be NULL. */
+int kmx_cert_set_point(kmx_cert* h, int32_t r, const double* X, kmx_cert_point_info* info_out);
+/* The loop's own kernels on caller data: Lambda_i (row-major 3x3) and
+ * out = S v. KMX_ESTATE without a point. */
+int kmx_cert_get_lambda(kmx_cert* h, double* out /* [n][9] */);
+int kmx_cert_apply(kmx_cert* h, const double* v_in /* [4n] */, double* out /* [4n] */);
+/* Plain Lanczos on S from the start vector of `seed` (no reorthogonalisation;
+ * the basis is not stored), decided on the host from the coefficients at step
+ * counts that are multiples of test_every; a breakdown (beta at the rounding
+ * level of the tridiagonal) ends it with the rule applied to that prefix.
+ * y_out != NULL: a second pass repeats the steps and accumulates the Ritz
+ * vector of theta_min, normalised. KMX_ESTATE without a point. */
+int kmx_cert_min_eig(kmx_cert* h, const kmx_cert_params* p, kmx_cert_result* res, double* y_out /* [4n] or NULL */);
+/* alpha_j, beta_j of the last kmx_cert_min_eig, the steps the host has read
+ * (*count_out of them; at most `capacity` are written). */
+int kmx_cert_get_coefficients(kmx_cert* h, int32_t capacity, double* alpha_out, double* beta_out,
+                              int32_t* count_out);
+/* Host only: the decision rule on a caller's tridiagonal (alpha [k], beta [k];
+ * beta[k-1] is the norm left after step k). KMX_EINVAL for eta <= 0 or k < 1. */
+int kmx_cert_ritz(int32_t k, const double* alpha, const double* beta, double eta, kmx_cert_result* res);
+/* Host only: the start vector of `seed` before its normalisation:
+ * z = seed + (i+1) 0x9E3779B97F4A7C15, the splitmix64 finaliser, and
+ * u_i = (z >> 11) 2^-52 - 1. */
+int kmx_cert_start_vector(uint64_t seed, int64_t count, double* out);
+/* Device times (ms, HIP events): [0] the last set_point's kernels; of the last
+ * kmx_cert_min_eig (0 before one): [1] the Lanczos steps, an event pair around
+ * each batch's launches with the spans summed, so the time the stream idles
+ * while the host decides is not in it; [2] the vector pass's launches (0 without
+ * y_out); [3] the transfers: both uploads of the start vector, every batch's
+ * read-back of alpha and beta, the upload of s and the download of y.
+ * KMX_ESTATE before the first set_point. */
+int kmx_cert_get_timing(kmx_cert* h, double* ms /* [4] */);
+/* Host times (ms, the host clock) of the last kmx_cert_min_eig: [0] the
+ * decisions (the tridiagonal solver and the rule over all tests), [1] the
+ * whole call, with enqueueing and the waits for the stream. */
+int kmx_cert_get_host_timing(kmx_cert* h, double* ms /* [2] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,27 @@ class ChordalBlockInfo(C.Structure):
                 ("relres_rot", C.c_double * 3), ("relres_trans", C.c_double * 3)]
 
 
+class CertParams(C.Structure):
+    """kmx_cert_params (0 in max_steps / test_every / check_every: the library's default)."""
+    _fields_ = [("eta", C.c_double), ("max_steps", C.c_int32), ("test_every", C.c_int32),
+                ("check_every", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
+class CertResult(C.Structure):
+    """kmx_cert_result."""
+    _fields_ = [("decision", C.c_int32), ("steps", C.c_int32), ("theta_min", C.c_double),
+                ("theta_max", C.c_double), ("residual", C.c_double)]
+
+
+class CertPointInfo(C.Structure):
+    """kmx_cert_point_info."""
+    _fields_ = [("cost", C.c_double), ("trace_lambda", C.c_double), ("stationarity", C.c_double)]
+
+
+KMX_CERT_UNDECIDED, KMX_CERT_CERTIFIED, KMX_CERT_NEGATIVE = 0, 1, 2
+CERT_DECISION = ("UNDECIDED", "CERTIFIED", "NEGATIVE")  # kmx_abi.h KMX_CERT_* in their order
+
+
 class BowDetectParams(C.Structure):
     """kmx_bow_detect_params (LcdParams.yaml:3-12)."""
     _fields_ = [("use_nss", C.c_int32), ("alpha", C.c_double), ("min_nss_factor", C.c_double),
@@ -311,6 +332,20 @@ def lib() -> C.CDLL:
                                       C.POINTER(C.c_uint8), pf64, pf64, pf64, pf64, pf64,
                                       C.POINTER(ChordalBlockInfo), C.POINTER(ChordalRobustInfo)], C.c_int),
         "kmx_chordal_get_robust_stats": ([P, pf64], C.c_int),
+        "kmx_cert_create": ([C.c_int, C.POINTER(P)], C.c_int),
+        "kmx_cert_destroy": ([P], C.c_int),
+        "kmx_cert_set_stream": ([P, P], C.c_int),
+        "kmx_cert_set_graph": ([P, i32, i64, pi32, pi32, pf64, pf64, pf64, pf64, pf64], C.c_int),
+        "kmx_cert_set_weights": ([P, pf64], C.c_int),
+        "kmx_cert_set_point": ([P, i32, pf64, C.POINTER(CertPointInfo)], C.c_int),
+        "kmx_cert_get_lambda": ([P, pf64], C.c_int),
+        "kmx_cert_apply": ([P, pf64, pf64], C.c_int),
+        "kmx_cert_min_eig": ([P, C.POINTER(CertParams), C.POINTER(CertResult), pf64], C.c_int),
+        "kmx_cert_get_coefficients": ([P, i32, pf64, pf64, pi32], C.c_int),
+        "kmx_cert_ritz": ([i32, pf64, pf64, f64, C.POINTER(CertResult)], C.c_int),
+        "kmx_cert_start_vector": ([C.c_uint64, i64, pf64], C.c_int),
+        "kmx_cert_get_timing": ([P, pf64], C.c_int),
+        "kmx_cert_get_host_timing": ([P, pf64], C.c_int),
     })
     for name, (argt, rest) in sig.items():
         if not hasattr(L, name):

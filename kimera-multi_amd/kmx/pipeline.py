@@ -248,7 +248,7 @@ def ate_rmse(g: PoseGraphData, traj: dict, *, anchor_robot: int = 0) -> float:
 
 def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, rank: int = 0, world: int = 1,
                  device: int = 0, rounds: int = 100, verifier=None, solver=None, exchange_device=None,
-                 return_trajectory: bool = False, local_init: str = "odometry") -> dict:
+                 return_trajectory: bool = False, local_init: str = "odometry", certify_eta=None) -> dict:
     """One team run: LCD verification of this rank's candidates (query robot
     in the rank's robot range) -> all_gather of the accepted loop closures ->
     team graph -> global initialisation -> `rounds` concurrent RBCD rounds
@@ -261,9 +261,16 @@ def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, ran
     an L2 method, so outlier loop closures at weight 1 can make it worse than
     the odometry chain) or "robust_chordal_gpu"
     (robust_chordal_initialization_team: GNC-TLS around that solve, decided on
-    the device, which rejects outlier loop closures). Returns stage timings and metrics (identical on every
-    rank)."""
+    the device, which rejects outlier loop closures). certify_eta (one rank
+    only: the team's X must be on one device): the result gets a "certificate"
+    entry, kmx.dpgo.certify.certify_team on the final iterate and the final GNC
+    weights at tolerance certify_eta, and out["dpgo"]["cost"], the solver's
+    cost of that iterate (half the certificate's tr(X Q X^T)). Returns stage
+    timings and metrics (identical on every rank)."""
     import time
+
+    if certify_eta is not None and world > 1:
+        raise ValueError("certify_eta needs world == 1: the team's iterate is not on one rank")
 
     from .dpgo.driver import RBCDDriver, robot_ranges
     from .synth.pose_graph import lift, lifting_matrix
@@ -346,6 +353,30 @@ def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, ran
         lc = g.fixed == 0
         out["dpgo"]["gnc_weight_mean_inlier_lc"] = float(w[lc & ~g.outlier].mean()) if (lc & ~g.outlier).any() else None
         out["dpgo"]["gnc_weight_mean_outlier_lc"] = float(w[lc & g.outlier].mean()) if (lc & g.outlier).any() else None
+    if certify_eta is not None:
+        from .dpgo.certify import certify_team
+        Xs = {a: drv.iterate_of(a) for a in range(g.n_robots)}
+        out["dpgo"]["cost"] = solver_team_cost(drv.solver, g, Xs, w)
+        out["certificate"] = certify_team(g, Xs, w, eta=certify_eta, device=device)
     if hasattr(drv.solver, "close"):
         drv.solver.close()
     return out
+
+
+def solver_team_cost(solver, g: PoseGraphData, X_by_robot: dict, w=None) -> float:
+    """The team's cost f = 1/2 sum_e w_e r_e^2 at X_by_robot as the solver
+    evaluates it: every robot's local cost (its private edges and its shared
+    edges, neighbours at their current iterates) summed, less the shared
+    edges' second count, which is formed here from the same iterates."""
+    from .abi import KMX_EVAL_COST_EGRAD
+    solver.refresh_local()
+    f = sum(solver.eval(a, KMX_EVAL_COST_EGRAD, X_by_robot[a])[1] for a in range(g.n_robots))
+    sh = np.nonzero(g.r1 != g.r2)[0]
+    if sh.size:
+        ws = np.asarray(g.weight if w is None else w, np.float64)[sh]
+        Xi = np.stack([X_by_robot[int(a)][int(p)] for a, p in zip(g.r1[sh], g.p1[sh])])
+        Xj = np.stack([X_by_robot[int(a)][int(p)] for a, p in zip(g.r2[sh], g.p2[sh])])
+        eR = Xj[:, :, :3] - np.einsum("kad,kdc->kac", Xi[:, :, :3], g.R[sh])
+        et = Xj[:, :, 3] - Xi[:, :, 3] - np.einsum("kad,kd->ka", Xi[:, :, :3], g.t[sh])
+        f -= 0.5 * float((ws * (g.kappa[sh] * (eR ** 2).sum((1, 2)) + g.tau[sh] * (et ** 2).sum(1))).sum())
+    return float(f)

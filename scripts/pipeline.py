@@ -32,6 +32,9 @@ def main():
                     help="each robot's initialisation in its own frame: its odometry chain, or the chordal "
                          "relaxation on the device (L2: the intra-robot outliers pull at full weight), or "
                          "that relaxation inside GNC-TLS on the device (rejects them)")
+    ap.add_argument("--certify", type=float, default=None, metavar="ETA",
+                    help="one GPU only: certify the final iterate and weights (lambda_min of the dual certificate "
+                         "matrix by Lanczos on the device) at tolerance ETA; the result gets a 'certificate' entry")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -52,7 +55,7 @@ def main():
     stream = PL.make_lc_stream(g0, a.robots * a.true_per_robot, a.robots * a.false_per_robot, seed=a.seed + 1)
     gen = time.perf_counter() - t0
     out = PL.run_pipeline(g0, stream, bench.params(), LcdParams(), rank=rank, world=world, device=local_rank,
-                          rounds=a.rounds, local_init=a.local_init)
+                          rounds=a.rounds, local_init=a.local_init, certify_eta=a.certify)
     out["config"] = {"workload": f"configs[4]: {a.robots} robots x {a.poses} poses, {g0.m} base edges "
                                  f"(intra-robot loop closures, 20% intra outliers, odometry noise "
                                  f"{a.sigma_r} rad / {a.sigma_t} m), LC stream "
