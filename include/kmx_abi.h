@@ -1088,6 +1088,36 @@ int kmx_cert_get_timing(kmx_cert* h, double* ms /* [4] */);
  * decisions (the tridiagonal solver and the rule over all tests), [1] the
  * whole call, with enqueueing and the waits for the stream. */
 int kmx_cert_get_host_timing(kmx_cert* h, double* ms /* [2] */);
+/* The escape step of the Riemannian staircase, for a point of
+ * rank r that kmx_cert_min_eig found NEGATIVE with the Ritz vector y. For each
+ * alpha[k] the rank-(r+1) candidate [X; alpha[k] y^T] is formed on the device:
+ * every pose's three rotation columns (length r + 1) are re-orthonormalised by
+ * Gram-Schmidt in column order, applied twice (a positive diagonal: the QR
+ * factor), the translation column passes through, and a pose whose new
+ * rotation entries are all zero is copied as it is (alpha = 0 gives [X; 0]
+ * exactly). cost_out[k] = tr(X+ Q X+^T) over the graph with the handle's
+ * current weights, in the ordered sums of kmx_cert_set_point, so one call of 8
+ * and 8 calls of 1 give the same bits. *best_out: the candidate of the lowest
+ * finite cost strictly below the point's own cost (kmx_cert_set_point's, kept
+ * in the handle), ties to the earlier index; -1 when no candidate descends (a
+ * result, not an error). KMX_ESTATE without a point; KMX_EINVAL for n_alpha
+ * outside 1..8 or an alpha or y that is not finite; KMX_EUNSUP for r == 8
+ * (there is no rank 9). These leave the handle as it was. The handle owns the
+ * candidates (n_alpha n (r+1) 32 bytes, grown on demand). */
+int kmx_cert_escape(kmx_cert* h, const double* y /* [4n] */, int32_t n_alpha, const double* alpha /* [n_alpha] */,
+                    double* cost_out /* [n_alpha] */, int32_t* best_out);
+/* Downloads candidate k of the last kmx_cert_escape and makes it the handle's
+ * point at rank r + 1 (kmx_cert_set_point's kernel on the device's copy; no
+ * upload); info_out as kmx_cert_set_point fills it (or NULL). KMX_ESTATE
+ * without a preceding kmx_cert_escape, or when kmx_cert_set_point,
+ * kmx_cert_set_graph, kmx_cert_set_weights or a commit came after it;
+ * KMX_EINVAL for k outside that call's candidates. */
+int kmx_cert_escape_commit(kmx_cert* h, int32_t k, double* X_out /* [n][r+1][4] */,
+                           kmx_cert_point_info* info_out);
+/* Device times (ms, HIP events) of the last kmx_cert_escape (0 before one):
+ * [0] its kernels (lift, cost, the reduction), [1] its transfers (the upload
+ * of y and alpha, the download of the costs). */
+int kmx_cert_get_escape_timing(kmx_cert* h, double* ms /* [2] */);
 
 #ifdef __cplusplus
 }

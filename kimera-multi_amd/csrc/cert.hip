@@ -20,6 +20,12 @@
 // with a fixed shuffle tree, one wave sums the tile partials in a fixed order.
 // No floating-point atomics, no grid barrier, no persistent kernel, no
 // device-side wait.
+//
+// The escape step of the Riemannian staircase lives here too:
+// kmx_cert_escape lifts the point to rank r + 1 along a direction y for up to 8
+// step lengths (k_ct_lift) and evaluates each candidate's cost (k_ct_cost, the
+// candidate on blockIdx.y; k_ct_reduce sums the tile partials of all of them),
+// kmx_cert_escape_commit makes one of them the point without an upload.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -253,6 +259,115 @@ __global__ void k_ct_weights(int64_t nrec, const double* __restrict__ wkt, CtRec
   rec[k].wt = wkt[2 * k + 1];
 }
 
+// The escape step's candidates: candidate blockIdx.y of pose p
+// is [X_p; a y_p^T] (R + 1 rows of 4) with a = alpha[blockIdx.y], its three
+// rotation columns orthonormalised by Gram-Schmidt in column order, every
+// column projected twice against the ones before it and then divided by its
+// norm (a positive diagonal). The translation column passes through. A pose
+// whose new rotation entries are all zero (a = 0, or y_p has none) is copied:
+// its X_p is on the manifold as it stands. cand is [n_alpha][n][R + 1][4].
+template <int R>
+__global__ __launch_bounds__(CT_TILE) void k_ct_lift(int n, const double* __restrict__ X,
+                                                     const double* __restrict__ y,
+                                                     const double* __restrict__ alpha, double* __restrict__ cand) {
+  const int p = blockIdx.x * CT_TILE + (int)threadIdx.x;
+  if (p >= n) return;
+  const double a = alpha[blockIdx.y];
+  double z[R + 1][4];
+#pragma unroll
+  for (int i = 0; i < R; ++i)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) z[i][c] = X[((size_t)p * R + i) * 4 + c];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) z[R][c] = a * y[(size_t)4 * p + c];
+  if (z[R][0] != 0.0 || z[R][1] != 0.0 || z[R][2] != 0.0) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+      for (int pass = 0; pass < 2; ++pass)
+#pragma unroll
+        for (int d = 0; d < c; ++d) {
+          double dot = 0.0;
+#pragma unroll
+          for (int i = 0; i <= R; ++i) dot += z[i][d] * z[i][c];
+#pragma unroll
+          for (int i = 0; i <= R; ++i) z[i][c] -= dot * z[i][d];
+        }
+      double nn = 0.0;
+#pragma unroll
+      for (int i = 0; i <= R; ++i) nn += z[i][c] * z[i][c];
+      const double nrm = sqrt(nn);
+      if (nrm > 0.0) {
+#pragma unroll
+        for (int i = 0; i <= R; ++i) z[i][c] /= nrm;
+      }
+    }
+  }
+  double* out = cand + (((size_t)blockIdx.y * n + p) * (R + 1)) * 4;
+#pragma unroll
+  for (int i = 0; i <= R; ++i)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) out[4 * i + c] = z[i][c];
+}
+
+// The tile partials of tr(Z Q Z^T) = sum_p <Z_p, (Z Q)_p> for candidate
+// blockIdx.y (Z = cand + blockIdx.y n R 4, rank R): D_p and (Z Q)_p from the
+// pose's records as k_ct_point forms them, in the CSR's order.
+// part is [tile][n_alpha], the layout k_ct_reduce sums.
+template <int R>
+__global__ __launch_bounds__(CT_TILE) void k_ct_cost(int n, const int* __restrict__ ptr,
+                                                     const CtRec* __restrict__ rec, const double* __restrict__ cand,
+                                                     double* __restrict__ part) {
+  const int p = blockIdx.x * CT_TILE + (int)threadIdx.x;
+  const double* __restrict__ Z = cand + (size_t)blockIdx.y * n * R * 4;
+  double s = 0.0;
+  if (p < n) {
+    double x[R][4], g[R][4], D[10];
+    for (int a = 0; a < R; ++a)
+      for (int c = 0; c < 4; ++c) {
+        x[a][c] = Z[((size_t)p * R + a) * 4 + c];
+        g[a][c] = 0.0;
+      }
+    for (int k = 0; k < 10; ++k) D[k] = 0.0;
+    const int k1 = ptr[p + 1];
+    for (int k = ptr[p]; k < k1; ++k) {
+      const CtRec e = rec[k];
+      if (e.wk == 0.0 && e.wt == 0.0) continue;
+      const bool tail = (e.other & kmx::CT_TAIL) != 0;
+      const int o = (int)(e.other & 0x7fffffffu);
+      if (tail) {
+        D[0] += e.wk + e.wt * e.t[0] * e.t[0];
+        D[1] += e.wt * e.t[0] * e.t[1];
+        D[2] += e.wt * e.t[0] * e.t[2];
+        D[3] += e.wt * e.t[0];
+        D[4] += e.wk + e.wt * e.t[1] * e.t[1];
+        D[5] += e.wt * e.t[1] * e.t[2];
+        D[6] += e.wt * e.t[1];
+        D[7] += e.wk + e.wt * e.t[2] * e.t[2];
+        D[8] += e.wt * e.t[2];
+        D[9] += e.wt;
+      } else {
+        D[0] += e.wk;
+        D[4] += e.wk;
+        D[7] += e.wk;
+        D[9] += e.wt;
+      }
+      for (int a = 0; a < R; ++a) {
+        double xo[4];
+        for (int c = 0; c < 4; ++c) xo[c] = Z[((size_t)o * R + a) * 4 + c];
+        ct_edge(e, tail, xo, g[a]);
+      }
+    }
+    for (int a = 0; a < R; ++a) {
+      double v[4];
+      ct_sym4(D, x[a], v);
+      for (int c = 0; c < 4; ++c) s += x[a][c] * (g[a][c] + v[c]);
+    }
+  }
+  const double t = ct_wave_sum(s);
+  if (threadIdx.x == 0) part[(size_t)gridDim.y * blockIdx.x + blockIdx.y] = t;
+}
+
 struct CtDev {
   int* ptr = nullptr;
   CtRec* rec = nullptr;
@@ -260,11 +375,15 @@ struct CtDev {
   double* vec[3] = {nullptr, nullptr, nullptr};
   double *y = nullptr, *alpha = nullptr, *B = nullptr, *sv = nullptr;
   int coef_cap = 0;
+  // the escape step: the candidates [n_alpha][n][r + 1][4] (grown on demand), the tile partials
+  // [n_tiles][CT_MAX_ALPHA], and the step lengths [0..7] with the costs [8..15]
+  double *cand = nullptr, *epart = nullptr, *esc = nullptr;
+  size_t cand_cap = 0;
 };
 
 void ct_free(CtDev& d) {
   void* ptrs[] = {d.ptr, d.rec, d.wkt, d.X, d.Dm, d.Lam, d.part, d.scal, d.vec[0], d.vec[1], d.vec[2],
-                  d.y, d.alpha, d.B, d.sv};
+                  d.y, d.alpha, d.B, d.sv, d.cand, d.epart, d.esc};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   d = CtDev();
@@ -279,7 +398,7 @@ int ct_alloc(T** p, size_t count) {
   return KMX_OK;
 }
 
-enum { EV_POINT0, EV_POINT1, EV_A, EV_B, EV_C, EV_D, EV_COUNT };
+enum { EV_POINT0, EV_POINT1, EV_A, EV_B, EV_C, EV_D, EV_COUNT };  // EV_A..EV_D: min_eig's, and escape's
 
 }  // namespace
 
@@ -297,6 +416,11 @@ struct kmx_cert {
   // summed over the batches), and host ms of the decisions and of the whole call (the host clock)
   double ms_lan = 0.0, ms_vec = 0.0, ms_xfer = 0.0, ms_host_rule = 0.0, ms_host_wall = 0.0;
   std::vector<double> alpha, beta;  // the last min_eig's, as far as the host read them
+  // the escape step: the point's cost (set_point's, kept for the choice rule), and the candidates of the last
+  // kmx_cert_escape while they are valid (n_esc > 0: their count, for the point of rank r)
+  double cost = 0.0;
+  int n_esc = 0;
+  double ms_esc = 0.0, ms_esc_xfer = 0.0;  // the last escape's kernels and transfers (HIP events)
 };
 
 namespace {
@@ -460,7 +584,8 @@ extern "C" int kmx_cert_set_graph(kmx_cert* h, int32_t n_poses, int64_t n_edges,
       (rc = ct_alloc(&d.X, n * 32)) || (rc = ct_alloc(&d.Dm, n * 10)) || (rc = ct_alloc(&d.Lam, n * 9)) ||
       (rc = ct_alloc(&d.part, (size_t)3 * g.n_tiles)) || (rc = ct_alloc(&d.scal, 4)) ||
       (rc = ct_alloc(&d.vec[0], 4 * n)) || (rc = ct_alloc(&d.vec[1], 4 * n)) || (rc = ct_alloc(&d.vec[2], 4 * n)) ||
-      (rc = ct_alloc(&d.y, 4 * n))) {
+      (rc = ct_alloc(&d.y, 4 * n)) || (rc = ct_alloc(&d.epart, (size_t)kmx::CT_MAX_ALPHA * g.n_tiles)) ||
+      (rc = ct_alloc(&d.esc, 2 * (size_t)kmx::CT_MAX_ALPHA))) {
     ct_free(d);
     return rc;
   }
@@ -478,6 +603,7 @@ extern "C" int kmx_cert_set_graph(kmx_cert* h, int32_t n_poses, int64_t n_edges,
   h->have_graph = true;
   h->have_point = false;
   h->timed_point = false;
+  h->n_esc = 0;
   h->ms_lan = h->ms_vec = h->ms_xfer = h->ms_host_rule = h->ms_host_wall = 0.0;
   h->alpha.clear();
   h->beta.clear();
@@ -494,9 +620,11 @@ extern "C" int kmx_cert_set_weights(kmx_cert* h, const double* weight) {
     return kmx::fail(KMX_EINVAL, "kmx_cert_set_weights: " + err);
   KMX_HIP(hipSetDevice(h->device));
   KMX_HIP(hipStreamSynchronize(h->stream));
+  h->n_esc = 0;  // the candidates' costs were the old weights'
   if (int rc = ct_upload_weights(h, h->dev, h->g, weight)) return rc;
-  if (h->have_point) {  // D - Lambda follows the weights
+  if (h->have_point) {  // D - Lambda and the point's cost follow the weights
     if (int rc = ct_run_point(h)) return rc;
+    KMX_HIP(hipMemcpyAsync(&h->cost, h->dev.scal, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     KMX_HIP(hipStreamSynchronize(h->stream));
   }
   return KMX_OK;
@@ -518,6 +646,7 @@ extern "C" int kmx_cert_set_point(kmx_cert* h, int32_t r, const double* X, kmx_c
   KMX_HIP(hipMemcpyAsync(d.X, X, cnt * sizeof(double), hipMemcpyHostToDevice, s));
   h->r = r;
   h->have_point = false;  // the device's copy is being replaced
+  h->n_esc = 0;
   KMX_HIP(hipEventRecord(h->ev[EV_POINT0], s));
   if (int rc = ct_run_point(h)) {
     h->r = r_before;
@@ -529,11 +658,122 @@ extern "C" int kmx_cert_set_point(kmx_cert* h, int32_t r, const double* X, kmx_c
   KMX_HIP(hipStreamSynchronize(s));
   h->have_point = true;
   h->timed_point = true;
+  h->cost = sc[0];
   if (info_out) {
     info_out->cost = sc[0];
     info_out->trace_lambda = sc[1];
     info_out->stationarity = std::sqrt(sc[2]);
   }
+  return KMX_OK;
+  KMX_GUARD_END
+}
+
+extern "C" int kmx_cert_escape(kmx_cert* h, const double* y, int32_t n_alpha, const double* alpha, double* cost_out,
+                               int32_t* best_out) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(h && cost_out && best_out, KMX_EINVAL, "null argument");
+  KMX_CHECK(h->have_point, KMX_ESTATE, "kmx_cert_escape before kmx_cert_set_point");
+  const kmx::CertGraph& g = h->g;
+  const size_t N = (size_t)4 * g.n;
+  std::string err;
+  if (kmx::cert_escape_check(n_alpha, alpha, N, y, &err) != KMX_OK)
+    return kmx::fail(KMX_EINVAL, "kmx_cert_escape: " + err);
+  KMX_CHECK(h->r < 8, KMX_EUNSUP, "kmx_cert_escape: the point has rank 8 and there is no rank 9");
+  CtDev& d = h->dev;
+  const int r = h->r;
+  KMX_HIP(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  KMX_HIP(hipStreamSynchronize(s));
+  const size_t need = (size_t)n_alpha * g.n * (size_t)(r + 1) * 4;
+  if (d.cand_cap < need) {  // the last escape's candidates go with the buffer
+    h->n_esc = 0;
+    if (d.cand) (void)hipFree(d.cand);
+    d.cand = nullptr;
+    d.cand_cap = 0;
+    if (int rc = ct_alloc(&d.cand, need)) return rc;
+    d.cand_cap = need;
+  }
+  h->n_esc = 0;  // the buffer is being overwritten
+  h->ms_esc = h->ms_esc_xfer = 0.0;
+  double* d_alpha = d.esc;
+  double* d_cost = d.esc + kmx::CT_MAX_ALPHA;
+  KMX_HIP(hipEventRecord(h->ev[EV_A], s));
+  KMX_HIP(hipMemcpyAsync(d.y, y, N * sizeof(double), hipMemcpyHostToDevice, s));
+  KMX_HIP(hipMemcpyAsync(d_alpha, alpha, (size_t)n_alpha * sizeof(double), hipMemcpyHostToDevice, s));
+  KMX_HIP(hipEventRecord(h->ev[EV_B], s));
+  const dim3 grid(g.n_tiles, n_alpha), wave(CT_TILE);
+#define KMX_CT_ESCAPE(RR)                                                                                  \
+  case RR:                                                                                                 \
+    hipLaunchKernelGGL((k_ct_lift<RR>), grid, wave, 0, s, g.n, d.X, d.y, d_alpha, d.cand);                 \
+    hipLaunchKernelGGL((k_ct_cost<RR + 1>), grid, wave, 0, s, g.n, d.ptr, d.rec, d.cand, d.epart);         \
+    break;
+  switch (r) {
+    KMX_CT_ESCAPE(3)
+    KMX_CT_ESCAPE(4)
+    KMX_CT_ESCAPE(5)
+    KMX_CT_ESCAPE(6)
+    KMX_CT_ESCAPE(7)
+    default:
+      return kmx::fail(KMX_EINVAL, "r outside 3..7");
+  }
+#undef KMX_CT_ESCAPE
+  hipLaunchKernelGGL(k_ct_reduce, dim3(1), dim3(64), 0, s, g.n_tiles, n_alpha, d.epart, d_cost, 0);
+  KMX_HIP(hipGetLastError());
+  KMX_HIP(hipEventRecord(h->ev[EV_C], s));
+  double cost[kmx::CT_MAX_ALPHA];
+  KMX_HIP(hipMemcpyAsync(cost, d_cost, (size_t)n_alpha * sizeof(double), hipMemcpyDeviceToHost, s));
+  KMX_HIP(hipEventRecord(h->ev[EV_D], s));
+  KMX_HIP(hipStreamSynchronize(s));
+  if (int rc = ct_span(h, EV_A, EV_B, &h->ms_esc_xfer)) return rc;
+  if (int rc = ct_span(h, EV_B, EV_C, &h->ms_esc)) return rc;
+  if (int rc = ct_span(h, EV_C, EV_D, &h->ms_esc_xfer)) return rc;
+  for (int32_t k = 0; k < n_alpha; ++k) cost_out[k] = cost[k];
+  *best_out = kmx::cert_escape_choose(n_alpha, cost, h->cost);
+  h->n_esc = n_alpha;
+  return KMX_OK;
+  KMX_GUARD_END
+}
+
+extern "C" int kmx_cert_escape_commit(kmx_cert* h, int32_t k, double* X_out, kmx_cert_point_info* info_out) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(h && X_out, KMX_EINVAL, "null argument");
+  KMX_CHECK(h->have_point && h->n_esc > 0, KMX_ESTATE,
+            "kmx_cert_escape_commit without the candidates of a kmx_cert_escape for this point and these weights");
+  KMX_CHECK(k >= 0 && k < h->n_esc, KMX_EINVAL, "kmx_cert_escape_commit: k outside the last escape's candidates");
+  CtDev& d = h->dev;
+  const int r1 = h->r + 1;
+  const size_t cnt = (size_t)h->g.n * (size_t)r1 * 4;
+  KMX_HIP(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const double* src = d.cand + (size_t)k * cnt;
+  KMX_HIP(hipMemcpyAsync(X_out, src, cnt * sizeof(double), hipMemcpyDeviceToHost, s));
+  h->have_point = false;  // the device's copy is being replaced
+  h->n_esc = 0;
+  KMX_HIP(hipMemcpyAsync(d.X, src, cnt * sizeof(double), hipMemcpyDeviceToDevice, s));
+  h->r = r1;
+  KMX_HIP(hipEventRecord(h->ev[EV_POINT0], s));
+  if (int rc = ct_run_point(h)) return rc;
+  KMX_HIP(hipEventRecord(h->ev[EV_POINT1], s));
+  double sc[3] = {0.0, 0.0, 0.0};
+  KMX_HIP(hipMemcpyAsync(sc, d.scal, sizeof(sc), hipMemcpyDeviceToHost, s));
+  KMX_HIP(hipStreamSynchronize(s));
+  h->have_point = true;
+  h->timed_point = true;
+  h->cost = sc[0];
+  if (info_out) {
+    info_out->cost = sc[0];
+    info_out->trace_lambda = sc[1];
+    info_out->stationarity = std::sqrt(sc[2]);
+  }
+  return KMX_OK;
+  KMX_GUARD_END
+}
+
+extern "C" int kmx_cert_get_escape_timing(kmx_cert* h, double* ms) {
+  KMX_GUARD_BEGIN
+  KMX_CHECK(h && ms, KMX_EINVAL, "null argument");
+  ms[0] = h->ms_esc;
+  ms[1] = h->ms_esc_xfer;
   return KMX_OK;
   KMX_GUARD_END
 }

@@ -2,8 +2,9 @@
 // kmx_cert_set_graph / kmx_cert_set_weights run before any device call, the
 // per-pose incidence CSR they upload, the start vector of the Lanczos
 // iteration, and the tridiagonal eigensolver with the decision rule
-// (kmx_cert_ritz). Plain C++, so `make cert_check` can build it with the host
-// sanitizers (cert_check.cpp).
+// (kmx_cert_ritz), and the argument checks and the choice rule of
+// kmx_cert_escape. Plain C++, so `make cert_check` and `make stair_check` can
+// build it with the host sanitizers (cert_check.cpp, stair_check.cpp).
 #pragma once
 #include <algorithm>
 #include <climits>
@@ -406,6 +407,41 @@ inline int cert_scan_step(CertScan* sc, int j /* step count, 1-based */, const d
     sc->done = true;
   }
   return KMX_OK;
+}
+
+// ---- the escape step of the Riemannian staircase (kmx_cert_escape)
+
+constexpr int32_t CT_MAX_ALPHA = 8;  // candidates per kmx_cert_escape call
+
+// The arguments of kmx_cert_escape: 1..CT_MAX_ALPHA step lengths, all finite,
+// and a finite direction y [ny]. KMX_OK, or KMX_EINVAL with *err set.
+inline int cert_escape_check(int32_t n_alpha, const double* alpha, size_t ny, const double* y, std::string* err) {
+  auto bad = [&](const std::string& s) {
+    if (err) *err = s;
+    return KMX_EINVAL;
+  };
+  if (n_alpha < 1 || n_alpha > CT_MAX_ALPHA)
+    return bad("n_alpha must be in 1.." + std::to_string(CT_MAX_ALPHA) + ", got " + std::to_string(n_alpha));
+  if (!alpha || !y) return bad("null argument");
+  for (int32_t k = 0; k < n_alpha; ++k)
+    if (!std::isfinite(alpha[k])) return bad("alpha not finite (index " + std::to_string(k) + ")");
+  for (size_t i = 0; i < ny; ++i)
+    if (!std::isfinite(y[i])) return bad("y not finite (index " + std::to_string(i) + ")");
+  return KMX_OK;
+}
+
+// The candidate kmx_cert_escape reports: the lowest finite cost strictly below
+// the point's own cost0, ties to the earlier index; -1 when no candidate
+// descends (a cost that is not finite is never chosen, and neither is any
+// candidate when cost0 is not finite).
+inline int32_t cert_escape_choose(int32_t n_alpha, const double* cost, double cost0) {
+  int32_t best = -1;
+  if (!cost || !std::isfinite(cost0)) return best;
+  for (int32_t k = 0; k < n_alpha; ++k) {
+    if (!std::isfinite(cost[k]) || !(cost[k] < cost0)) continue;
+    if (best < 0 || cost[k] < cost[best]) best = k;
+  }
+  return best;
 }
 
 }  // namespace kmx

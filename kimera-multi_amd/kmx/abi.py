@@ -346,6 +346,9 @@ def lib() -> C.CDLL:
         "kmx_cert_start_vector": ([C.c_uint64, i64, pf64], C.c_int),
         "kmx_cert_get_timing": ([P, pf64], C.c_int),
         "kmx_cert_get_host_timing": ([P, pf64], C.c_int),
+        "kmx_cert_escape": ([P, pf64, i32, pf64, pf64, pi32], C.c_int),
+        "kmx_cert_escape_commit": ([P, i32, pf64, C.POINTER(CertPointInfo)], C.c_int),
+        "kmx_cert_get_escape_timing": ([P, pf64], C.c_int),
     })
     for name, (argt, rest) in sig.items():
         if not hasattr(L, name):

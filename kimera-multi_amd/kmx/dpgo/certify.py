@@ -97,6 +97,27 @@ class Certifier:
             raise ValueError("X: not finite")
         return X
 
+    @staticmethod
+    def check_escape(n_poses, r, y, alphas):
+        """escape's arguments -> (y [4n], alphas [k]) as the library gets
+        them: a point of rank 3..7 (there is no rank 9), a finite y [4n] (or
+        [n, 4]) and 1..8 finite step lengths."""
+        if not 3 <= int(r) <= 7:
+            raise ValueError(f"escape: the point's rank must be in 3..7 (set_point first; no rank 9), got {r}")
+        y = np.asarray(y)
+        if y.shape == (n_poses, 4):
+            y = y.reshape(-1)
+        y = _real(y, (4 * n_poses,), "y")
+        if not np.isfinite(y).all():
+            raise ValueError("y: not finite")
+        alphas = np.asarray(alphas)
+        if alphas.ndim != 1 or not 1 <= alphas.shape[0] <= 8:
+            raise ValueError(f"alphas: expected 1..8 step lengths, got shape {alphas.shape}")
+        alphas = _real(alphas, alphas.shape, "alphas")
+        if not np.isfinite(alphas).all():
+            raise ValueError("alphas: not finite")
+        return y, alphas
+
     # ---- the library
     def set_graph(self, n_poses, src, dst, R, t, kappa, tau, weight=None):
         """Poses 0..n_poses-1 (the team, flattened); edges src -> dst with R
@@ -155,6 +176,35 @@ class Certifier:
             out["y"] = y
         return out
 
+    def escape(self, y, alphas) -> dict:
+        """The staircase's escape step on the device (kmx_cert_escape): the
+        cost tr(X+ Q X+^T) of every rank-(r+1) candidate X+ = [X; alpha y^T]
+        (Stiefel blocks re-orthonormalised, as escape_point) -> {"cost": [k],
+        "best": the index of the lowest cost strictly below the point's own,
+        -1 when none descends}."""
+        y, alphas = self.check_escape(self.n, self.r, y, alphas)
+        cost = np.zeros(alphas.shape[0])
+        best = C.c_int32(-1)
+        check(self.L.kmx_cert_escape(self.h, fptr(y), alphas.shape[0], fptr(alphas), fptr(cost), C.byref(best)),
+              "kmx_cert_escape")
+        return {"cost": cost, "best": int(best.value)}
+
+    def escape_commit(self, k: int):
+        """Candidate k of the last escape becomes the handle's point at rank
+        r + 1 (no upload) -> (X+ [n, r + 1, 4], set_point's info)."""
+        X = np.zeros((self.n, self.r + 1, 4))
+        info = abi.CertPointInfo()
+        check(self.L.kmx_cert_escape_commit(self.h, int(k), fptr(X), C.byref(info)), "kmx_cert_escape_commit")
+        self.r += 1
+        return X, {"cost": info.cost, "trace_lambda": info.trace_lambda, "stationarity": info.stationarity}
+
+    def escape_timing(self) -> dict:
+        """Device times (ms, HIP events) of the last escape: its kernels and
+        its transfers."""
+        ms = np.zeros(2)
+        check(self.L.kmx_cert_get_escape_timing(self.h, fptr(ms)), "kmx_cert_get_escape_timing")
+        return {"escape_ms": float(ms[0]), "transfer_ms": float(ms[1])}
+
     def coefficients(self):
         """(alpha [k], beta [k]) of the last min_eig, the steps the host read."""
         cnt = C.c_int32(0)
@@ -211,6 +261,37 @@ def flatten_team(g, X_by_robot):
             raise ValueError(f"X_by_robot[{a}]: expected shape ({n_poses[a]}, r, 4), got {Xa.shape}")
         parts.append(Xa)
     return int(off[-1]), src, dst, np.ascontiguousarray(np.concatenate(parts))
+
+
+def split_team(g, X):
+    """flatten_team's inverse for the point: X [n, r, 4] -> {robot: [n_a, r, 4]}."""
+    n_poses = np.asarray(g.n_poses, np.int64)
+    off = np.concatenate([[0], np.cumsum(n_poses)])
+    X = np.asarray(X, np.float64)
+    if X.ndim != 3 or X.shape[0] != off[-1] or X.shape[2] != 4:
+        raise ValueError(f"X: expected shape ({int(off[-1])}, r, 4), got {X.shape}")
+    return {a: np.ascontiguousarray(X[off[a]:off[a + 1]]) for a in range(int(g.n_robots))}
+
+
+def rounding_lift(X) -> np.ndarray:
+    """The lifting matrix Y [r, 3] to round X [n, r, 4] with
+    (kmx.pipeline.rounded(X, Y)): the three dominant eigenvectors of
+    sum_i Y_i Y_i^T (r x r, on the host), the third's sign chosen so that most
+    Y^T Y_i have a positive determinant. A solution that left the span of the
+    lifting matrix it started from (the staircase's) has no other; for an exact
+    lift X_i = Y0 [R_i | t_i] it spans Y0's columns and gives the same rounded
+    relative trajectory."""
+    X = np.asarray(X, np.float64)
+    if X.ndim != 3 or X.shape[2] != 4 or X.shape[1] < 3:
+        raise ValueError(f"X: expected shape (n, r >= 3, 4), got {X.shape}")
+    Yi = X[:, :, :3]
+    M = np.einsum("nac,nbc->ab", Yi, Yi)
+    _, V = np.linalg.eigh(M)
+    Y = np.ascontiguousarray(V[:, ::-1][:, :3])
+    det = np.linalg.det(np.einsum("ad,nac->ndc", Y, Yi))
+    if (det > 0).sum() < (det < 0).sum():
+        Y[:, 2] = -Y[:, 2]
+    return Y
 
 
 def certify_team(g, X_by_robot, weights=None, *, eta: float, device: int = 0, want_vector: bool = False, **kw) -> dict:

@@ -248,7 +248,8 @@ def ate_rmse(g: PoseGraphData, traj: dict, *, anchor_robot: int = 0) -> float:
 
 def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, rank: int = 0, world: int = 1,
                  device: int = 0, rounds: int = 100, verifier=None, solver=None, exchange_device=None,
-                 return_trajectory: bool = False, local_init: str = "odometry", certify_eta=None) -> dict:
+                 return_trajectory: bool = False, local_init: str = "odometry", certify_eta=None,
+                 staircase_rmax=None, staircase_kw=None) -> dict:
     """One team run: LCD verification of this rank's candidates (query robot
     in the rank's robot range) -> all_gather of the accepted loop closures ->
     team graph -> global initialisation -> `rounds` concurrent RBCD rounds
@@ -265,12 +266,24 @@ def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, ran
     only: the team's X must be on one device): the result gets a "certificate"
     entry, kmx.dpgo.certify.certify_team on the final iterate and the final GNC
     weights at tolerance certify_eta, and out["dpgo"]["cost"], the solver's
-    cost of that iterate (half the certificate's tr(X Q X^T)). Returns stage
-    timings and metrics (identical on every rank)."""
+    cost of that iterate (half the certificate's tr(X Q X^T)). staircase_rmax
+    (needs certify_eta, one rank only): after the rounds the Riemannian
+    staircase (kmx.dpgo.staircase.staircase_team) runs from the final iterate
+    with the final GNC weights fixed, up to rank staircase_rmax, at tolerance
+    certify_eta; the result gets a "staircase" entry (status, r, levels) with
+    "ate_m", the error of the trajectory rounded with the result's own lift
+    (rounding_lift). staircase_kw: staircase_team's grad_tol, stat_tol,
+    max_rounds, alphas and min_eig's keywords (defaults: 1e-6, 1e-3, 200).
+    "certificate" stays the RBCD iterate's. Returns stage timings and metrics
+    (identical on every rank)."""
     import time
 
     if certify_eta is not None and world > 1:
         raise ValueError("certify_eta needs world == 1: the team's iterate is not on one rank")
+    if staircase_rmax is not None and certify_eta is None:
+        raise ValueError("staircase_rmax needs certify_eta: the staircase decides at that tolerance")
+    if staircase_rmax is not None and world > 1:
+        raise ValueError("staircase_rmax needs world == 1: the team's iterate is not on one rank")
 
     from .dpgo.driver import RBCDDriver, robot_ranges
     from .synth.pose_graph import lift, lifting_matrix
@@ -358,6 +371,19 @@ def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, ran
         Xs = {a: drv.iterate_of(a) for a in range(g.n_robots)}
         out["dpgo"]["cost"] = solver_team_cost(drv.solver, g, Xs, w)
         out["certificate"] = certify_team(g, Xs, w, eta=certify_eta, device=device)
+        if staircase_rmax is not None:
+            from .dpgo.staircase import staircase_team
+            kw = dict(grad_tol=1e-6, stat_tol=1e-3, max_rounds=200)
+            kw.update(staircase_kw or {})
+            sc = staircase_team(g, Xs, w, params, eta=certify_eta, r_max=staircase_rmax, device=device, **kw)
+            off = np.concatenate([[0], np.cumsum(np.asarray(g.n_poses, np.int64))])
+            Xf = np.concatenate([sc["X"][a] for a in range(g.n_robots)])
+            Rr, tr = rounded(Xf, sc["lift"])
+            traj = {a: (Rr[off[a]:off[a + 1]], tr[off[a]:off[a + 1]]) for a in range(g.n_robots)}
+            out["staircase"] = {"status": sc["status"], "r": sc["r"], "levels": sc["levels"],
+                                "ate_m": ate_rmse(g, traj)}
+            if return_trajectory:
+                out["staircase"]["trajectory"] = traj
     if hasattr(drv.solver, "close"):
         drv.solver.close()
     return out

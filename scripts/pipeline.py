@@ -35,6 +35,10 @@ def main():
     ap.add_argument("--certify", type=float, default=None, metavar="ETA",
                     help="one GPU only: certify the final iterate and weights (lambda_min of the dual certificate "
                          "matrix by Lanczos on the device) at tolerance ETA; the result gets a 'certificate' entry")
+    ap.add_argument("--staircase", type=int, default=None, metavar="RMAX",
+                    help="with --certify, one GPU only: the Riemannian staircase from the final iterate and weights "
+                         "up to rank RMAX (escape along the certificate's negative direction, re-solve one rank up); "
+                         "the result gets a 'staircase' entry")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -55,7 +59,8 @@ def main():
     stream = PL.make_lc_stream(g0, a.robots * a.true_per_robot, a.robots * a.false_per_robot, seed=a.seed + 1)
     gen = time.perf_counter() - t0
     out = PL.run_pipeline(g0, stream, bench.params(), LcdParams(), rank=rank, world=world, device=local_rank,
-                          rounds=a.rounds, local_init=a.local_init, certify_eta=a.certify)
+                          rounds=a.rounds, local_init=a.local_init, certify_eta=a.certify,
+                          staircase_rmax=a.staircase)
     out["config"] = {"workload": f"configs[4]: {a.robots} robots x {a.poses} poses, {g0.m} base edges "
                                  f"(intra-robot loop closures, 20% intra outliers, odometry noise "
                                  f"{a.sigma_r} rad / {a.sigma_t} m), LC stream "
