@@ -1119,6 +1119,92 @@ int kmx_cert_escape_commit(kmx_cert* h, int32_t k, double* X_out /* [n][r+1][4] 
  * of y and alpha, the download of the costs). */
 int kmx_cert_get_escape_timing(kmx_cert* h, double* ms /* [2] */);
 
+/* ------------------------------------------------------------------------- */
+/* Mesh deformation (Kimera-PGMO's mesh update: embedded deformation,          */
+/* Sumner et al. 2007, interpolation only)                                     */
+/* ------------------------------------------------------------------------- */
+/* [U: Kimera-PGMO is not vendored; restated from the published formulas.]
+ * Additive to ABI 10. A streaming handle: control nodes and mesh vertices are
+ * append-only.
+ *
+ * Control node j: a robot id, a stamp (ns), a rest pose (Rrest_j, g_j) and a
+ * current pose (Rcur_j, p_j). Its correction is the rigid map
+ *   A_j(x) = R_j (x - g_j) + p_j,  R_j = Rcur_j Rrest_j^T.
+ * A node that was never given a current pose has current = rest. Within a
+ * robot, node stamps are non-decreasing across appends.
+ *
+ * Vertex i: a robot id, a stamp s_i and a position v_i (fp32 in and out; all
+ * arithmetic is fp64). Binding: the candidates are the nodes of the vertex's
+ * robot with |s_j - s_i| <= window_ns (both ends inclusive, s_i -+ window_ns
+ * saturating at the int64 limits), ranked by the squared distance
+ *   d^2 = dx dx + dy dy + dz dz,  dx = double(v.x) - g.x, ...
+ * (summed in that order, no contraction), ties to the lower node id. With m
+ * candidates the vertex uses the min(m, k + 1) - 1 nearest and d_max is the
+ * distance of the next one; m == 1 uses that node at weight 1; m == 0 leaves
+ * the vertex unbound. Weights: w_j = (1 - d_j / d_max)^2 divided by their sum
+ * (taken in rank order); when that sum is not > 0 (d_max == 0, or every used
+ * node at d_max) the nearest node alone is used, at weight 1.
+ * Deformation: v_i' = sum_j w_j A_j(v_i) in rank order, rounded to fp32 once;
+ * an unbound vertex is returned as it is. Nodes appended after a vertex was
+ * bound do not affect it until it is bound again. */
+typedef struct kmx_mesh kmx_mesh;
+typedef struct {
+  int32_t k;         /* nodes per vertex, 1..8 (KMX_EUNSUP otherwise) */
+  int32_t n_robots;  /* robot ids are 0..n_robots-1 */
+  int64_t window_ns; /* W >= 0 */
+} kmx_mesh_params;
+typedef struct {
+  int64_t n_nodes, n_vertices;
+  int64_t node_capacity, vertex_capacity; /* device rows allocated */
+  int64_t device_bytes;
+  int32_t k, lds_nodes;           /* lds_nodes: the most node positions one workgroup of the bind kernel stages */
+  int32_t last_bind_blocks;       /* workgroups of the last kmx_mesh_bind ... */
+  int32_t last_bind_global_blocks; /* ... and those of them that read node positions from global memory */
+} kmx_mesh_info_t;
+typedef struct {
+  int64_t n_vertices; /* of the call */
+  int64_t n_unbound;  /* no candidate node: returned unmoved */
+  int64_t n_partial;  /* bound to 1..k-1 nodes */
+  double max_displacement;  /* max |v' - v| over the call's vertices, from the fp32 result */
+  double sum_sq_displacement;
+} kmx_mesh_stats;
+
+int kmx_mesh_create(const kmx_mesh_params* params, int device, kmx_mesh** out);
+int kmx_mesh_destroy(kmx_mesh* h);
+int kmx_mesh_set_stream(kmx_mesh* h, void* hip_stream);
+/* per_robot_nodes / per_robot_vertices: [n_robots], either may be NULL. */
+int kmx_mesh_info(kmx_mesh* h, kmx_mesh_info_t* info, int64_t* per_robot_nodes, int64_t* per_robot_vertices);
+/* Appends n nodes (ids n_nodes ..): robot[n], stamp_ns[n], Rrest[n][3][3] row
+ * major, g[n][3]. KMX_EINVAL for a null array, a robot id out of range, a value
+ * that is not finite or a stamp below its robot's newest; nothing is added then. */
+int kmx_mesh_add_nodes(kmx_mesh* h, int64_t n, const int32_t* robot, const int64_t* stamp_ns,
+                       const double* Rrest, const double* g);
+/* Current poses of nodes [first, first + n): Rcur[n][3][3], p[n][3]; R_j is
+ * formed on the device. KMX_EINVAL for a range outside the nodes or a value
+ * that is not finite (nothing is changed). */
+int kmx_mesh_set_node_poses(kmx_mesh* h, int64_t first, int64_t n, const double* Rcur, const double* p);
+/* Appends n vertices, unbound; *first_id_out (or NULL) gets the first one's id. */
+int kmx_mesh_add_vertices(kmx_mesh* h, int64_t n, const int32_t* robot, const int64_t* stamp_ns,
+                          const float* xyz, int64_t* first_id_out);
+/* Binds vertices [first, first + n) to the nodes present now. */
+int kmx_mesh_bind(kmx_mesh* h, int64_t first, int64_t n);
+/* idx[n][k] (node ids in rank order, -1 beyond count), w[n][k] (0 beyond
+ * count), count[n]; any of the three may be NULL. */
+int kmx_mesh_get_bindings(kmx_mesh* h, int64_t first, int64_t n, int32_t* idx, double* w, int32_t* count);
+/* Deforms vertices [first, first + n) into xyz_out[n][3] (host) and waits.
+ * stats_out (or NULL): reduced in a fixed order (workgroup partials, then one
+ * wave), so identical from run to run. */
+int kmx_mesh_deform(kmx_mesh* h, int64_t first, int64_t n, float* xyz_out, kmx_mesh_stats* stats_out);
+/* The same into device memory dev_xyz_out[n][3] (fp32) on the handle's
+ * stream; enqueues only, kmx_mesh_sync waits. */
+int kmx_mesh_deform_device(kmx_mesh* h, int64_t first, int64_t n, void* dev_xyz_out);
+int kmx_mesh_sync(kmx_mesh* h);
+/* With timing on, bind and deform bracket their kernels with HIP events;
+ * read_timing waits and returns the last bind's and the last deform's device
+ * time in ms (0 for one that has not run since timing was enabled). */
+int kmx_mesh_enable_timing(kmx_mesh* h, int enable);
+int kmx_mesh_read_timing(kmx_mesh* h, double* bind_ms, double* deform_ms);
+
 #ifdef __cplusplus
 }
 #endif

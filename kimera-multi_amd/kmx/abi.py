@@ -190,6 +190,26 @@ assert BOW_RECORD_DTYPE.itemsize == C.sizeof(BowDetectRecord) == 48
 BOW_STATUS = ("NO_MATCHES", "LOW_NSS_FACTOR", "LOW_SCORE", "NO_GROUPS", "FAILED_TEMPORAL_CONSTRAINT", "LOOP_DETECTED")
 BOW_MODE_INTRA, BOW_MODE_INTER = 0, 1
 
+
+
+class MeshParams(C.Structure):
+    """kmx_mesh_params."""
+    _fields_ = [("k", C.c_int32), ("n_robots", C.c_int32), ("window_ns", C.c_int64)]
+
+
+class MeshInfo(C.Structure):
+    """kmx_mesh_info_t."""
+    _fields_ = [("n_nodes", C.c_int64), ("n_vertices", C.c_int64), ("node_capacity", C.c_int64),
+                ("vertex_capacity", C.c_int64), ("device_bytes", C.c_int64), ("k", C.c_int32),
+                ("lds_nodes", C.c_int32), ("last_bind_blocks", C.c_int32), ("last_bind_global_blocks", C.c_int32)]
+
+
+class MeshStats(C.Structure):
+    """kmx_mesh_stats."""
+    _fields_ = [("n_vertices", C.c_int64), ("n_unbound", C.c_int64), ("n_partial", C.c_int64),
+                ("max_displacement", C.c_double), ("sum_sq_displacement", C.c_double)]
+
+
 _lib = None
 
 
@@ -349,6 +369,20 @@ def lib() -> C.CDLL:
         "kmx_cert_escape": ([P, pf64, i32, pf64, pf64, pi32], C.c_int),
         "kmx_cert_escape_commit": ([P, i32, pf64, C.POINTER(CertPointInfo)], C.c_int),
         "kmx_cert_get_escape_timing": ([P, pf64], C.c_int),
+        "kmx_mesh_create": ([C.POINTER(MeshParams), C.c_int, C.POINTER(P)], C.c_int),
+        "kmx_mesh_destroy": ([P], C.c_int),
+        "kmx_mesh_set_stream": ([P, P], C.c_int),
+        "kmx_mesh_info": ([P, C.POINTER(MeshInfo), pi64, pi64], C.c_int),
+        "kmx_mesh_add_nodes": ([P, i64, pi32, pi64, pf64, pf64], C.c_int),
+        "kmx_mesh_set_node_poses": ([P, i64, i64, pf64, pf64], C.c_int),
+        "kmx_mesh_add_vertices": ([P, i64, pi32, pi64, C.POINTER(C.c_float), pi64], C.c_int),
+        "kmx_mesh_bind": ([P, i64, i64], C.c_int),
+        "kmx_mesh_get_bindings": ([P, i64, i64, pi32, pf64, pi32], C.c_int),
+        "kmx_mesh_deform": ([P, i64, i64, C.POINTER(C.c_float), C.POINTER(MeshStats)], C.c_int),
+        "kmx_mesh_deform_device": ([P, i64, i64, P], C.c_int),
+        "kmx_mesh_sync": ([P], C.c_int),
+        "kmx_mesh_enable_timing": ([P, C.c_int], C.c_int),
+        "kmx_mesh_read_timing": ([P, pf64, pf64], C.c_int),
     })
     for name, (argt, rest) in sig.items():
         if not hasattr(L, name):
@@ -387,6 +421,11 @@ def iptr(a: np.ndarray):
 def i64ptr(a: np.ndarray):
     assert a.dtype == np.int64 and a.flags.c_contiguous
     return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def f32ptr(a: np.ndarray):
+    assert a.dtype == np.float32 and a.flags.c_contiguous
+    return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
 def u32ptr(a: np.ndarray):

@@ -249,7 +249,8 @@ def ate_rmse(g: PoseGraphData, traj: dict, *, anchor_robot: int = 0) -> float:
 def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, rank: int = 0, world: int = 1,
                  device: int = 0, rounds: int = 100, verifier=None, solver=None, exchange_device=None,
                  return_trajectory: bool = False, local_init: str = "odometry", certify_eta=None,
-                 staircase_rmax=None, staircase_kw=None) -> dict:
+                 staircase_rmax=None, staircase_kw=None, mesh=None, mesh_k: int = 4,
+                 mesh_window_s: float = 1.0) -> dict:
     """One team run: LCD verification of this rank's candidates (query robot
     in the rank's robot range) -> all_gather of the accepted loop closures ->
     team graph -> global initialisation -> `rounds` concurrent RBCD rounds
@@ -274,8 +275,18 @@ def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, ran
     "ate_m", the error of the trajectory rounded with the result's own lift
     (rounding_lift). staircase_kw: staircase_team's grad_tol, stat_tol,
     max_rounds, alphas and min_eig's keywords (defaults: 1e-6, 1e-3, 200).
-    "certificate" stays the RBCD iterate's. Returns stage timings and metrics
-    (identical on every rank)."""
+    "certificate" stays the RBCD iterate's. mesh (one rank only; a
+    kmx.synth.mesh.MeshData, or anything with its xyz, robot, stamp, kf_stamp
+    and gt_xyz): after the rounds the mesh follows the result on the device
+    (kmx.pgmo.MeshDeformer, mesh_k nodes per vertex in a window of
+    mesh_window_s): every robot's odometry chain is the rest trajectory and
+    the rounded RBCD trajectory the current one. The result gets a "mesh"
+    entry: vertices, unbound, bind_seconds and deform_seconds (device times),
+    rmse_before_m and rmse_after_m against mesh.gt_xyz, both expressed
+    relative to the anchor robot's first pose as ate_rmse does (before: the
+    vertices as given, in their robots' odometry frames), and with
+    return_trajectory "xyz", the deformed vertices. Returns stage timings and
+    metrics (identical on every rank)."""
     import time
 
     if certify_eta is not None and world > 1:
@@ -284,6 +295,8 @@ def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, ran
         raise ValueError("staircase_rmax needs certify_eta: the staircase decides at that tolerance")
     if staircase_rmax is not None and world > 1:
         raise ValueError("staircase_rmax needs world == 1: the team's iterate is not on one rank")
+    if mesh is not None and world > 1:
+        raise ValueError("mesh needs world == 1: the team's trajectory and the mesh are on one rank")
 
     from .dpgo.driver import RBCDDriver, robot_ranges
     from .synth.pose_graph import lift, lifting_matrix
@@ -384,9 +397,47 @@ def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, ran
                                 "ate_m": ate_rmse(g, traj)}
             if return_trajectory:
                 out["staircase"]["trajectory"] = traj
+    if mesh is not None:
+        out["mesh"] = deform_mesh(g, mesh, odometry_init(g), mine, k=mesh_k, window_s=mesh_window_s, device=device,
+                                  return_xyz=return_trajectory)
     if hasattr(drv.solver, "close"):
         drv.solver.close()
     return out
+
+
+def mesh_rmse(g: PoseGraphData, xyz, gt_xyz, traj: dict, *, anchor_robot: int = 0) -> float:
+    """Vertex RMSE after expressing the vertices relative to traj's first pose
+    of `anchor_robot` and the ground truth relative to its ground-truth first
+    pose (ate_rmse's convention)."""
+    Re0, te0 = traj[anchor_robot][0][0], traj[anchor_robot][1][0]
+    Rg0, tg0 = g.gt_R[anchor_robot][0], g.gt_t[anchor_robot][0]
+    pe = (np.asarray(xyz, np.float64) - te0) @ Re0
+    pg = (np.asarray(gt_xyz, np.float64) - tg0) @ Rg0
+    return float(np.sqrt(((pe - pg) ** 2).sum(1).mean()))
+
+
+def deform_mesh(g: PoseGraphData, mesh, rest: dict, current: dict, *, k: int = 4, window_s: float = 1.0,
+                device: int = 0, return_xyz: bool = False) -> dict:
+    """The mesh stage of run_pipeline: keyframes of every robot as control
+    nodes (rest[a] -> current[a]), one bind and one deformation on the device."""
+    from .pgmo import MeshDeformer
+    md = MeshDeformer(k=k, window_s=window_s, n_robots=g.n_robots, device=device)
+    try:
+        for a in range(g.n_robots):
+            md.add_keyframes(a, mesh.kf_stamp[a], rest[a][0], rest[a][1])
+            md.update_trajectory(a, current[a][0], current[a][1])
+        md.add_vertices(mesh.robot, mesh.stamp, mesh.xyz)
+        xyz, st = md.deform()
+        tm = md.timing()
+    finally:
+        md.close()
+    res = {"vertices": int(st["vertices"]), "unbound": int(st["unbound"]), "bind_seconds": tm["bind_ms"] * 1e-3,
+           "deform_seconds": tm["deform_ms"] * 1e-3,
+           "rmse_before_m": mesh_rmse(g, mesh.xyz, mesh.gt_xyz, rest),
+           "rmse_after_m": mesh_rmse(g, xyz, mesh.gt_xyz, current)}
+    if return_xyz:
+        res["xyz"] = xyz
+    return res
 
 
 def solver_team_cost(solver, g: PoseGraphData, X_by_robot: dict, w=None) -> float:

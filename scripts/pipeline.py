@@ -39,6 +39,9 @@ def main():
                     help="with --certify, one GPU only: the Riemannian staircase from the final iterate and weights "
                          "up to rank RMAX (escape along the certificate's negative direction, re-solve one rank up); "
                          "the result gets a 'staircase' entry")
+    ap.add_argument("--mesh", type=int, default=None, metavar="N",
+                    help="one GPU only: a synthetic mesh of N vertices per keyframe (kmx.synth.mesh.make_mesh) "
+                         "follows the result on the device; the result gets a 'mesh' entry")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -57,10 +60,14 @@ def main():
     g0 = make_pose_graph(a.robots, n, int(a.edges_per_pose * n), f_inter=0.0, outlier_scope="robot",
                          sigma_R=a.sigma_r, sigma_t=a.sigma_t, seed=a.seed)
     stream = PL.make_lc_stream(g0, a.robots * a.true_per_robot, a.robots * a.false_per_robot, seed=a.seed + 1)
+    mesh = None
+    if a.mesh is not None:
+        from kmx.synth.mesh import make_mesh
+        mesh = make_mesh(g0, a.mesh, 3.0, a.seed + 2)
     gen = time.perf_counter() - t0
     out = PL.run_pipeline(g0, stream, bench.params(), LcdParams(), rank=rank, world=world, device=local_rank,
                           rounds=a.rounds, local_init=a.local_init, certify_eta=a.certify,
-                          staircase_rmax=a.staircase)
+                          staircase_rmax=a.staircase, mesh=mesh)
     out["config"] = {"workload": f"configs[4]: {a.robots} robots x {a.poses} poses, {g0.m} base edges "
                                  f"(intra-robot loop closures, 20% intra outliers, odometry noise "
                                  f"{a.sigma_r} rad / {a.sigma_t} m), LC stream "
