@@ -14,12 +14,13 @@
 #include <string>
 #include <vector>
 
+#include "graph_host.h"
 #include "kmx_abi.h"
 
 namespace kmx {
 
 constexpr int CT_TILE = 64;               // poses per tile = lanes per workgroup (one wave)
-constexpr uint32_t CT_TAIL = 1u << 31;    // record bit: this pose is the edge's tail (p == i): it applies C
+constexpr uint32_t CT_TAIL = GRAPH_TAIL;  // record bit: this pose is the edge's tail (p == i): it applies C
 
 // What kmx_cert_set_graph keeps: the incidence CSR of the team graph (sorted
 // by pose, in edge order within a pose). There are no blocks: S couples robots.
@@ -58,18 +59,8 @@ inline int cert_build(int32_t n, int64_t m, const int32_t* src, const int32_t* d
   if (m > 0 && (!src || !dst || !R || !t || !kappa || !tau)) return bad("null edge array");
   if (m >= (int64_t)INT32_MAX / 2) return bad("too many edges (2 * n_edges must fit int32)");
   if (n >= INT32_MAX / 8) return bad("too many poses");
-  for (int64_t e = 0; e < m; ++e) {
-    const std::string at = " (edge " + std::to_string(e) + ")";
-    if (src[e] < 0 || src[e] >= n || dst[e] < 0 || dst[e] >= n) return bad("edge endpoint out of range" + at);
-    if (src[e] == dst[e]) return bad("edge from a pose to itself" + at);
-    for (int k = 0; k < 9; ++k)
-      if (!std::isfinite(R[9 * e + k])) return bad("R not finite" + at);
-    for (int k = 0; k < 3; ++k)
-      if (!std::isfinite(t[3 * e + k])) return bad("t not finite" + at);
-    if (!std::isfinite(kappa[e]) || !(kappa[e] > 0)) return bad("kappa must be finite and > 0" + at);
-    if (!std::isfinite(tau[e]) || !(tau[e] > 0)) return bad("tau must be finite and > 0" + at);
-  }
-  std::string werr;
+  std::string werr = graph_check_edges(n, m, src, dst, R, t, kappa, tau, [](int64_t) { return (const char*)nullptr; });
+  if (!werr.empty()) return bad(werr);
   if (cert_check_weights(m, weight, &werr) != KMX_OK) return bad(werr);
 
   CertGraph g;
@@ -77,26 +68,7 @@ inline int cert_build(int32_t n, int64_t m, const int32_t* src, const int32_t* d
   g.m = m;
   g.kappa.assign(kappa, kappa + m);
   g.tau.assign(tau, tau + m);
-  // incidence CSR by counting sort: a pose's records come in edge order, and
-  // an edge's two records are distinct (src != dst)
-  g.inc_ptr.assign((size_t)n + 1, 0);
-  for (int64_t e = 0; e < m; ++e) {
-    g.inc_ptr[src[e] + 1]++;
-    g.inc_ptr[dst[e] + 1]++;
-  }
-  for (int32_t p = 0; p < n; ++p) g.inc_ptr[p + 1] += g.inc_ptr[p];
-  const size_t nrec = (size_t)2 * (size_t)m;
-  g.inc_other.resize(nrec);
-  g.inc_edge.resize(nrec);
-  std::vector<int32_t> fill(g.inc_ptr.begin(), g.inc_ptr.end() - 1);
-  for (int64_t e = 0; e < m; ++e) {
-    const size_t ks = (size_t)fill[src[e]]++;  // the tail's record
-    g.inc_other[ks] = (uint32_t)dst[e] | CT_TAIL;
-    g.inc_edge[ks] = (int32_t)e;
-    const size_t kd = (size_t)fill[dst[e]]++;  // the head's record
-    g.inc_other[kd] = (uint32_t)src[e];
-    g.inc_edge[kd] = (int32_t)e;
-  }
+  graph_incidence_csr(n, m, src, dst, &g.inc_ptr, &g.inc_other, &g.inc_edge);
   g.n_tiles = (n + CT_TILE - 1) / CT_TILE;
   *out = std::move(g);
   return KMX_OK;

@@ -12,12 +12,13 @@
 #include <string>
 #include <vector>
 
+#include "graph_host.h"
 #include "kmx_abi.h"
 
 namespace kmx {
 
 constexpr int CH_TILE = 64;                 // poses per tile = lanes per workgroup (one wave)
-constexpr uint32_t CH_DIR_OUT = 1u << 31;   // record bit: this pose is the edge's source (p == i)
+constexpr uint32_t CH_DIR_OUT = GRAPH_TAIL;  // record bit: this pose is the edge's source (p == i)
 
 // What kmx_chordal_set_graph keeps: the incidence CSR (sorted by pose, in edge
 // order within a pose) and the tiles. A tile is at most CH_TILE consecutive
@@ -107,19 +108,10 @@ inline int chordal_build(int32_t n, int32_t nb, const int32_t* block_ptr, int64_
     if (!is_free[anchors[a]]) return bad("anchor listed twice");
     is_free[anchors[a]] = 0;
   }
-  for (int64_t e = 0; e < m; ++e) {
-    const std::string at = " (edge " + std::to_string(e) + ")";
-    if (src[e] < 0 || src[e] >= n || dst[e] < 0 || dst[e] >= n) return bad("edge endpoint out of range" + at);
-    if (src[e] == dst[e]) return bad("edge from a pose to itself" + at);
-    if (pose_block[src[e]] != pose_block[dst[e]]) return bad("edge across blocks" + at);
-    for (int k = 0; k < 9; ++k)
-      if (!std::isfinite(R[9 * e + k])) return bad("R not finite" + at);
-    for (int k = 0; k < 3; ++k)
-      if (!std::isfinite(t[3 * e + k])) return bad("t not finite" + at);
-    if (!std::isfinite(kappa[e]) || !(kappa[e] > 0)) return bad("kappa must be finite and > 0" + at);
-    if (!std::isfinite(tau[e]) || !(tau[e] > 0)) return bad("tau must be finite and > 0" + at);
-  }
-  std::string werr;
+  std::string werr = graph_check_edges(n, m, src, dst, R, t, kappa, tau, [&](int64_t e) {
+    return pose_block[src[e]] != pose_block[dst[e]] ? "edge across blocks" : nullptr;
+  });
+  if (!werr.empty()) return bad(werr);
   if (chordal_check_weights(n, m, src, dst, weight, is_free.data(), &werr) != KMX_OK) return bad(werr);
 
   ChordalGraph g;
@@ -133,32 +125,15 @@ inline int chordal_build(int32_t n, int32_t nb, const int32_t* block_ptr, int64_
   g.dst.assign(dst, dst + m);
   g.w0.assign((size_t)m, 1.0);
   if (weight) g.w0.assign(weight, weight + m);
-  // incidence CSR by counting sort: a pose's records come in edge order, and
-  // an edge's two records are distinct (src != dst)
-  g.inc_ptr.assign((size_t)n + 1, 0);
-  for (int64_t e = 0; e < m; ++e) {
-    g.inc_ptr[src[e] + 1]++;
-    g.inc_ptr[dst[e] + 1]++;
-  }
-  for (int32_t p = 0; p < n; ++p) g.inc_ptr[p + 1] += g.inc_ptr[p];
-  const size_t nrec = (size_t)2 * (size_t)m;
-  g.inc_other.resize(nrec);
-  g.inc_edge.resize(nrec);
+  graph_incidence_csr(n, m, src, dst, &g.inc_ptr, &g.inc_other, &g.inc_edge);
+  const size_t nrec = g.inc_edge.size();
   g.inc_M.resize(9 * nrec);
   g.inc_t.resize(3 * nrec);
-  std::vector<int32_t> fill(g.inc_ptr.begin(), g.inc_ptr.end() - 1);
-  for (int64_t e = 0; e < m; ++e) {
-    const double* Re = R + 9 * e;
-    const size_t ks = (size_t)fill[src[e]]++;  // the source's record: X_j R_e^T
-    g.inc_other[ks] = (uint32_t)dst[e] | CH_DIR_OUT;
-    g.inc_edge[ks] = (int32_t)e;
+  for (size_t k = 0; k < nrec; ++k) {  // the source's record: X_j R_e^T, the target's: X_i R_e
+    const double* Re = R + 9 * (size_t)g.inc_edge[k];
     for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) g.inc_M[9 * ks + 3 * r + c] = Re[3 * c + r];
-    const size_t kd = (size_t)fill[dst[e]]++;  // the target's record: X_i R_e
-    g.inc_other[kd] = (uint32_t)src[e];
-    g.inc_edge[kd] = (int32_t)e;
-    for (int k = 0; k < 9; ++k) g.inc_M[9 * kd + k] = Re[k];
-    for (int k = 0; k < 3; ++k) g.inc_t[3 * ks + k] = g.inc_t[3 * kd + k] = t[3 * e + k];
+      for (int c = 0; c < 3; ++c) g.inc_M[9 * k + 3 * r + c] = (g.inc_other[k] & CH_DIR_OUT) ? Re[3 * c + r] : Re[3 * r + c];
+    for (int q = 0; q < 3; ++q) g.inc_t[3 * k + q] = t[3 * (size_t)g.inc_edge[k] + q];
   }
   g.tile_ptr.assign((size_t)nb + 1, 0);
   for (int32_t b = 0; b < nb; ++b) {

@@ -55,6 +55,7 @@
 #include <vector>
 
 #include "common.h"
+#include "pgo_host.h"
 
 // KMX_HESS_PROBE (diagnostic builds only, scripts/gpu_hess_probe.sh): bits
 // remove one k_hess stream each so its PMC traffic can be attributed; the
@@ -65,7 +66,9 @@
 
 namespace {
 
-constexpr int WAVES = 4;
+// the tile rule, the record sizes, TileDesc, RedMode and the cut's thresholds: pgo_host.h
+using namespace kmx;
+
 constexpr int BLOCK = 64 * WAVES;
 constexpr int NPART = 4;  // partial sums per tile
 // per-kernel LDS reduction area: NPART x WAVES wave sums + the ticket flag
@@ -139,18 +142,6 @@ struct Params {
   int gnc_on, inner_iters, max_updates, n_ext;
   int rgd;          // KMX_METHOD_RGD: one preconditioned gradient step per block update
   double rgd_step;
-};
-
-// One tile's description, read by a single 32-B scalar load at the start of
-// every tile kernel: its robot, its first pose, its incidence range start
-// inc_ptr[p0] and, packed, its pose count np (< 256) and incidence count
-// n = inc_ptr[p0 + np] - inc_ptr[p0] (np | n << 8), so the record loads do not
-// wait for an inc_ptr lookup; and its robot's tile range, so the consumer
-// kernels' robot sums do not wait for an rtile0 lookup.
-struct alignas(16) TileDesc {
-  int robot, p0, k0, np_n;
-  int rt0, rt1;  // the robot's tile range: the consumer kernels' robot sums start from it
-  int pad0, pad1;
 };
 
 struct Dev {
@@ -331,7 +322,7 @@ __device__ __forceinline__ int2 unpack_int2(double v) {
 template <int RW>
 struct Rec {
   static constexpr int Q = RW / 2;        // 16-B parts in registers
-  static constexpr int GS = RW == 10 ? 8 : 16;  // doubles per record in HBM
+  static constexpr int GS = rec_gs(RW);         // doubles per record in HBM
   static constexpr int WK = RW == 10 ? 6 : 12;  // index of w kappa (w tau follows)
   static constexpr int QS = RW == 10 ? 4 : Q;   // 16-B parts of the record as stored
   // The load in two halves, for a gather that fetches the word with the other
@@ -622,7 +613,7 @@ __device__ __forceinline__ Lane lane_map(const Dev& d) {
 // (one lane each).
 template <int R, int W = WAVES>
 struct SmemH {  // Hessian gather (k_hess, eval EHESS)
-  static constexpr int TP = W * (64 / R);
+  static constexpr int TP = tile_poses(R, W);
   static constexpr int CH = TP * R;                                       // <= 64 W
   static constexpr int c_off = 0;                                         // double[CH][R][4]
   static constexpr int ptr_off = CH * R * 32;                             // int[TP + 1]
@@ -631,7 +622,7 @@ struct SmemH {  // Hessian gather (k_hess, eval EHESS)
 };
 template <int R, int W = WAVES>
 struct SmemHG {  // gradient / cost gathers: a chunk buffer plus the tile's own rows
-  static constexpr int TP = W * (64 / R);
+  static constexpr int TP = tile_poses(R, W);
   static constexpr int CH = 240;                                          // incidences per chunk
   static constexpr int c_off = 0;                                         // double[CH][R][4]
   static constexpr int x_off = CH * R * 32;                               // double[TP][R][4]
@@ -641,7 +632,7 @@ struct SmemHG {  // gradient / cost gathers: a chunk buffer plus the tile's own 
 };
 template <int R, int W = WAVES>
 struct SmemC {  // trial cost: own rows + CSR pointers only
-  static constexpr int TP = W * (64 / R);
+  static constexpr int TP = tile_poses(R, W);
   static constexpr int x_off = 0;
   static constexpr int ptr_off = TP * R * 32;
   static constexpr int red_off = ptr_off + ((TP + 1) * 4 + 15) / 16 * 16;
@@ -1004,7 +995,7 @@ __device__ __forceinline__ double inc_owner_cost(const Dev& d, const Lane& L, co
 // each workgroup resident for microseconds after its work) and a half form
 // with only the update's k_reduce kept (0.814 / 0.839 vs 0.817 / 0.839 ms per
 // round: no gain).
-enum RedMode { RM_LAUNCH = 0, RM_CONSUMER = 2 };
+// (enum RedMode { RM_LAUNCH, RM_CONSUMER }: pgo_host.h)
 
 template <int KIND, int NV, int RM, typename Store>
 __device__ __forceinline__ void finish_tile(const Dev& d, const Lane& L, const double* vals, char* smem_red,
@@ -1220,7 +1211,6 @@ __device__ __forceinline__ void ctl_publish(Ctl* dst, const Ctl& cs, bool retrac
 // RM_LAUNCH: one workgroup per robot reduces the robot's tile partials in
 // tile order and runs the control logic (after k_update it also reports the
 // robot's tCG progress to the host).
-constexpr int TILES_TARGET = 736;  // tile count the cut of small problems aims at (set_graph)
 constexpr int RBLOCK = 256;  // k_reduce: one workgroup per robot (1024 threads measured slower: 6.3 vs 4.6 us)
 static_assert(RBLOCK == BLOCK, "robot_sum runs in k_reduce and in the tCG kernels");
 // Sum of NS partials (row stride `stride`) over tiles [t0, t1) of a robot by
@@ -3131,21 +3121,10 @@ struct kmx_pgo {
   // The grouped round's reduction form (KMX_GROUP_RED = 0 launched, 2
   // consumer): which instantiation of enqueue_round_t the groups' chains
   // take; `rm` still decides whether groups are in effect and the single
-  // chain's form.
-  // On one chain the consumer form only ties at 100k poses (above); on two
-  // chains it drops 22 of a chain's 45 launches and the other group's
-  // workgroups fill part of the waits for the robot sums: configs[3]
-  // 0.603-0.619 ms per round against 0.622-0.633 for the launched form
-  // (profiles/r08/group_consumer/). Every workgroup of
-  // the consumer kernels reads all tile partials of its robot, so its cost
-  // grows with the robot's tile count: with 8 robots in 2 groups it wins 3-5 %
-  // at 275-288 tiles per robot (12.5k poses), 1-2 % at 310-324 and ~1 % at
-  // 354-368, loses 1.4 % at 400-421, 7 % at ~500 and 20 % at ~2600 (the
-  // 1M-pose config). It is the default while no local robot has more than
-  // GROUP_CONSUMER_MAX_TILES tiles.
+  // chain's form. Consumer while no local robot has more than
+  // GROUP_CONSUMER_MAX_TILES tiles (pgo_host.h, with the measurements).
   int grm = 2;
   int grm_forced = -1;
-  static constexpr int GROUP_CONSUMER_MAX_TILES = 384;
   hipStream_t gstream[MAX_GROUPS - 1] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_fork = nullptr, ev_join[MAX_GROUPS - 1] = {nullptr, nullptr, nullptr};
   // Gated k_hess launches (KMX_HESS_GATE=0: off): every k_hess launch after a
@@ -3166,20 +3145,15 @@ struct kmx_pgo {
   bool tcg_tail = true;
   // (measured and removed: a hipStreamQuery before the status spin put a ~5 us
   // bubble before the next tCG step's first kernel, profiles/r02/ab_query)
-  // reduction mode: set per graph (below) unless KMX_RED forces one (0 launch,
-  // 2 consumer). Measured at the end of round 2
-  // (profiles/r02/small_round/16_*): the consumer form (no reduction launch,
-  // the stop decision before the gather) wins per round at 25k poses (244 vs
-  // 280 us), 37.5k (318 vs 357), 62.5k (530 vs 543) and 75k (583 vs 591), ties
-  // at 50k and 87.5k, and loses at 100k (773 vs 731-738: two and a bit
-  // generations of workgroups, each waiting for its robot's sums)
+  // reduction mode: set per graph (pgo_plan: consumer up to
+  // RM_CONSUMER_MAX_POSES local poses) unless KMX_RED forces one (0 launch,
+  // 2 consumer)
   int rm = RM_LAUNCH;
   int rm_forced = -1;
   // consumer-form k_hess: the stop decision before the gather (small problems)
   // or after it; KMX_HESS_DECIDE forces one (0 after, 1 before)
   int early_stop = 1;
   int decide_forced = -1;
-  static constexpr int RM_CONSUMER_MAX_POSES = 80000;
   bool poll_timeout = false;
   // timing
   bool timing = false;
@@ -3198,53 +3172,6 @@ struct kmx_pgo {
 };
 
 namespace {
-
-// Unit quaternion (w, x, y, z) of a rotation matrix (row-major), by the
-// largest of the four diagonal combinations (Shepperd), and back.
-void rot_to_quat(const double* R, double* q) {
-  const double tr = R[0] + R[4] + R[8];
-  double w, x, y, z;
-  if (tr > 0.0) {
-    const double s = 2.0 * std::sqrt(tr + 1.0);
-    w = 0.25 * s; x = (R[7] - R[5]) / s; y = (R[2] - R[6]) / s; z = (R[3] - R[1]) / s;
-  } else if (R[0] > R[4] && R[0] > R[8]) {
-    const double s = 2.0 * std::sqrt(1.0 + R[0] - R[4] - R[8]);
-    w = (R[7] - R[5]) / s; x = 0.25 * s; y = (R[1] + R[3]) / s; z = (R[2] + R[6]) / s;
-  } else if (R[4] > R[8]) {
-    const double s = 2.0 * std::sqrt(1.0 + R[4] - R[0] - R[8]);
-    w = (R[2] - R[6]) / s; x = (R[1] + R[3]) / s; y = 0.25 * s; z = (R[5] + R[7]) / s;
-  } else {
-    const double s = 2.0 * std::sqrt(1.0 + R[8] - R[0] - R[4]);
-    w = (R[3] - R[1]) / s; x = (R[2] + R[6]) / s; y = (R[5] + R[7]) / s; z = 0.25 * s;
-  }
-  const double n = std::sqrt(w * w + x * x + y * y + z * z);
-  q[0] = w / n; q[1] = x / n; q[2] = y / n; q[3] = z / n;
-}
-// Rec<10>'s three stored components: all but the largest (made >= 0 by
-// negating the quaternion, which leaves R unchanged), whose index goes to
-// rec_o's bits 29-31; and the device's rebuild of the fourth (Rec<10>::load).
-int quat_pack(const double* q, double* q3) {
-  int big = 0;
-  for (int i = 1; i < 4; ++i)
-    if (std::fabs(q[i]) > std::fabs(q[big])) big = i;
-  const double sg = q[big] < 0.0 ? -1.0 : 1.0;
-  for (int i = 0, j = 0; i < 4; ++i)
-    if (i != big) q3[j++] = sg * q[i];
-  return big;
-}
-void quat_unpack(const double* q3, int big, double* q) {
-  const double ql = std::sqrt(1.0 - (q3[0] * q3[0] + q3[1] * q3[1] + q3[2] * q3[2]));
-  for (int i = 0, j = 0; i < 4; ++i) q[i] = i == big ? ql : q3[j++];
-}
-// the device's Rec<10>::edge expressions
-void quat_to_rot(const double* q, double* R) {
-  const double w = q[0], x = q[1], y = q[2], z = q[3];
-  const double xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z;
-  const double wx = w * x, wy = w * y, wz = w * z;
-  R[0] = 1.0 - 2.0 * (yy + zz); R[1] = 2.0 * (xy - wz); R[2] = 2.0 * (xz + wy);
-  R[3] = 2.0 * (xy + wz); R[4] = 1.0 - 2.0 * (xx + zz); R[5] = 2.0 * (yz - wx);
-  R[6] = 2.0 * (xz - wy); R[7] = 2.0 * (yz + wx); R[8] = 1.0 - 2.0 * (xx + yy);
-}
 
 template <typename T>
 int dalloc(T** p, size_t count) {
@@ -3911,6 +3838,24 @@ extern "C" int kmx_pgo_get_group_reduction(kmx_pgo* h, int* form) {
   return KMX_OK;
 }
 
+// pgo_plan's two-int struct is uploaded as the device's int2
+static_assert(sizeof(kmx::PgoInt2) == sizeof(int2) && offsetof(kmx::PgoInt2, x) == offsetof(int2, x) &&
+                  offsetof(kmx::PgoInt2, y) == offsetof(int2, y),
+              "PgoInt2 is int2");
+
+namespace {
+// One plan vector to its device buffer (an empty list has nothing to copy).
+template <typename D, typename S>
+hipError_t upload(kmx_pgo* h, D* dst, const std::vector<S>& src) {
+  static_assert(sizeof(D) == sizeof(S), "uploaded as bytes");
+  if (src.empty()) return hipSuccess;
+  return hipMemcpyAsync(dst, src.data(), sizeof(S) * src.size(), hipMemcpyHostToDevice, h->stream);
+}
+}  // namespace
+
+// The graph is checked and planned on the host (pgo_plan, pgo_host.h) before
+// the handle is touched: an error from it leaves the handle as it was. Then
+// the old graph is dropped and the plan is uploaded.
 extern "C" int kmx_pgo_set_graph(kmx_pgo* h, int n_robots, const int32_t* n_poses, const uint8_t* local,
                                  int64_t m, const int32_t* r1, const int32_t* p1, const int32_t* r2,
                                  const int32_t* p2, const double* R, const double* t, const double* kappa,
@@ -3921,313 +3866,69 @@ extern "C" int kmx_pgo_set_graph(kmx_pgo* h, int n_robots, const int32_t* n_pose
   KMX_CHECK(m >= 0 && m < (1ll << 31) - 1, KMX_EINVAL, "edge count out of range");
   KMX_CHECK(m == 0 || (r1 && p1 && r2 && p2 && R && t && kappa && tau && weight && fixed_weight), KMX_EINVAL,
             "null edge array");
+  PgoPlanIn in;
+  in.r = h->P.r;
+  in.tile_incidences = h->P.tile_incidences;
+  in.groups_req = h->groups_req;
+  in.rm_forced = h->rm_forced;
+  in.decide_forced = h->decide_forced;
+  in.grm_forced = h->grm_forced;
+  in.onesync = onesync(h);
+  PgoPlan plan;
+  std::string err;
+  if (int rc = pgo_plan(in, n_robots, n_poses, local, m, r1, p1, r2, p2, R, t, kappa, tau, weight, fixed_weight,
+                        &plan, &err))
+    return kmx::fail(rc, err);
   KMX_HIP(hipSetDevice(h->device));
   KMX_HIP(hipStreamSynchronize(h->stream));
   free_dev(h);
   free_xchg(h);  // the exchange slot lists index this graph's public table
   accel_reset(h);
+  // the plan's host fields
   const int r = h->P.r, ps = 4 * r;
+  const int L = (int)plan.robots.size(), nloc = plan.nloc;
   h->n_robots = n_robots;
   h->npose.assign(n_poses, n_poses + n_robots);
-  h->local_of.assign(n_robots, -1);
-  h->robots.clear();
-  h->loff.clear();
-  int nloc = 0;
-  for (int a = 0; a < n_robots; ++a) {
-    KMX_CHECK(n_poses[a] >= 0, KMX_EINVAL, "negative pose count");
-    if (local[a]) {
-      h->local_of[a] = (int)h->robots.size();
-      h->robots.push_back(a);
-      h->loff.push_back(nloc);
-      nloc += n_poses[a];
-    }
-  }
-  h->nloc = nloc;
-  h->rm = h->rm_forced >= 0 ? h->rm_forced : (nloc <= kmx_pgo::RM_CONSUMER_MAX_POSES ? RM_CONSUMER : RM_LAUNCH);
-  if (onesync(h)) h->rm = RM_CONSUMER;  // its decisions are taken by every workgroup
-  // decide before the gather on small problems
-  h->early_stop = h->decide_forced >= 0 ? h->decide_forced : (nloc <= kmx_pgo::RM_CONSUMER_MAX_POSES ? 1 : 0);
-  const int L = (int)h->robots.size();
-  KMX_CHECK(L > 0, KMX_EINVAL, "no local robot");
-  KMX_CHECK(L <= 1024, KMX_EUNSUP, "at most 1024 local robots per handle");
   h->m_global = m;
-  // validate + public table (team-wide, so every handle agrees on slot ids)
-  std::vector<int64_t> keys;
-  for (int64_t e = 0; e < m; ++e) {
-    KMX_CHECK(r1[e] >= 0 && r1[e] < n_robots && r2[e] >= 0 && r2[e] < n_robots, KMX_EINVAL,
-              "edge robot id out of range");
-    KMX_CHECK(p1[e] >= 0 && p1[e] < n_poses[r1[e]] && p2[e] >= 0 && p2[e] < n_poses[r2[e]], KMX_EINVAL,
-              "edge pose id out of range");
-    KMX_CHECK(!(r1[e] == r2[e] && p1[e] == p2[e]), KMX_EINVAL, "self-loop edge");
-    if (r1[e] != r2[e]) {
-      keys.push_back(((int64_t)r1[e] << 32) | (uint32_t)p1[e]);
-      keys.push_back(((int64_t)r2[e] << 32) | (uint32_t)p2[e]);
-    }
+  h->local_of = std::move(plan.local_of);
+  h->robots = std::move(plan.robots);
+  h->loff = std::move(plan.loff);
+  h->nloc = nloc;
+  h->rm = plan.rm;
+  h->early_stop = plan.early_stop;
+  h->grm = plan.grm;
+  h->pub_key = std::move(plan.pub_key);
+  h->npub = plan.npub;
+  h->first_owned = plan.first_owned;
+  h->n_owned = plan.n_owned;
+  h->loc_edge_gid = std::move(plan.loc_edge_gid);
+  h->mloc = plan.mloc;
+  h->m_robot = std::move(plan.m_robot);
+  h->rw = plan.rw;
+  h->ninc = plan.ninc;
+  h->nshared = plan.nshared;
+  h->n_gnc = (int)plan.gnc_edge.size();
+  h->n_sh_local = (int)plan.sh_edge.size();
+  h->n_osh = (int)plan.osh_edge.size();
+  h->rt0_h = plan.rt0;
+  h->ntiles = (int)plan.tile.size();
+  h->grp.assign(plan.grp.size(), kmx_pgo::Group{});
+  for (size_t g = 0; g < plan.grp.size(); ++g) {
+    const PgoGroupCut& c = plan.grp[g];
+    h->grp[g].l0 = c.l0; h->grp[g].l1 = c.l1;
+    h->grp[g].t0 = c.t0; h->grp[g].nt = c.nt;
   }
-  std::sort(keys.begin(), keys.end());
-  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
-  h->pub_key = keys;
-  h->npub = (int64_t)keys.size();
-  auto slot_of = [&](int rb, int pp) -> int64_t {
-    const int64_t k = ((int64_t)rb << 32) | (uint32_t)pp;
-    auto it = std::lower_bound(h->pub_key.begin(), h->pub_key.end(), k);
-    return (it != h->pub_key.end() && *it == k) ? (int64_t)(it - h->pub_key.begin()) : -1;
-  };
-  std::vector<int> pub_src(std::max<int64_t>(h->npub, 1), -1);
-  std::vector<int> pose_slot(std::max(nloc, 1), -1);
-  int64_t first = -1, last = -1;
-  for (int64_t s = 0; s < h->npub; ++s) {
-    const int rb = (int)(keys[s] >> 32), pp = (int)(keys[s] & 0xffffffff);
-    if (h->local_of[rb] >= 0) {
-      pub_src[s] = h->loff[h->local_of[rb]] + pp;
-      pose_slot[pub_src[s]] = (int)s;
-      if (first < 0) first = s;
-      KMX_CHECK(last < 0 || last == s - 1, KMX_EUNSUP,
-                "local robots must own a contiguous range of the public table (assign robot ranges to ranks)");
-      last = s;
-    }
-  }
-  h->first_owned = first < 0 ? 0 : first;
-  h->n_owned = first < 0 ? 0 : last - first + 1;
-  // local edges, incidences
-  auto lpose = [&](int rb, int pp) { return h->loff[h->local_of[rb]] + pp; };
-  std::vector<int64_t> ledges;
-  for (int64_t e = 0; e < m; ++e)
-    if (h->local_of[r1[e]] >= 0 || h->local_of[r2[e]] >= 0) ledges.push_back(e);
-  h->mloc = (int)ledges.size();
-  h->loc_edge_gid = ledges;
-  std::vector<double> ek_h(std::max(h->mloc, 1), 0.0), et_h(std::max(h->mloc, 1), 0.0);
-  std::vector<double> ew_h(std::max(h->mloc, 1), 0.0);
-  std::vector<int> deg(nloc + 1, 0);
-  h->m_robot.assign(L, 0);
-  for (int k = 0; k < h->mloc; ++k) {
-    const int64_t e = ledges[k];
-    ek_h[k] = kappa[e];
-    et_h[k] = tau[e];
-    ew_h[k] = weight[e];
-    const int a1 = h->local_of[r1[e]], a2 = h->local_of[r2[e]];
-    if (a1 >= 0) { deg[lpose(r1[e], p1[e])]++; h->m_robot[a1]++; }
-    if (a2 >= 0) { deg[lpose(r2[e], p2[e])]++; if (r2[e] != r1[e]) h->m_robot[a2]++; }
-  }
-  // record width: compact (quaternion) when every local measurement rotation
-  // is rebuilt from its unit quaternion to 1e-12 (a rotation), full otherwise
-  // (the three stored components per edge, and the rebuilt one's index)
-  std::vector<double> quat((size_t)std::max(h->mloc, 1) * 3);
-  std::vector<int> qbig(std::max(h->mloc, 1), 0);
-  {
-    // (the other endpoint takes rec_o's low 29 bits: local poses and public
-    // slots below 2^28, far above any single GPU's share)
-    bool ok = nloc < (1 << 28) && h->npub < (1 << 28);
-    for (int k = 0; k < h->mloc && ok; ++k) {
-      const double* Q = R + 9 * ledges[k];
-      double q4[4], qr[4], Rq[9];
-      rot_to_quat(Q, q4);
-      qbig[k] = quat_pack(q4, &quat[3 * (size_t)k]);
-      quat_unpack(&quat[3 * (size_t)k], qbig[k], qr);
-      quat_to_rot(qr, Rq);
-      for (int i = 0; i < 9 && ok; ++i) ok = std::fabs(Rq[i] - Q[i]) <= 1e-12;
-    }
-    h->rw = ok ? 10 : 16;
-  }
-  const int RW = h->rw;
-  std::vector<int> inc_ptr(nloc + 1, 0);
-  for (int i = 0; i < nloc; ++i) inc_ptr[i + 1] = inc_ptr[i] + deg[i];
-  h->ninc = inc_ptr[nloc];
-  const int GS = RW == 10 ? 8 : 16;  // Rec<RW>::GS
-  std::vector<double> rec((size_t)(h->ninc + 1) * GS, 0.0);  // + one zero pad record
-  std::vector<int> rec_o(RW == 10 ? h->ninc + 1 : 1, 0);
-  std::vector<int2> eipos(std::max(h->mloc, 1), make_int2(-1, -1));
-  std::vector<int> fill(inc_ptr.begin(), inc_ptr.end() - 1);
-  auto put_rec = [&](int pos, int k, int64_t e, int other, int code) {
-    double* c = &rec[(size_t)pos * GS];
-    const double* Q = RW == 10 ? &quat[3 * (size_t)k] : R + 9 * e;
-    int j = 0;
-    for (int q = 0; q < (RW == 10 ? 3 : 9); ++q) c[j++] = Q[q];
-    for (int q = 0; q < 3; ++q) c[j++] = t[3 * e + q];
-    c[j++] = weight[e] * kappa[e];
-    const double wt = weight[e] * tau[e];
-    if (RW == 10) {  // compact: the tail flag in w tau's sign bit, the other endpoint apart
-      c[j++] = (code & 0x80000000) ? -wt : wt;
-      rec_o[pos] = (int)(((unsigned)other & 0x1fffffffu) | ((unsigned)qbig[k] << 29));
-    } else {
-      c[j++] = wt;
-      const long long bits = (long long)(unsigned)other | ((long long)code << 32);
-      std::memcpy(&c[j], &bits, 8);
-    }
-  };
-  for (int k = 0; k < h->mloc; ++k) {  // increasing global edge id per pose
-    const int64_t e = ledges[k];
-    const bool priv = r1[e] == r2[e];
-    if (h->local_of[r1[e]] >= 0) {
-      const int sp = lpose(r1[e], p1[e]);
-      const int other = priv ? lpose(r2[e], p2[e]) : (int)(-1 - slot_of(r2[e], p2[e]));
-      eipos[k].x = fill[sp];
-      put_rec(fill[sp]++, k, e, other, (int)(k | 0x80000000u));
-    }
-    if (h->local_of[r2[e]] >= 0) {
-      const int sp = lpose(r2[e], p2[e]);
-      const int other = priv ? lpose(r1[e], p1[e]) : (int)(-1 - slot_of(r1[e], p1[e]));
-      eipos[k].y = fill[sp];
-      put_rec(fill[sp]++, k, e, other, k);
-    }
-  }
-  // GNC: every non-fixed local edge is re-weighted here (a shared loop closure
-  // on both handles of its robots, identically); the owner-packed shared-weight
-  // table (owner = lower robot id, drawio:2198) is kept for the explicit exchange.
-  std::vector<int> gnc_edge, sh_edge, sh_idx, osh_edge, osh_idx;
-  std::vector<int2> gnc_ends;
-  int64_t nsh = 0;
-  {
-    size_t k = 0;
-    for (int64_t e = 0; e < m; ++e) {
-      if (r1[e] == r2[e]) continue;
-      const int64_t si = nsh++;
-      while (k < ledges.size() && ledges[k] < e) ++k;
-      if (k < ledges.size() && ledges[k] == e) {
-        sh_edge.push_back((int)k);
-        sh_idx.push_back((int)si);
-        if (h->local_of[std::min(r1[e], r2[e])] >= 0) {
-          osh_edge.push_back((int)k);
-          osh_idx.push_back((int)si);
-        }
-      }
-    }
-  }
-  h->nshared = nsh;
-  for (int k = 0; k < h->mloc; ++k) {
-    const int64_t e = ledges[k];
-    if (fixed_weight[e]) continue;
-    // a local endpoint is read from the iterate, a foreign one from the public
-    // table (after the exchange they hold the same row)
-    auto enc = [&](int rb, int pp) -> int {
-      return h->local_of[rb] >= 0 ? lpose(rb, pp) : (int)(-1 - slot_of(rb, pp));
-    };
-    gnc_edge.push_back(k);
-    gnc_ends.push_back(make_int2(enc(r1[e], p1[e]), enc(r2[e], p2[e])));
-  }
-  h->n_gnc = (int)gnc_edge.size();
-  h->n_sh_local = (int)sh_edge.size();
-  h->n_osh = (int)osh_edge.size();
-  // tiles: at most TP poses of one robot, cut by incidence count so every
-  // workgroup's gather walks about the same number of incidences (a tile closes
-  // when the next pose would take it past 1.05 x the robot's mean per full tile)
-  // and capped at two chunks of TP * r incidences (two LDS hand-offs in k_hess)
-  std::vector<int> tr, tp0, tnp, rt0(L + 1, 0);
-  // incidences per tile: at most two gather chunks; small problems are cut
-  // finer, to about TILES_TARGET tiles (3 workgroups per CU, one generation),
-  // but not below 180 (3/4 of a chunk). Measured on one 12.5k-pose block
-  // (125k incidences): 160.0 / 156.5 / 154.9 / 152.6 us per round at caps
-  // 480 / 360 / 240 / 180, 207 at 120 (> 1024 tiles: a second generation);
-  // 25k poses: 254.7 at 480, 245.6 at 360, 301 at 240
-  // (profiles/r02/small_round/5_tile_cap.log). kmx_pgo_params.tile_incidences
-  // overrides it (the multi-rank driver sets it from the team; bench.py
-  // --tile-incidences for sweeps).
-  int64_t inc_all = (int64_t)inc_ptr[nloc] - inc_ptr[0];
-  auto cut = [&](int TP, int64_t tilecap) {
-    tr.clear(); tp0.clear(); tnp.clear();
-    for (int l = 0; l < L; ++l) {
-      const int n = n_poses[h->robots[l]];
-      const int base = h->loff[l];
-      rt0[l] = (int)tr.size();
-      const int64_t inc_l = (int64_t)inc_ptr[base + n] - inc_ptr[base];
-      const int64_t full = std::max<int64_t>(1, (n + TP - 1) / TP);
-      const int64_t cap = std::min(tilecap, std::max<int64_t>(1, (inc_l * 21 / 20 + full - 1) / full));
-      int p0 = 0;
-      while (p0 < n) {
-        int np = 0;
-        int64_t cum = 0;
-        while (p0 + np < n && np < TP) {
-          const int64_t dg = inc_ptr[base + p0 + np + 1] - inc_ptr[base + p0 + np];
-          if (np > 0 && cum + dg > cap) break;
-          cum += dg;
-          ++np;
-        }
-        tr.push_back(l);
-        tp0.push_back(base + p0);
-        tnp.push_back(np);
-        p0 += np;
-      }
-    }
-  };
-  {
-    const int TP = WAVES * (64 / r);
-    int64_t tilecap = std::min<int64_t>(2 * (int64_t)TP * r,
-                                        std::max<int64_t>(180, (inc_all + TILES_TARGET - 1) / TILES_TARGET));
-    if (h->P.tile_incidences > 0) tilecap = std::max(16, h->P.tile_incidences);
-    cut(TP, tilecap);
-  }
-  rt0[L] = (int)tr.size();
-  h->rt0_h = rt0;
-  h->ntiles = (int)tr.size();
-  KMX_CHECK(h->ntiles > 0, KMX_EINVAL, "no local poses");
-  {
-    // robot groups: contiguous robot ranges, at most as many as robots have
-    // tiles, cut where the incidence prefix is nearest to g / G of the total
-    // (every group keeps a robot with tiles); a robot without tiles belongs to
-    // the group its index falls in and launches nothing
-    std::vector<int64_t> pre(L + 1, 0);
-    std::vector<int> tiled(L + 1, 0);  // robots with tiles before l
-    for (int l = 0; l < L; ++l) {
-      const int n = n_poses[h->robots[l]], base = h->loff[l];
-      pre[l + 1] = pre[l] + ((int64_t)inc_ptr[base + n] - inc_ptr[base]);
-      tiled[l + 1] = tiled[l] + (rt0[l + 1] > rt0[l] ? 1 : 0);
-    }
-    const int G = std::max(1, std::min(h->groups_req, tiled[L]));
-    std::vector<int> start(G + 1, 0);
-    start[G] = L;
-    for (int g = 1; g < G; ++g) {
-      int best = -1;
-      for (int c = start[g - 1] + 1; c < L; ++c) {
-        // a tiled robot in [start[g - 1], c), and G - g of them left in [c, L)
-        if (tiled[c] == tiled[start[g - 1]] || tiled[L] - tiled[c] < G - g) continue;
-        const int64_t dc = std::llabs(G * pre[c] - g * pre[L]);
-        if (best < 0 || dc < std::llabs(G * pre[best] - g * pre[L])) best = c;
-      }
-      start[g] = best;
-    }
-    h->grp.assign(G, kmx_pgo::Group{});
-    for (int g = 0; g < G; ++g) {
-      kmx_pgo::Group& q = h->grp[g];
-      q.l0 = start[g];
-      q.l1 = start[g + 1];
-      q.t0 = rt0[q.l0];
-      q.nt = rt0[q.l1] - rt0[q.l0];
-    }
-    // the single chain (its polling state outlives the graph, as the handle's poll mode)
-    h->all.l0 = 0; h->all.l1 = L;
-    h->all.t0 = 0; h->all.nt = h->ntiles;
-    // the grouped round's reduction form (kmx_pgo::grm)
-    int most = 0;
-    for (int l = 0; l < L; ++l) most = std::max(most, rt0[l + 1] - rt0[l]);
-    h->grm = h->grm_forced >= 0 ? h->grm_forced
-                                : (most <= kmx_pgo::GROUP_CONSUMER_MAX_TILES ? RM_CONSUMER : RM_LAUNCH);
-  }
-  std::vector<int> own_src(std::max<int64_t>(h->n_owned, 1), 0);
-  for (int64_t k = 0; k < h->n_owned; ++k) own_src[k] = pub_src[h->first_owned + k];
-  std::vector<int> nrob(L);
-  for (int l = 0; l < L; ++l) nrob[l] = n_poses[h->robots[l]];
-  // tile descriptors: validated before any device allocation, so a rejected
-  // graph leaves the handle without buffers (ready() false)
-  std::vector<TileDesc> tdesc(h->ntiles);
-  for (int t = 0; t < h->ntiles; ++t) {
-    TileDesc& td = tdesc[t];
-    td.robot = tr[t];
-    td.p0 = tp0[t];
-    td.k0 = inc_ptr[tp0[t]];
-    const int ninc = inc_ptr[tp0[t] + tnp[t]] - td.k0;
-    KMX_CHECK(tnp[t] < 256 && ninc < (1 << 23), KMX_EINVAL, "tile too large");
-    td.np_n = tnp[t] | (ninc << 8);
-    td.rt0 = rt0[tr[t]];
-    td.rt1 = rt0[tr[t] + 1];
-    td.pad0 = td.pad1 = 0;
-  }
+  // the single chain (its polling state outlives the graph, as the handle's poll mode)
+  h->all.l0 = 0; h->all.l1 = L;
+  h->all.t0 = 0; h->all.nt = h->ntiles;
   // device
   int rc;
   const size_t vec = (size_t)std::max(nloc, 1) * ps;
   if ((rc = dalloc(&h->d_tile, h->ntiles)) || (rc = dalloc(&h->d_rtile0, L + 1)) ||
-      (rc = dalloc(&h->d_inc_ptr, nloc + 1)) || (rc = dalloc(&h->d_rec, rec.size())) || (rc = dalloc(&h->d_rec_o, rec_o.size())) ||
-      (rc = dalloc(&h->d_ekappa, ek_h.size())) || (rc = dalloc(&h->d_etau, et_h.size())) ||
-      (rc = dalloc(&h->d_ew, ew_h.size())) || (rc = dalloc(&h->d_eipos, eipos.size())) ||
+      (rc = dalloc(&h->d_inc_ptr, nloc + 1)) || (rc = dalloc(&h->d_rec, plan.rec.size())) ||
+      (rc = dalloc(&h->d_rec_o, plan.rec_o.size())) || (rc = dalloc(&h->d_ekappa, plan.ek.size())) ||
+      (rc = dalloc(&h->d_etau, plan.et.size())) || (rc = dalloc(&h->d_ew, plan.ew.size())) ||
+      (rc = dalloc(&h->d_eipos, plan.eipos.size())) ||
       (rc = dalloc(&h->d_vec, vec * nvec(h))) || (rc = dalloc(&h->d_S, (size_t)std::max(nloc, 1) * 6)) ||
       (rc = dalloc(&h->d_Pinv, (size_t)std::max(nloc, 1) * SYM4)) ||
       (rc = dalloc(&h->d_hD, (size_t)std::max(nloc, 1) * SYM4)) ||
@@ -4239,8 +3940,8 @@ extern "C" int kmx_pgo_set_graph(kmx_pgo* h, int n_robots, const int32_t* n_pose
       (rc = dalloc(&h->d_ctl2, L)) || (rc = dalloc(&h->d_part_h, (size_t)h->ntiles * 2)) ||
       (rc = dalloc(&h->d_part_u, (size_t)h->ntiles * 2)) ||
       (rc = dalloc(&h->d_cnt, 1)) || (rc = dalloc(&h->d_m_robot, L)) ||
-      (rc = dalloc(&h->d_n_robot, L)) || (rc = dalloc(&h->d_pub_src, pub_src.size())) ||
-      (rc = dalloc(&h->d_own_src, own_src.size())) || (rc = dalloc(&h->d_pose_slot, pose_slot.size())) ||
+      (rc = dalloc(&h->d_n_robot, L)) || (rc = dalloc(&h->d_pub_src, plan.pub_src.size())) ||
+      (rc = dalloc(&h->d_own_src, plan.own_src.size())) || (rc = dalloc(&h->d_pose_slot, plan.pose_slot.size())) ||
       (rc = dalloc(&h->d_gnc_edge, std::max(h->n_gnc, 1))) || (rc = dalloc(&h->d_gnc_ends, std::max(h->n_gnc, 1))) ||
       (rc = dalloc(&h->d_sh_edge, std::max(h->n_sh_local, 1))) ||
       (rc = dalloc(&h->d_sh_idx, std::max(h->n_sh_local, 1))) || (rc = dalloc(&h->d_active, L)) ||
@@ -4253,18 +3954,15 @@ extern "C" int kmx_pgo_set_graph(kmx_pgo* h, int n_robots, const int32_t* n_pose
     return rc;
   }
   h->ext_cap = 64;
-  auto up = [&](void* dst, const void* src, size_t bytes) {
-    return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream);
-  };
-  KMX_HIP(up(h->d_tile, tdesc.data(), sizeof(TileDesc) * tdesc.size()));
-  KMX_HIP(up(h->d_rtile0, rt0.data(), sizeof(int) * rt0.size()));
-  KMX_HIP(up(h->d_inc_ptr, inc_ptr.data(), sizeof(int) * inc_ptr.size()));
-  KMX_HIP(up(h->d_rec, rec.data(), sizeof(double) * rec.size()));
-  KMX_HIP(up(h->d_rec_o, rec_o.data(), sizeof(int) * rec_o.size()));
-  KMX_HIP(up(h->d_ekappa, ek_h.data(), sizeof(double) * ek_h.size()));
-  KMX_HIP(up(h->d_etau, et_h.data(), sizeof(double) * et_h.size()));
-  KMX_HIP(up(h->d_ew, ew_h.data(), sizeof(double) * ew_h.size()));
-  KMX_HIP(up(h->d_eipos, eipos.data(), sizeof(int2) * eipos.size()));
+  KMX_HIP(upload(h, h->d_tile, plan.tile));
+  KMX_HIP(upload(h, h->d_rtile0, plan.rt0));
+  KMX_HIP(upload(h, h->d_inc_ptr, plan.inc_ptr));
+  KMX_HIP(upload(h, h->d_rec, plan.rec));
+  KMX_HIP(upload(h, h->d_rec_o, plan.rec_o));
+  KMX_HIP(upload(h, h->d_ekappa, plan.ek));
+  KMX_HIP(upload(h, h->d_etau, plan.et));
+  KMX_HIP(upload(h, h->d_ew, plan.ew));
+  KMX_HIP(upload(h, h->d_eipos, plan.eipos));
   KMX_HIP(hipMemsetAsync(h->d_vec, 0, sizeof(double) * vec * nvec(h), h->stream));
   KMX_HIP(hipMemsetAsync(h->d_coefh, 0, sizeof(double) * L * std::max(h->P.tcg_max_iterations, 1), h->stream));
   KMX_HIP(hipMemsetAsync(h->d_pub, 0, sizeof(double) * std::max<int64_t>(h->npub, 1) * ps, h->stream));
@@ -4282,33 +3980,25 @@ extern "C" int kmx_pgo_set_graph(kmx_pgo* h, int n_robots, const int32_t* n_pose
   }
   for (int l = 0; l < L; ++l) h->hstat[l].word = 0;
   h->seq = 0;
-  {
-    std::vector<double> relc(L);  // no block update yet: not converged (an empty block is)
-    for (int l = 0; l < L; ++l) relc[l] = nrob[l] > 0 ? std::numeric_limits<double>::infinity() : 0.0;
-    KMX_HIP(up(h->d_relc, relc.data(), sizeof(double) * L));
-    Gnc g0[2] = {};
-    g0[0].mu = g0[1].mu = h->P.gnc_mu_init;
-    KMX_HIP(up(h->d_gnc, g0, sizeof(g0)));
-  }
-  KMX_HIP(up(h->d_m_robot, h->m_robot.data(), sizeof(long long) * L));
-  KMX_HIP(up(h->d_n_robot, nrob.data(), sizeof(int) * L));
-  KMX_HIP(up(h->d_pub_src, pub_src.data(), sizeof(int) * pub_src.size()));
-  KMX_HIP(up(h->d_own_src, own_src.data(), sizeof(int) * own_src.size()));
-  KMX_HIP(up(h->d_pose_slot, pose_slot.data(), sizeof(int) * pose_slot.size()));
-  if (h->n_gnc) {
-    KMX_HIP(up(h->d_gnc_edge, gnc_edge.data(), sizeof(int) * gnc_edge.size()));
-    KMX_HIP(up(h->d_gnc_ends, gnc_ends.data(), sizeof(int2) * gnc_ends.size()));
-  }
-  if (h->n_sh_local) {
-    KMX_HIP(up(h->d_sh_edge, sh_edge.data(), sizeof(int) * sh_edge.size()));
-    KMX_HIP(up(h->d_sh_idx, sh_idx.data(), sizeof(int) * sh_idx.size()));
-  }
-  if (h->n_osh) {
-    KMX_HIP(up(h->d_osh_edge, osh_edge.data(), sizeof(int) * osh_edge.size()));
-    KMX_HIP(up(h->d_osh_idx, osh_idx.data(), sizeof(int) * osh_idx.size()));
-  }
-  std::vector<unsigned char> ones(L, 1);
-  KMX_HIP(up(h->d_active, ones.data(), L));
+  std::vector<double> relc(L);  // no block update yet: not converged (an empty block is)
+  for (int l = 0; l < L; ++l) relc[l] = plan.nrob[l] > 0 ? std::numeric_limits<double>::infinity() : 0.0;
+  KMX_HIP(upload(h, h->d_relc, relc));
+  std::vector<Gnc> g0(2, Gnc{});
+  g0[0].mu = g0[1].mu = h->P.gnc_mu_init;
+  KMX_HIP(upload(h, h->d_gnc, g0));
+  KMX_HIP(upload(h, h->d_m_robot, h->m_robot));
+  KMX_HIP(upload(h, h->d_n_robot, plan.nrob));
+  KMX_HIP(upload(h, h->d_pub_src, plan.pub_src));
+  KMX_HIP(upload(h, h->d_own_src, plan.own_src));
+  KMX_HIP(upload(h, h->d_pose_slot, plan.pose_slot));
+  KMX_HIP(upload(h, h->d_gnc_edge, plan.gnc_edge));
+  KMX_HIP(upload(h, h->d_gnc_ends, plan.gnc_ends));
+  KMX_HIP(upload(h, h->d_sh_edge, plan.sh_edge));
+  KMX_HIP(upload(h, h->d_sh_idx, plan.sh_idx));
+  KMX_HIP(upload(h, h->d_osh_edge, plan.osh_edge));
+  KMX_HIP(upload(h, h->d_osh_idx, plan.osh_idx));
+  const std::vector<unsigned char> ones(L, 1);
+  KMX_HIP(upload(h, h->d_active, ones));
   // host vectors must outlive the async copies
   KMX_HIP(hipStreamSynchronize(h->stream));
   Dev& d = h->dv;
