@@ -1205,6 +1205,140 @@ int kmx_mesh_sync(kmx_mesh* h);
 int kmx_mesh_enable_timing(kmx_mesh* h, int enable);
 int kmx_mesh_read_timing(kmx_mesh* h, double* bind_ms, double* deform_ms);
 
+/* ------------------------------------------------------------------------- */
+/* Deformation graph optimisation (Kimera-PGMO's solve over simplified mesh    */
+/* vertices with keyframe priors; embedded deformation, Sumner et al. 2007):   */
+/* Levenberg-Marquardt with block-Jacobi preconditioned CG                      */
+/* ------------------------------------------------------------------------- */
+/* [U: Kimera-PGMO is not vendored; restated from the published formulas.]
+ * Additive to ABI 10. tests/dgraph_ref.py restates this text in numpy.
+ *
+ * Nodes and unknowns.
+ *  - Nodes are 0..n-1, each with a rest pose (Rrest_i, g_i).
+ *  - A keyframe's rest pose is its odometry pose. A control vertex has
+ *    Rrest = I.
+ *  - The unknown is (R_i, t_i), starting at the rest pose unless the caller
+ *    sets a start.
+ *
+ * Deformation edges.
+ *  - An edge is directed, e = (i -> j, w_e), with w_e finite and >= 0. A
+ *    weight of 0 is kept and skipped.
+ *  - A mesh edge or a keyframe-vertex link is two directed edges.
+ *  - Formed once on the device when the graph is set:
+ *    d_e = Rrest_i^T (g_j - g_i), each entry summed over the inner index in
+ *    order.
+ *  - Residual: r_e = R_i d_e + t_i - t_j. It is zero at rest.
+ *  - Term: w_e |r_e|^2.
+ *
+ * Priors per node. mode_i in {0 none, 1 soft, 2 hard}.
+ *  - Soft adds kappa_i |R_i - Rhat_i|_F^2 + tau_i |t_i - that_i|^2. kappa_i
+ *    and tau_i are finite and >= 0.
+ *  - Hard puts the node at (Rhat_i, that_i) and removes it from the unknowns.
+ *    Its step is 0, and its edges still act on its neighbours.
+ *
+ * Well-posedness, checked on the host.
+ *  - Run a union-find over the edges of weight > 0.
+ *  - Every component must hold a hard node or a soft node with tau > 0.
+ *  - Otherwise return KMX_EINVAL, and the handle stays as it was.
+ *  - A free node whose rotation is not determined (fewer than two non-parallel
+ *    outgoing edges and no kappa) is legal: the damping below keeps it where
+ *    it is.
+ *
+ * Local update.
+ *  - R_i <- Exp(omega_i) R_i (left, world frame) and t_i <- t_i + delta_i.
+ *    That is 6 numbers per free node, in the order (omega, delta).
+ *  - With a_e = R_i d_e the edge's linearisation is
+ *    omega_i x a_e + delta_i - delta_j.
+ *  - So an incidence record needs only `other`, `w` and `a_e`: 36 B, re-formed
+ *    once per outer iteration.
+ *  - The rotation prior's Gauss-Newton block is 2 kappa_i I.
+ *
+ * Levenberg-Marquardt. Cost f = the sum of the terms above; b = J^T r. The
+ * first rules below follow GTSAM's LM with lambda I damping [U].
+ *  - Each outer iteration solves (J^T J + lambda I) delta = -b and forms the
+ *    trial point and its cost f+.
+ *  - Accept iff f+ < f. A NaN f+ is a reject.
+ *  - On accept: lambda <- max(lambda / factor, lambda_min). On reject:
+ *    lambda <- lambda factor.
+ *  - Stop reasons:
+ *    1. an accepted step with f - f+ <= rel_tol f;
+ *    2. f+ <= abs_tol (tested on an accepted step, before reason 1);
+ *    3. max_iterations;
+ *    4. lambda > lambda_max (tested after a reject);
+ *    5. |b| = 0 at the start.
+ *  - Defaults: lambda_init 1e-5, factor 10, lambda_min 1e-10, lambda_max 1e5,
+ *    rel_tol 1e-5, abs_tol 0, max_iterations 100.
+ *
+ * Inner solve.
+ *  - Conjugate gradients from delta = 0, the plain two-reduction form.
+ *  - Preconditioned by the inverse of each free node's 6x6 diagonal block of
+ *    J^T J + lambda I.
+ *  - Stops at |r|_2 <= cg_rtol |b|_2 or cg_max_iterations. Defaults are 1e-6
+ *    and 500.
+ *
+ * Sums are ordered (a node adds its records in edge order, a tile of 64 nodes
+ * reduces by a fixed tree, one wave sums the tiles), so a solve is identical
+ * from run to run and does not depend on check_every. */
+typedef struct kmx_dgraph kmx_dgraph;
+typedef struct {
+  /* 0 (or, for abs_tol and rel_tol, a negative value) in a field: its default */
+  double lambda_init, lambda_factor, lambda_min, lambda_max;
+  double rel_tol;  /* < 0: the default; 0 is 0 */
+  double abs_tol;  /* default 0 */
+  double cg_rtol;
+  int32_t max_iterations, cg_max_iterations;
+  int32_t check_every; /* CG iterations enqueued between two reads of the stop word, default 50 */
+  int32_t reserved;
+} kmx_dgraph_params;
+typedef struct {
+  double cost_initial, cost_final, lambda_final, gradnorm_initial;
+  int32_t iterations;    /* outer iterations run (accepted and rejected) */
+  int32_t accepted;      /* of them accepted */
+  int32_t stop_reason;   /* 1..5 above */
+  int32_t cg_iterations; /* summed over the outer iterations */
+} kmx_dgraph_result;
+typedef struct {
+  double cost, trial_cost, lambda;
+  int32_t cg_iterations, accepted;
+} kmx_dgraph_log_entry;
+enum {
+  KMX_DGRAPH_EVAL_COST = 0,   /* out[1] */
+  KMX_DGRAPH_EVAL_GRAD = 1,   /* out[n][6]: b = J^T r, 0 at hard nodes */
+  KMX_DGRAPH_EVAL_JTJ = 2,    /* out[n][6] = J^T J v for v[n][6]; hard nodes' rows of v are not read */
+  KMX_DGRAPH_EVAL_BLOCKS = 3  /* out[n][21]: the upper triangles of the 6x6 diagonal blocks of J^T J, row by row */
+};
+
+int kmx_dgraph_create(int device, kmx_dgraph** out);
+int kmx_dgraph_destroy(kmx_dgraph* h);
+int kmx_dgraph_set_stream(kmx_dgraph* h, void* hip_stream);
+/* Rrest[n][3][3] row major, g[n][3]; m directed edges src -> dst with weights
+ * w[m] (NULL: all 1). KMX_EINVAL for a null array, n < 0, m < 0, an endpoint
+ * out of range, a self-loop, a value that is not finite or a negative weight.
+ * Poses go to rest and the priors are cleared. */
+int kmx_dgraph_set_graph(kmx_dgraph* h, int32_t n, const double* Rrest, const double* g, int64_t m,
+                         const int32_t* src, const int32_t* dst, const double* w);
+/* New weights for the same edges (NULL: all 1); uploads only. When priors are
+ * set the well-posedness rule is checked against them. A solve after it is
+ * bitwise what a fresh handle built without the zero-weight edges gives. */
+int kmx_dgraph_set_weights(kmx_dgraph* h, const double* w);
+/* mode[n] (uint8), Rhat[n][3][3], that[n][3], kappa[n], tau[n]; rows of nodes
+ * with mode 0 are not read. KMX_ESTATE before set_graph. */
+int kmx_dgraph_set_priors(kmx_dgraph* h, const uint8_t* mode, const double* Rhat, const double* that,
+                          const double* kappa, const double* tau);
+/* R[n][3][3], t[n][3]; both NULL: the rest poses. */
+int kmx_dgraph_set_poses(kmx_dgraph* h, const double* R, const double* t);
+int kmx_dgraph_get_poses(kmx_dgraph* h, double* R, double* t);
+/* At the current point, hard nodes at their priors. v: KMX_DGRAPH_EVAL_JTJ only. */
+int kmx_dgraph_eval(kmx_dgraph* h, int32_t what, const double* v, double* out);
+/* params NULL: every default. result may be NULL. */
+int kmx_dgraph_solve(kmx_dgraph* h, const kmx_dgraph_params* params, kmx_dgraph_result* result);
+/* The last solve's outer iterations: *n_out of them, the first min(cap, *n_out) written to log. */
+int kmx_dgraph_get_log(kmx_dgraph* h, int32_t cap, kmx_dgraph_log_entry* log, int32_t* n_out);
+/* Device times (ms, HIP events) of the last solve: [0] linearise (with the
+ * preconditioner), [1] CG, [2] trial point and decision, [3] total; and [4]
+ * the matrix-free product kernel alone of the last KMX_DGRAPH_EVAL_JTJ. */
+int kmx_dgraph_get_timing(kmx_dgraph* h, double* ms /* [5] */);
+
 #ifdef __cplusplus
 }
 #endif

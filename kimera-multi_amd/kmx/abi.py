@@ -210,6 +210,30 @@ class MeshStats(C.Structure):
                 ("max_displacement", C.c_double), ("sum_sq_displacement", C.c_double)]
 
 
+class DgraphParams(C.Structure):
+    """kmx_dgraph_params (0 in a field: the library's default; rel_tol < 0: its default)."""
+    _fields_ = [("lambda_init", C.c_double), ("lambda_factor", C.c_double), ("lambda_min", C.c_double),
+                ("lambda_max", C.c_double), ("rel_tol", C.c_double), ("abs_tol", C.c_double), ("cg_rtol", C.c_double),
+                ("max_iterations", C.c_int32), ("cg_max_iterations", C.c_int32), ("check_every", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class DgraphResult(C.Structure):
+    """kmx_dgraph_result."""
+    _fields_ = [("cost_initial", C.c_double), ("cost_final", C.c_double), ("lambda_final", C.c_double),
+                ("gradnorm_initial", C.c_double), ("iterations", C.c_int32), ("accepted", C.c_int32),
+                ("stop_reason", C.c_int32), ("cg_iterations", C.c_int32)]
+
+
+class DgraphLogEntry(C.Structure):
+    """kmx_dgraph_log_entry: one per outer iteration."""
+    _fields_ = [("cost", C.c_double), ("trial_cost", C.c_double), ("lam", C.c_double),
+                ("cg_iterations", C.c_int32), ("accepted", C.c_int32)]
+
+
+KMX_DGRAPH_EVAL_COST, KMX_DGRAPH_EVAL_GRAD, KMX_DGRAPH_EVAL_JTJ, KMX_DGRAPH_EVAL_BLOCKS = 0, 1, 2, 3
+DGRAPH_STOP = {1: "rel_tol", 2: "abs_tol", 3: "max_iterations", 4: "lambda_max", 5: "zero_gradient"}
+
 _lib = None
 
 
@@ -383,6 +407,18 @@ def lib() -> C.CDLL:
         "kmx_mesh_sync": ([P], C.c_int),
         "kmx_mesh_enable_timing": ([P, C.c_int], C.c_int),
         "kmx_mesh_read_timing": ([P, pf64, pf64], C.c_int),
+        "kmx_dgraph_create": ([C.c_int, C.POINTER(P)], C.c_int),
+        "kmx_dgraph_destroy": ([P], C.c_int),
+        "kmx_dgraph_set_stream": ([P, P], C.c_int),
+        "kmx_dgraph_set_graph": ([P, i32, pf64, pf64, i64, pi32, pi32, pf64], C.c_int),
+        "kmx_dgraph_set_weights": ([P, pf64], C.c_int),
+        "kmx_dgraph_set_priors": ([P, pu8, pf64, pf64, pf64, pf64], C.c_int),
+        "kmx_dgraph_set_poses": ([P, pf64, pf64], C.c_int),
+        "kmx_dgraph_get_poses": ([P, pf64, pf64], C.c_int),
+        "kmx_dgraph_eval": ([P, i32, pf64, pf64], C.c_int),
+        "kmx_dgraph_solve": ([P, C.POINTER(DgraphParams), C.POINTER(DgraphResult)], C.c_int),
+        "kmx_dgraph_get_log": ([P, i32, C.POINTER(DgraphLogEntry), pi32], C.c_int),
+        "kmx_dgraph_get_timing": ([P, pf64], C.c_int),
     })
     for name, (argt, rest) in sig.items():
         if not hasattr(L, name):

@@ -250,7 +250,7 @@ def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, ran
                  device: int = 0, rounds: int = 100, verifier=None, solver=None, exchange_device=None,
                  return_trajectory: bool = False, local_init: str = "odometry", certify_eta=None,
                  staircase_rmax=None, staircase_kw=None, mesh=None, mesh_k: int = 4,
-                 mesh_window_s: float = 1.0) -> dict:
+                 mesh_window_s: float = 1.0, mesh_graph=None) -> dict:
     """One team run: LCD verification of this rank's candidates (query robot
     in the rank's robot range) -> all_gather of the accepted loop closures ->
     team graph -> global initialisation -> `rounds` concurrent RBCD rounds
@@ -285,8 +285,13 @@ def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, ran
     rmse_before_m and rmse_after_m against mesh.gt_xyz, both expressed
     relative to the anchor robot's first pose as ate_rmse does (before: the
     vertices as given, in their robots' odometry frames), and with
-    return_trajectory "xyz", the deformed vertices. Returns stage timings and
-    metrics (identical on every rank)."""
+    return_trajectory "xyz", the deformed vertices. mesh_graph (needs mesh; a
+    voxel resolution in metres): the mesh is simplified at that resolution,
+    the deformation graph over keyframes and control vertices is solved on the
+    device with soft priors on the keyframes at the rounded RBCD trajectory
+    (kmx.pgmo.DeformationGraph), and the vertices are bound to and moved by
+    the graph's nodes; the "mesh" entry gains "graph" (see deform_mesh).
+    Returns stage timings and metrics (identical on every rank)."""
     import time
 
     if certify_eta is not None and world > 1:
@@ -297,6 +302,8 @@ def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, ran
         raise ValueError("staircase_rmax needs world == 1: the team's iterate is not on one rank")
     if mesh is not None and world > 1:
         raise ValueError("mesh needs world == 1: the team's trajectory and the mesh are on one rank")
+    if mesh_graph is not None and mesh is None:
+        raise ValueError("mesh_graph needs mesh: the graph is built from the mesh")
 
     from .dpgo.driver import RBCDDriver, robot_ranges
     from .synth.pose_graph import lift, lifting_matrix
@@ -399,7 +406,7 @@ def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, ran
                 out["staircase"]["trajectory"] = traj
     if mesh is not None:
         out["mesh"] = deform_mesh(g, mesh, odometry_init(g), mine, k=mesh_k, window_s=mesh_window_s, device=device,
-                                  return_xyz=return_trajectory)
+                                  return_xyz=return_trajectory, graph_resolution=mesh_graph)
     if hasattr(drv.solver, "close"):
         drv.solver.close()
     return out
@@ -417,15 +424,61 @@ def mesh_rmse(g: PoseGraphData, xyz, gt_xyz, traj: dict, *, anchor_robot: int = 
 
 
 def deform_mesh(g: PoseGraphData, mesh, rest: dict, current: dict, *, k: int = 4, window_s: float = 1.0,
-                device: int = 0, return_xyz: bool = False) -> dict:
+                device: int = 0, return_xyz: bool = False, graph_resolution=None, graph_kappa: float = 100.0,
+                graph_tau: float = 100.0, graph_solve=None, graph_horizon_s=None) -> dict:
     """The mesh stage of run_pipeline: keyframes of every robot as control
-    nodes (rest[a] -> current[a]), one bind and one deformation on the device."""
+    nodes (rest[a] -> current[a]), one bind and one deformation on the device.
+    graph_resolution (metres; default None: off): the mesh is simplified on a
+    voxel grid of that size (kmx.pgmo.simplify_voxel; graph_horizon_s: its
+    horizon_s), the deformation graph of
+    keyframes and control vertices (graph_from_mesh, all edge weights 1) is
+    solved on the device with soft priors (graph_kappa, graph_tau) on the
+    keyframes at current[a] (graph_solve: DeformationGraph.solve's keywords),
+    starting from every control vertex moved by its keyframe's correction, and
+    the vertices are bound to and moved by the graph's nodes. The result
+    then has "graph": nodes, edges, control_vertices, iterations, accepted,
+    stop, cost_before, cost_after and solve_ms (device time)."""
     from .pgmo import MeshDeformer
-    md = MeshDeformer(k=k, window_s=window_s, n_robots=g.n_robots, device=device)
+    graph = None
+    if graph_resolution is None:
+        md = MeshDeformer(k=k, window_s=window_s, n_robots=g.n_robots, device=device)
+    else:
+        from .pgmo import DeformationGraph, graph_from_mesh, simplify_voxel
+        cx, cs, cr, cf, _ = simplify_voxel(mesh.xyz, mesh.faces, mesh.stamp, mesh.robot, graph_resolution,
+                                           horizon_s=graph_horizon_s)
+        G = graph_from_mesh(cx, cs, cr, cf, mesh.kf_stamp, [rest[a] for a in range(g.n_robots)])
+        nk, n = G["n_keyframes"], G["g"].shape[0]
+        mode = np.zeros(n, np.uint8)
+        mode[:nk] = 1
+        R_hat, t_hat = G["R_rest"].copy(), G["g"].copy()
+        R_hat[:nk] = np.concatenate([current[a][0] for a in range(g.n_robots)])
+        t_hat[:nk] = np.concatenate([current[a][1] for a in range(g.n_robots)])
+        dg = DeformationGraph(device)
+        try:
+            dg.set_graph(G["R_rest"], G["g"], G["src"], G["dst"], G["w"], robot=G["robot"], stamp=G["stamp"])
+            dg.set_priors(mode, R_hat, t_hat, graph_kappa, graph_tau)
+            # the start: every control vertex follows its keyframe's rigid correction C = Rcur Rrest^T. A vertex
+            # with fewer than two non-parallel outgoing edges keeps the part of C its edges do not determine.
+            C_kf = R_hat[:nk] @ G["R_rest"][:nk].transpose(0, 2, 1)
+            lk = G["link"]
+            R0, t0 = R_hat.copy(), t_hat.copy()
+            R0[nk:] = C_kf[lk]
+            t0[nk:] = np.einsum("nij,nj->ni", C_kf[lk], G["g"][nk:] - G["g"][lk]) + t_hat[lk]
+            dg.set_poses(R0, t0)
+            res = dg.solve(**(graph_solve or {}))
+            graph = {"nodes": n, "edges": int(G["src"].shape[0]), "control_vertices": n - nk,
+                     "iterations": res["iterations"], "accepted": res["accepted"], "stop": res["stop"],
+                     "cost_before": res["cost_initial"], "cost_after": res["cost_final"],
+                     "solve_ms": dg.timing()["total_ms"]}
+            md = dg.deformer(k, window_s, n_robots=g.n_robots)
+            dg.push(md)
+        finally:
+            dg.close()
     try:
-        for a in range(g.n_robots):
-            md.add_keyframes(a, mesh.kf_stamp[a], rest[a][0], rest[a][1])
-            md.update_trajectory(a, current[a][0], current[a][1])
+        if graph is None:
+            for a in range(g.n_robots):
+                md.add_keyframes(a, mesh.kf_stamp[a], rest[a][0], rest[a][1])
+                md.update_trajectory(a, current[a][0], current[a][1])
         md.add_vertices(mesh.robot, mesh.stamp, mesh.xyz)
         xyz, st = md.deform()
         tm = md.timing()
@@ -435,6 +488,8 @@ def deform_mesh(g: PoseGraphData, mesh, rest: dict, current: dict, *, k: int = 4
            "deform_seconds": tm["deform_ms"] * 1e-3,
            "rmse_before_m": mesh_rmse(g, mesh.xyz, mesh.gt_xyz, rest),
            "rmse_after_m": mesh_rmse(g, xyz, mesh.gt_xyz, current)}
+    if graph is not None:
+        res["graph"] = graph
     if return_xyz:
         res["xyz"] = xyz
     return res

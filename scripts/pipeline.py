@@ -42,6 +42,9 @@ def main():
     ap.add_argument("--mesh", type=int, default=None, metavar="N",
                     help="one GPU only: a synthetic mesh of N vertices per keyframe (kmx.synth.mesh.make_mesh) "
                          "follows the result on the device; the result gets a 'mesh' entry")
+    ap.add_argument("--mesh-graph", type=float, default=None, metavar="RES",
+                    help="with --mesh: simplify the mesh on a voxel grid of RES metres, solve the deformation graph "
+                         "over keyframes and control vertices on the device and deform through its nodes")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -60,6 +63,8 @@ def main():
     g0 = make_pose_graph(a.robots, n, int(a.edges_per_pose * n), f_inter=0.0, outlier_scope="robot",
                          sigma_R=a.sigma_r, sigma_t=a.sigma_t, seed=a.seed)
     stream = PL.make_lc_stream(g0, a.robots * a.true_per_robot, a.robots * a.false_per_robot, seed=a.seed + 1)
+    if a.mesh_graph is not None and a.mesh is None:
+        ap.error("--mesh-graph needs --mesh")
     mesh = None
     if a.mesh is not None:
         from kmx.synth.mesh import make_mesh
@@ -67,7 +72,7 @@ def main():
     gen = time.perf_counter() - t0
     out = PL.run_pipeline(g0, stream, bench.params(), LcdParams(), rank=rank, world=world, device=local_rank,
                           rounds=a.rounds, local_init=a.local_init, certify_eta=a.certify,
-                          staircase_rmax=a.staircase, mesh=mesh)
+                          staircase_rmax=a.staircase, mesh=mesh, mesh_graph=a.mesh_graph)
     out["config"] = {"workload": f"configs[4]: {a.robots} robots x {a.poses} poses, {g0.m} base edges "
                                  f"(intra-robot loop closures, 20% intra outliers, odometry noise "
                                  f"{a.sigma_r} rad / {a.sigma_t} m), LC stream "
