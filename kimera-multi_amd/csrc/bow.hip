@@ -34,6 +34,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -1144,170 +1145,113 @@ __global__ void k_bow_detect_prep(int nq, int mode, int window, int use_nss, Bow
   nss[t] = use_nss ? entry_score(src, id, id - 1) : 0.0;
 }
 
-template <typename T>
-int bow_alloc(T** p, size_t n) {
-  *p = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * std::max<size_t>(n, 1));
-  if (e != hipSuccess) return kmx::fail(KMX_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-  return 0;
-}
+// The handle's device buffers in the six sets that live and die together. A
+// set is replaced as a whole (h->qry = BowQuerySet()) and a grown one is built
+// aside and moved in, so no buffer is named again to be freed.
+struct BowDbSet {  // the inverted file over [0, n_sealed) and the base query's scratch
+  kmx::DevBuf<int> ptr, ent;  // ent / wt hold ent.cap() postings
+  kmx::DevBuf<double> wt;
+  int n_wg = 0;
+  kmx::DevBuf<double> acc;  // HBM-accumulator query: acc.cap() per-workgroup slots, with touched
+  kmx::DevBuf<int> touched;
+  kmx::DevBuf<int> cptr;  // LDS-accumulator query (k_bow_query_lds): per-word chunk split points
+};
+struct BowQuerySet {  // query scratch: qptr.cap() queries (+ 1), qw.cap() words, id.cap() results
+  kmx::DevBuf<long long> qptr;
+  kmx::DevBuf<unsigned> qw;
+  kmx::DevBuf<double> qv;
+  kmx::DevBuf<int> maxid, n, id;
+  kmx::DevBuf<double> score;
+};
+struct BowPairSet {  // pair-score scratch: aptr.cap() pairs (+ 1), aw.cap() words a side
+  kmx::DevBuf<long long> aptr, bptr;
+  kmx::DevBuf<unsigned> aw, bw;
+  kmx::DevBuf<double> av, bv, out;
+};
+struct BowFwdSet {  // the forward store (every entry's vector) and the seal's grow-only scratch
+  kmx::DevBuf<long long> fptr;  // [fe_cap() + 1]
+  kmx::DevBuf<unsigned> fw;     // [fw.cap()] postings, with fv
+  kmx::DevBuf<double> fv;
+  std::vector<int64_t> h_fptr{0};  // host mirror of fptr (8 bytes per entry; no words or weights)
+  kmx::DevBuf<int> cnt, tmp_e;
+  kmx::DevBuf<double> tmp_v;  // allocated after tmp_e: its capacity is the pair's
+  size_t fe_cap() const { return fptr.cap() ? fptr.cap() - 1 : 0; }
+};
+struct BowIdSet {  // entry-id scratch: eid [2 cap()], eout [cap()]
+  kmx::DevBuf<int> eid;
+  kmx::DevBuf<double> eout;
+  size_t cap() const { return eout.cap(); }
+};
+struct BowDetSet {  // detection scratch (grow-only) and the result block with its pinned host mirror
+  kmx::DevBuf<int> hasprev;  // [cap()] has_prev, then [cap()] k_bow_decide's match ids
+  kmx::DevBuf<int4> tin;
+  kmx::DevBuf<char> dout;
+  kmx::PinnedBuf<char> h_dout;
+  int nq = -1;  // the enqueued call's query count (kmx_bow_detect_fetch)
+  size_t cap() const { return tin.cap(); }
+};
 
 }  // namespace
 
-struct kmx_bow {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+struct kmx_bow : kmx::StreamCore {
   int n_words = 0, n_entries = 0;
-  int *d_ptr = nullptr, *d_ent = nullptr;
-  double* d_wt = nullptr;
-  // query scratch
-  int n_wg = 0;
-  double* d_acc = nullptr;
-  int* d_touched = nullptr;
-  int* d_err = nullptr;
-  // LDS-accumulator query (k_bow_query_lds): per-word chunk split points
+  BowDbSet db;
+  kmx::DevBuf<int> d_err;
   bool lds = true;
   int ch = 0, nch = 0;
-  int* d_cptr = nullptr;
-  size_t qcap = 0, wcap = 0;
-  long long* d_qptr = nullptr;
-  unsigned* d_qw = nullptr;
-  double* d_qv = nullptr;
-  int* d_maxid = nullptr;
-  int *d_n = nullptr, *d_id = nullptr;
-  double* d_score = nullptr;
-  size_t rcap = 0;
-  // pair-score scratch
-  size_t pcap = 0, pwcap = 0;
-  long long *d_aptr = nullptr, *d_bptr = nullptr;
-  unsigned *d_aw = nullptr, *d_bw = nullptr;
-  double *d_av = nullptr, *d_bv = nullptr, *d_pout = nullptr;
-  // streaming database: entries [0, n_sealed) are in the inverted file above,
-  // [n_sealed, n_entries) only in the forward store (every entry's vector)
+  BowQuerySet qry;
+  BowPairSet pair;
+  // streaming database: entries [0, n_sealed) are in the inverted file,
+  // [n_sealed, n_entries) only in the forward store
   int n_sealed = 0;
   int tail_cap = TAIL_DEFAULT, tail_cap_set = TAIL_DEFAULT;
-  size_t fe_cap = 0, fp_cap = 0;  // forward store capacity: entries, postings
-  long long* d_fptr = nullptr;
-  unsigned* d_fw = nullptr;
-  double* d_fv = nullptr;
-  std::vector<int64_t> h_fptr{0};  // host mirror of d_fptr (8 bytes per entry; no words or weights)
-  size_t base_cap = 0;             // ints at d_ent / doubles at d_wt
-  size_t cptr_cap = 0, scratch_cap = 0;
-  hipEvent_t ev = nullptr;         // orders this handle after another handle's stream
-  // seal scratch (grow-only) and entry-id scratch
-  int* d_cnt = nullptr;
-  size_t tmp_cap = 0;
-  int* d_tmp_e = nullptr;
-  double* d_tmp_v = nullptr;
-  size_t ecap = 0;
-  int* d_eid = nullptr;
-  double* d_eout = nullptr;
+  BowFwdSet fwd;
+  kmx::Event ev;  // orders this handle after another handle's stream
+  BowIdSet ids;
   // detection on the device: the temporal constraint's state (4 ints, then 4
-  // of scratch for a pass that leaves the state alone), grow-only scratch and
-  // the result block [records nq][n_cand, error][cand 2 * nq], with its
-  // pinned host mirror so that one copy brings a call's results back
-  int* d_tstate = nullptr;
-  size_t dcap = 0;
-  int* d_hasprev = nullptr;        // [dcap] has_prev, then [dcap] k_bow_decide's match ids
-  int4* d_tin = nullptr;
-  char *d_dout = nullptr, *h_dout = nullptr;
-  int det_nq = -1;                 // the enqueued call's query count (kmx_bow_detect_fetch)
+  // of scratch for a pass that leaves the state alone), and the result block
+  // [records nq][n_cand, error][cand 2 * nq], mirrored in pinned host memory
+  // so that one copy brings a call's results back
+  kmx::DevBuf<int> d_tstate;
+  BowDetSet det;
   bool timing = false;
-  hipEvent_t tev[4] = {nullptr, nullptr, nullptr, nullptr};
+  kmx::Event tev[4];  // created by the first timed detection
 };
 
 namespace {
-void bow_free_db(kmx_bow* h) {
-  for (void* p : {(void*)h->d_ptr, (void*)h->d_ent, (void*)h->d_wt, (void*)h->d_acc, (void*)h->d_touched,
-                  (void*)h->d_cptr})
-    if (p) (void)hipFree(p);
-  h->d_ptr = h->d_ent = h->d_cptr = nullptr;
-  h->d_wt = nullptr;
-  h->d_acc = nullptr;
-  h->d_touched = nullptr;
-  h->n_wg = 0;
-  h->base_cap = h->cptr_cap = h->scratch_cap = 0;
-}
-void bow_free_fwd(kmx_bow* h) {
-  for (void* p : {(void*)h->d_fptr, (void*)h->d_fw, (void*)h->d_fv, (void*)h->d_cnt, (void*)h->d_tmp_e,
-                  (void*)h->d_tmp_v})
-    if (p) (void)hipFree(p);
-  h->d_fptr = nullptr; h->d_fw = nullptr; h->d_fv = nullptr;
-  h->d_cnt = h->d_tmp_e = nullptr; h->d_tmp_v = nullptr;
-  h->fe_cap = h->fp_cap = h->tmp_cap = 0;
-  h->h_fptr.assign(1, 0);
-}
-void bow_free_e(kmx_bow* h) {
-  if (h->d_eid) (void)hipFree(h->d_eid);
-  if (h->d_eout) (void)hipFree(h->d_eout);
-  h->d_eid = nullptr; h->d_eout = nullptr;
-  h->ecap = 0;
-}
-void bow_free_d(kmx_bow* h) {
-  for (void* p : {(void*)h->d_hasprev, (void*)h->d_tin, (void*)h->d_dout})
-    if (p) (void)hipFree(p);
-  if (h->h_dout) (void)hipHostFree(h->h_dout);
-  h->d_hasprev = nullptr; h->d_tin = nullptr; h->d_dout = nullptr; h->h_dout = nullptr;
-  h->dcap = 0;
-  h->det_nq = -1;
-}
-void bow_free_q(kmx_bow* h) {
-  for (void* p : {(void*)h->d_qptr, (void*)h->d_qw, (void*)h->d_qv, (void*)h->d_maxid, (void*)h->d_n,
-                  (void*)h->d_id, (void*)h->d_score})
-    if (p) (void)hipFree(p);
-  h->d_qptr = nullptr; h->d_qw = nullptr; h->d_qv = nullptr; h->d_maxid = nullptr;
-  h->d_n = h->d_id = nullptr; h->d_score = nullptr;
-  h->qcap = h->wcap = h->rcap = 0;
-}
-void bow_free_p(kmx_bow* h) {
-  for (void* p : {(void*)h->d_aptr, (void*)h->d_bptr, (void*)h->d_aw, (void*)h->d_bw, (void*)h->d_av,
-                  (void*)h->d_bv, (void*)h->d_pout})
-    if (p) (void)hipFree(p);
-  h->d_aptr = h->d_bptr = nullptr; h->d_aw = h->d_bw = nullptr;
-  h->d_av = h->d_bv = h->d_pout = nullptr;
-  h->pcap = h->pwcap = 0;
-}
-
 // Room in the forward store for ne entries and np postings: capacity
 // doubling, one device-to-device copy of what is held per doubling.
 int bow_fwd_reserve(kmx_bow* h, size_t ne, size_t np) {
-  const bool grow_e = !h->d_fptr || ne > h->fe_cap, grow_p = !h->d_fw || np > h->fp_cap;
+  BowFwdSet& F = h->fwd;
+  const bool grow_e = !F.fptr.get() || ne > F.fe_cap(), grow_p = !F.fw.get() || np > F.fw.cap();
   if (!grow_e && !grow_p) return 0;
-  const size_t held_e = (size_t)h->n_entries + 1, held_p = (size_t)h->h_fptr.back();
-  long long* nf = nullptr;
-  unsigned* nw = nullptr;
-  double* nv = nullptr;
+  const size_t held_e = (size_t)h->n_entries + 1, held_p = (size_t)F.h_fptr.back();
+  kmx::DevBuf<long long> nf;
+  kmx::DevBuf<unsigned> nw;
+  kmx::DevBuf<double> nv;
   int rc = 0;
-  const size_t ec = std::max<size_t>({ne, 2 * h->fe_cap, 1024}), pc = std::max<size_t>({np, 2 * h->fp_cap, 65536});
-  if (grow_e) rc = bow_alloc(&nf, ec + 1);
-  if (!rc && grow_p) rc = bow_alloc(&nw, pc);
-  if (!rc && grow_p) rc = bow_alloc(&nv, pc);
+  const size_t ec = std::max<size_t>({ne, 2 * F.fe_cap(), 1024}), pc = std::max<size_t>({np, 2 * F.fw.cap(), 65536});
+  if (grow_e) rc = nf.alloc(ec + 1);
+  if (!rc && grow_p) rc = nw.alloc(pc);
+  if (!rc && grow_p) rc = nv.alloc(pc);
+  if (rc) return rc;
   hipError_t e = hipSuccess;
-  if (!rc && grow_e)
-    e = h->d_fptr ? hipMemcpyAsync(nf, h->d_fptr, sizeof(long long) * held_e, hipMemcpyDeviceToDevice, h->stream)
-                  : hipMemsetAsync(nf, 0, sizeof(long long), h->stream);
-  if (!rc && grow_p && h->d_fw && held_p) {
-    if (e == hipSuccess) e = hipMemcpyAsync(nw, h->d_fw, sizeof(unsigned) * held_p, hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(nv, h->d_fv, sizeof(double) * held_p, hipMemcpyDeviceToDevice, h->stream);
+  if (grow_e)
+    e = F.fptr.get()
+            ? hipMemcpyAsync(nf.get(), F.fptr.get(), sizeof(long long) * held_e, hipMemcpyDeviceToDevice, h->stream)
+            : hipMemsetAsync(nf.get(), 0, sizeof(long long), h->stream);
+  if (grow_p && F.fw.get() && held_p) {
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(nw.get(), F.fw.get(), sizeof(unsigned) * held_p, hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(nv.get(), F.fv.get(), sizeof(double) * held_p, hipMemcpyDeviceToDevice, h->stream);
   }
-  if (!rc && e == hipSuccess) e = hipStreamSynchronize(h->stream);  // queries in flight read the old store
-  if (rc || e != hipSuccess) {
-    for (void* p : {(void*)nf, (void*)nw, (void*)nv})
-      if (p) (void)hipFree(p);
-    return rc ? rc : kmx::fail(KMX_EHIP, std::string("forward store: ") + hipGetErrorString(e));
-  }
-  if (grow_e) {
-    if (h->d_fptr) (void)hipFree(h->d_fptr);
-    h->d_fptr = nf;
-    h->fe_cap = ec;
-  }
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // queries in flight read the old store
+  if (e != hipSuccess) return kmx::fail(KMX_EHIP, std::string("forward store: ") + hipGetErrorString(e));
+  if (grow_e) F.fptr = std::move(nf);
   if (grow_p) {
-    if (h->d_fw) (void)hipFree(h->d_fw);
-    if (h->d_fv) (void)hipFree(h->d_fv);
-    h->d_fw = nw;
-    h->d_fv = nv;
-    h->fp_cap = pc;
+    F.fw = std::move(nw);
+    F.fv = std::move(nv);
   }
   return 0;
 }
@@ -1320,84 +1264,63 @@ int bow_seal(kmx_bow* h) {
   const int n = h->n_entries, e0 = h->n_sealed, nw = h->n_words;
   if (n == e0) return KMX_OK;
   KMX_HIP(hipSetDevice(h->device));
-  const long long p0 = h->h_fptr[e0], p1 = h->h_fptr[n];
+  const long long p0 = h->fwd.h_fptr[e0], p1 = h->fwd.h_fptr[n];
   const size_t n_tail = (size_t)(p1 - p0), n_new = (size_t)p1;
   int rc = 0;
-  if (!h->d_cnt && (rc = bow_alloc(&h->d_cnt, (size_t)nw + 1))) return rc;
-  if (n_tail > h->tmp_cap || !h->d_tmp_e) {
-    if (h->d_tmp_e) (void)hipFree(h->d_tmp_e);
-    if (h->d_tmp_v) (void)hipFree(h->d_tmp_v);
-    h->d_tmp_e = nullptr;
-    h->d_tmp_v = nullptr;
-    h->tmp_cap = 0;
+  if (!h->fwd.cnt.get() && (rc = h->fwd.cnt.alloc((size_t)nw + 1))) return rc;
+  if (n_tail > h->fwd.tmp_v.cap() || !h->fwd.tmp_v.get()) {
+    h->fwd.tmp_e.reset();
+    h->fwd.tmp_v.reset();
     const size_t cap = std::max<size_t>(n_tail, 65536);
-    if ((rc = bow_alloc(&h->d_tmp_e, cap)) || (rc = bow_alloc(&h->d_tmp_v, cap))) return rc;
-    h->tmp_cap = cap;
+    if ((rc = h->fwd.tmp_e.alloc(cap)) || (rc = h->fwd.tmp_v.alloc(cap))) return rc;
   }
   const int nch = std::max(1, (n + h->ch - 1) / h->ch), nsub = nch * LW_WAVES, sch = h->ch / LW_WAVES;
   const size_t cneed = h->lds ? (size_t)nw * (nsub + 1) : 0;
-  const size_t sneed = h->lds ? 1 : (size_t)h->n_wg * std::max(n, 1);
-  int *new_ptr = nullptr, *new_ent = nullptr, *new_cptr = nullptr, *new_touched = nullptr;
-  double *new_wt = nullptr, *new_acc = nullptr;
-  auto drop = [&]() {
-    for (void* p : {(void*)new_ptr, (void*)new_ent, (void*)new_wt, (void*)new_cptr, (void*)new_acc,
-                    (void*)new_touched})
-      if (p) (void)hipFree(p);
-  };
-  if ((rc = bow_alloc(&new_ptr, (size_t)nw + 1)) || (rc = bow_alloc(&new_ent, n_new)) ||
-      (rc = bow_alloc(&new_wt, n_new)) || (cneed > h->cptr_cap && (rc = bow_alloc(&new_cptr, cneed))) ||
-      (sneed > h->scratch_cap && ((rc = bow_alloc(&new_acc, sneed)) || (rc = bow_alloc(&new_touched, sneed))))) {
-    drop();
+  const size_t sneed = h->lds ? 1 : (size_t)h->db.n_wg * std::max(n, 1);
+  // the new file is built aside: an early return frees it and the handle keeps the old one
+  BowDbSet nb;
+  if ((rc = nb.ptr.alloc((size_t)nw + 1)) || (rc = nb.ent.alloc(n_new)) || (rc = nb.wt.alloc(n_new)) ||
+      (cneed > h->db.cptr.cap() && (rc = nb.cptr.alloc(cneed))) ||
+      (sneed > h->db.acc.cap() && ((rc = nb.acc.alloc(sneed)) || (rc = nb.touched.alloc(sneed)))))
     return rc;
-  }
-  BowFwd f{h->d_fptr, h->d_fw, h->d_fv};
-  hipError_t e = hipMemsetAsync(h->d_cnt, 0, sizeof(int) * ((size_t)nw + 1), h->stream);
+  int *new_ptr = nb.ptr.get(), *new_ent = nb.ent.get(), *new_cptr = nb.cptr.get();
+  double *new_wt = nb.wt.get(), *new_acc = nb.acc.get();
+  BowFwd f{h->fwd.fptr.get(), h->fwd.fw.get(), h->fwd.fv.get()};
+  hipError_t e = hipMemsetAsync(h->fwd.cnt.get(), 0, sizeof(int) * ((size_t)nw + 1), h->stream);
   if (e == hipSuccess && n_tail) {
     const int grid = (int)std::min<size_t>((n_tail + 255) / 256, 2048);
-    hipLaunchKernelGGL(k_bow_seal_count, dim3(grid), dim3(256), 0, h->stream, (const unsigned*)h->d_fw, p0, p1, nw,
-                       h->d_cnt);
+    hipLaunchKernelGGL(k_bow_seal_count, dim3(grid), dim3(256), 0, h->stream, (const unsigned*)h->fwd.fw.get(), p0, p1,
+                       nw, h->fwd.cnt.get());
   }
   if (e == hipSuccess)
-    hipLaunchKernelGGL(k_bow_seal_ptr, dim3(1), dim3(TL_BLOCK), 0, h->stream, nw, (const int*)h->d_ptr,
-                       (const int*)h->d_cnt, new_ptr);
-  if (e == hipSuccess) e = hipMemsetAsync(h->d_cnt, 0, sizeof(int) * ((size_t)nw + 1), h->stream);
+    hipLaunchKernelGGL(k_bow_seal_ptr, dim3(1), dim3(TL_BLOCK), 0, h->stream, nw, (const int*)h->db.ptr.get(),
+                       (const int*)h->fwd.cnt.get(), new_ptr);
+  if (e == hipSuccess) e = hipMemsetAsync(h->fwd.cnt.get(), 0, sizeof(int) * ((size_t)nw + 1), h->stream);
   if (e == hipSuccess && n_tail)
     hipLaunchKernelGGL(k_bow_seal_fill, dim3(std::min((n - e0 + 3) / 4, 2048)), dim3(256), 0, h->stream, f, e0, n, nw,
-                       (const int*)h->d_ptr, (const int*)new_ptr, h->d_cnt, h->d_tmp_e, h->d_tmp_v, (int)n_tail);
+                       (const int*)h->db.ptr.get(), (const int*)new_ptr, h->fwd.cnt.get(), h->fwd.tmp_e.get(),
+                       h->fwd.tmp_v.get(), (int)n_tail);
   if (e == hipSuccess)
     hipLaunchKernelGGL(k_bow_seal_place, dim3(std::min((nw + 3) / 4, 4096)), dim3(256), 0, h->stream, nw,
-                       (const int*)h->d_ptr, (const int*)new_ptr, (const int*)h->d_ent, (const double*)h->d_wt,
-                       (const int*)h->d_tmp_e, (const double*)h->d_tmp_v, new_ent, new_wt);
+                       (const int*)h->db.ptr.get(), (const int*)new_ptr, (const int*)h->db.ent.get(),
+                       (const double*)h->db.wt.get(), (const int*)h->fwd.tmp_e.get(), (const double*)h->fwd.tmp_v.get(),
+                       new_ent, new_wt);
   if (e == hipSuccess && h->lds) {  // in place when the table keeps its shape: only earlier queries read it
     const int grid = (int)std::min<size_t>((cneed + 255) / 256, 4096);
     hipLaunchKernelGGL(k_bow_cptr, dim3(grid), dim3(256), 0, h->stream, nw, nsub, sch, (const int*)new_ptr,
-                       (const int*)new_ent, new_cptr ? new_cptr : h->d_cptr);
+                       (const int*)new_ent, new_cptr ? new_cptr : h->db.cptr.get());
   }
   if (e == hipSuccess && new_acc) e = hipMemsetAsync(new_acc, 0, sizeof(double) * sneed, h->stream);
   if (e == hipSuccess) e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // the old arrays are read until here
-  if (e != hipSuccess) {
-    drop();
-    return kmx::fail(KMX_EHIP, std::string("kmx_bow_seal: ") + hipGetErrorString(e));
-  }
-  (void)hipFree(h->d_ptr);
-  (void)hipFree(h->d_ent);
-  (void)hipFree(h->d_wt);
-  h->d_ptr = new_ptr;
-  h->d_ent = new_ent;
-  h->d_wt = new_wt;
-  h->base_cap = std::max<size_t>(n_new, 1);
-  if (new_cptr) {
-    if (h->d_cptr) (void)hipFree(h->d_cptr);
-    h->d_cptr = new_cptr;
-    h->cptr_cap = cneed;
-  }
+  if (e != hipSuccess) return kmx::fail(KMX_EHIP, std::string("kmx_bow_seal: ") + hipGetErrorString(e));
+  h->db.ptr = std::move(nb.ptr);
+  h->db.ent = std::move(nb.ent);
+  h->db.wt = std::move(nb.wt);
+  if (new_cptr) h->db.cptr = std::move(nb.cptr);
   if (new_acc) {
-    (void)hipFree(h->d_acc);
-    (void)hipFree(h->d_touched);
-    h->d_acc = new_acc;
-    h->d_touched = new_touched;
-    h->scratch_cap = sneed;
+    h->db.acc = std::move(nb.acc);
+    h->db.touched = std::move(nb.touched);
   }
   h->nch = nch;
   h->n_sealed = n;
@@ -1408,62 +1331,25 @@ int bow_seal(kmx_bow* h) {
 extern "C" int kmx_bow_create(int device, kmx_bow** out) {
   KMX_GUARD_BEGIN
   KMX_CHECK(out, KMX_EINVAL, "null argument");
-  int ndev = 0;
-  KMX_HIP(hipGetDeviceCount(&ndev));
-  KMX_CHECK(device >= 0 && device < ndev, KMX_EINVAL, "bad HIP device ordinal");
-  KMX_HIP(hipSetDevice(device));
-  kmx_bow* h = new kmx_bow();
-  h->device = device;
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-    delete h;
-    return kmx::fail(KMX_EHIP, "hipStreamCreate failed");
-  }
-  h->own_stream = true;
-  if (hipMalloc(reinterpret_cast<void**>(&h->d_err), 2 * sizeof(int)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&h->d_tstate), 8 * sizeof(int)) != hipSuccess ||
-      hipMemset(h->d_tstate, 0, 8 * sizeof(int)) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev, hipEventDisableTiming) != hipSuccess) {
-    if (h->d_err) (void)hipFree(h->d_err);
-    if (h->d_tstate) (void)hipFree(h->d_tstate);
-    (void)hipStreamDestroy(h->stream);
-    delete h;
-    return kmx::fail(KMX_ENOMEM, "hipMalloc failed");
-  }
-  *out = h;
+  std::unique_ptr<kmx_bow> h(new kmx_bow());
+  int rc;
+  if ((rc = h->open(device)) || (rc = h->d_err.alloc(2)) || (rc = h->d_tstate.alloc(8))) return rc;
+  // these two have always been reported with the allocations' code
+  if (hipMemset(h->d_tstate.get(), 0, 8 * sizeof(int)) != hipSuccess || h->ev.create(hipEventDisableTiming))
+    return kmx::fail(KMX_ENOMEM, "kmx_bow_create: hipMemset / hipEventCreate failed");
+  *out = h.release();
   return KMX_OK;
   KMX_GUARD_END
 }
 
 extern "C" int kmx_bow_destroy(kmx_bow* h) {
-  if (!h) return KMX_OK;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  bow_free_db(h);
-  bow_free_q(h);
-  bow_free_p(h);
-  bow_free_fwd(h);
-  bow_free_e(h);
-  bow_free_d(h);
-  for (hipEvent_t e : h->tev)
-    if (e) (void)hipEventDestroy(e);
-  if (h->ev) (void)hipEventDestroy(h->ev);
-  if (h->d_err) (void)hipFree(h->d_err);
-  if (h->d_tstate) (void)hipFree(h->d_tstate);
-  if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-  return KMX_OK;
+  return kmx::destroy(h);
 }
 
+// Unlike the other handles', a borrowed stream is left alone: only a stream of the handle's own is synchronised.
 extern "C" int kmx_bow_set_stream(kmx_bow* h, void* s) {
   KMX_CHECK(h, KMX_EINVAL, "null handle");
-  KMX_HIP(hipSetDevice(h->device));
-  if (h->own_stream && h->stream) {
-    KMX_HIP(hipStreamSynchronize(h->stream));
-    KMX_HIP(hipStreamDestroy(h->stream));
-  }
-  h->own_stream = false;
-  h->stream = reinterpret_cast<hipStream_t>(s);
-  return KMX_OK;
+  return h->adopt(s, false);
 }
 
 extern "C" int kmx_bow_set_database(kmx_bow* h, int32_t n_words, int32_t n_entries, const int64_t* vptr,
@@ -1489,7 +1375,7 @@ extern "C" int kmx_bow_set_database(kmx_bow* h, int32_t n_words, int32_t n_entri
       ent[p] = e;
       wt[p] = weights[k];
     }
-  bow_free_db(h);
+  h->db = BowDbSet();
   h->n_words = n_words;
   h->n_entries = n_entries;
   // KMX_BOW_LDS=0 selects the HBM-accumulator kernel; KMX_BOW_CHUNK sets the
@@ -1517,45 +1403,42 @@ extern "C" int kmx_bow_set_database(kmx_bow* h, int32_t n_words, int32_t n_entri
   // scratch of n_entries; the LDS kernel runs one workgroup per CU
   int cus = 256;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
-  h->n_wg = h->lds ? std::max(1, cus) : std::max(1, cus * 4);
-  const size_t scratch = h->lds ? 1 : (size_t)h->n_wg * std::max(n_entries, 1);
+  h->db.n_wg = h->lds ? std::max(1, cus) : std::max(1, cus * 4);
+  const size_t scratch = h->lds ? 1 : (size_t)h->db.n_wg * std::max(n_entries, 1);
   int rc;
-  if ((rc = bow_alloc(&h->d_ptr, ptr.size())) || (rc = bow_alloc(&h->d_ent, ent.size())) ||
-      (rc = bow_alloc(&h->d_wt, wt.size())) || (rc = bow_alloc(&h->d_acc, scratch)) ||
-      (rc = bow_alloc(&h->d_touched, scratch)) || (h->lds && (rc = bow_alloc(&h->d_cptr, cptr.size())))) {
-    bow_free_db(h);
+  if ((rc = h->db.ptr.alloc(ptr.size())) || (rc = h->db.ent.alloc(ent.size())) || (rc = h->db.wt.alloc(wt.size())) ||
+      (rc = h->db.acc.alloc(scratch)) || (rc = h->db.touched.alloc(scratch)) ||
+      (h->lds && (rc = h->db.cptr.alloc(cptr.size())))) {
+    h->db = BowDbSet();
     return rc;
   }
-  if (h->lds) KMX_HIP(hipMemcpy(h->d_cptr, cptr.data(), sizeof(int) * cptr.size(), hipMemcpyHostToDevice));
-  KMX_HIP(hipMemcpy(h->d_ptr, ptr.data(), sizeof(int) * ptr.size(), hipMemcpyHostToDevice));
-  KMX_HIP(hipMemcpy(h->d_ent, ent.data(), sizeof(int) * ent.size(), hipMemcpyHostToDevice));
-  KMX_HIP(hipMemcpy(h->d_wt, wt.data(), sizeof(double) * wt.size(), hipMemcpyHostToDevice));
-  KMX_HIP(hipMemset(h->d_acc, 0, sizeof(double) * scratch));
-  h->base_cap = ent.size();
-  h->cptr_cap = h->lds ? cptr.size() : 0;
-  h->scratch_cap = scratch;
+  if (h->lds) KMX_HIP(hipMemcpy(h->db.cptr.get(), cptr.data(), sizeof(int) * cptr.size(), hipMemcpyHostToDevice));
+  KMX_HIP(hipMemcpy(h->db.ptr.get(), ptr.data(), sizeof(int) * ptr.size(), hipMemcpyHostToDevice));
+  KMX_HIP(hipMemcpy(h->db.ent.get(), ent.data(), sizeof(int) * ent.size(), hipMemcpyHostToDevice));
+  KMX_HIP(hipMemcpy(h->db.wt.get(), wt.data(), sizeof(double) * wt.size(), hipMemcpyHostToDevice));
+  KMX_HIP(hipMemset(h->db.acc.get(), 0, sizeof(double) * scratch));
   // the forward store: the same vectors entry-major (one more upload of the
   // CSR), all of them sealed. KMX_BOW_TAIL overrides kmx_bow_set_tail_cap.
   h->n_entries = 0;  // until the forward store holds them
   h->n_sealed = 0;
-  bow_free_fwd(h);
+  h->fwd = BowFwdSet();
   h->tail_cap = h->tail_cap_set;
   if (const char* v = std::getenv("KMX_BOW_TAIL")) h->tail_cap = std::max(0, std::min(TAIL_MAX, std::atoi(v)));
   const int64_t held = vptr[n_entries] - vptr[0];
   if (int rc2 = bow_fwd_reserve(h, (size_t)n_entries, (size_t)held)) {
-    bow_free_db(h);
+    h->db = BowDbSet();
     return rc2;
   }
   std::vector<int64_t> fp((size_t)n_entries + 1);
   for (int e = 0; e <= n_entries; ++e) fp[e] = vptr[e] - vptr[0];
-  KMX_HIP(hipMemcpy(h->d_fptr, fp.data(), sizeof(long long) * fp.size(), hipMemcpyHostToDevice));
+  KMX_HIP(hipMemcpy(h->fwd.fptr.get(), fp.data(), sizeof(long long) * fp.size(), hipMemcpyHostToDevice));
   if (held) {
-    KMX_HIP(hipMemcpy(h->d_fw, words + vptr[0], sizeof(unsigned) * (size_t)held, hipMemcpyHostToDevice));
-    KMX_HIP(hipMemcpy(h->d_fv, weights + vptr[0], sizeof(double) * (size_t)held, hipMemcpyHostToDevice));
+    KMX_HIP(hipMemcpy(h->fwd.fw.get(), words + vptr[0], sizeof(unsigned) * (size_t)held, hipMemcpyHostToDevice));
+    KMX_HIP(hipMemcpy(h->fwd.fv.get(), weights + vptr[0], sizeof(double) * (size_t)held, hipMemcpyHostToDevice));
   }
-  h->h_fptr.swap(fp);
+  h->fwd.h_fptr.swap(fp);
   h->n_entries = h->n_sealed = n_entries;
-  KMX_HIP(hipMemsetAsync(h->d_tstate, 0, 8 * sizeof(int), h->stream));  // a new stream of keyframes
+  KMX_HIP(hipMemsetAsync(h->d_tstate.get(), 0, 8 * sizeof(int), h->stream));  // a new stream of keyframes
   return KMX_OK;
   KMX_GUARD_END
 }
@@ -1571,14 +1454,14 @@ extern "C" int kmx_bow_set_tail_cap(kmx_bow* h, int32_t cap) {
   KMX_CHECK(cap >= 0 && cap <= TAIL_MAX, KMX_EINVAL, "tail_cap must be in [0, 1024]");
   h->tail_cap_set = cap;
   if (!std::getenv("KMX_BOW_TAIL")) h->tail_cap = cap;
-  if (h->d_ptr && h->n_entries - h->n_sealed > h->tail_cap) return bow_seal(h);
+  if (h->db.ptr.get() && h->n_entries - h->n_sealed > h->tail_cap) return bow_seal(h);
   return KMX_OK;
   KMX_GUARD_END
 }
 
 extern "C" int kmx_bow_seal(kmx_bow* h) {
   KMX_GUARD_BEGIN
-  KMX_CHECK(h && h->d_ptr, KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
+  KMX_CHECK(h && h->db.ptr.get(), KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
   return bow_seal(h);
   KMX_GUARD_END
 }
@@ -1590,13 +1473,13 @@ extern "C" int kmx_bow_info(kmx_bow* h, int32_t* n_words, int32_t* n_entries, in
   if (n_entries) *n_entries = h->n_entries;
   if (n_sealed) *n_sealed = h->n_sealed;
   if (tail_cap) *tail_cap = h->tail_cap;
-  if (n_postings) *n_postings = h->h_fptr.back();
+  if (n_postings) *n_postings = h->fwd.h_fptr.back();
   if (device_bytes) {
     size_t b = 0;
-    if (h->d_ptr)
-      b = sizeof(int) * ((size_t)h->n_words + 1) + (sizeof(int) + sizeof(double)) * h->base_cap +
-          sizeof(int) * h->cptr_cap + (sizeof(int) + sizeof(double)) * h->scratch_cap +
-          sizeof(long long) * (h->fe_cap + 1) + (sizeof(unsigned) + sizeof(double)) * h->fp_cap;
+    if (h->db.ptr.get())
+      b = sizeof(int) * ((size_t)h->n_words + 1) + (sizeof(int) + sizeof(double)) * h->db.ent.cap() +
+          sizeof(int) * h->db.cptr.cap() + (sizeof(int) + sizeof(double)) * h->db.acc.cap() +
+          sizeof(long long) * (h->fwd.fe_cap() + 1) + (sizeof(unsigned) + sizeof(double)) * h->fwd.fw.cap();
     *device_bytes = (int64_t)b;
   }
   return KMX_OK;
@@ -1606,26 +1489,28 @@ extern "C" int kmx_bow_add_entries(kmx_bow* h, int32_t n, const int64_t* vptr, c
                                    const double* weights, int32_t* first_id_out) {
   KMX_GUARD_BEGIN
   KMX_CHECK(h, KMX_EINVAL, "null handle");
-  KMX_CHECK(h->d_ptr, KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
+  KMX_CHECK(h->db.ptr.get(), KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
   std::string err;
-  if (int rc = kmx::bow_check_csr(h->n_words, h->n_entries, h->h_fptr.back(), n, vptr, words, weights, &err))
+  if (int rc = kmx::bow_check_csr(h->n_words, h->n_entries, h->fwd.h_fptr.back(), n, vptr, words, weights, &err))
     return kmx::fail(rc, err);
   if (first_id_out) *first_id_out = h->n_entries;
   if (n == 0) return KMX_OK;
-  const int64_t total = vptr[n] - vptr[0], base = h->h_fptr.back();
+  const int64_t total = vptr[n] - vptr[0], base = h->fwd.h_fptr.back();
   KMX_HIP(hipSetDevice(h->device));
   if (int rc = bow_fwd_reserve(h, (size_t)h->n_entries + n, (size_t)(base + total))) return rc;
-  const size_t m0 = h->h_fptr.size();  // n_entries + 1
-  for (int e = 1; e <= n; ++e) h->h_fptr.push_back(base + (vptr[e] - vptr[0]));
-  hipError_t e1 = hipMemcpyAsync(h->d_fptr + m0, h->h_fptr.data() + m0, sizeof(long long) * n,
+  const size_t m0 = h->fwd.h_fptr.size();  // n_entries + 1
+  for (int e = 1; e <= n; ++e) h->fwd.h_fptr.push_back(base + (vptr[e] - vptr[0]));
+  hipError_t e1 = hipMemcpyAsync(h->fwd.fptr.get() + m0, h->fwd.h_fptr.data() + m0, sizeof(long long) * n,
                                  hipMemcpyHostToDevice, h->stream);
   if (e1 == hipSuccess && total)
-    e1 = hipMemcpyAsync(h->d_fw + base, words + vptr[0], sizeof(unsigned) * total, hipMemcpyHostToDevice, h->stream);
+    e1 = hipMemcpyAsync(h->fwd.fw.get() + base, words + vptr[0], sizeof(unsigned) * total, hipMemcpyHostToDevice,
+                        h->stream);
   if (e1 == hipSuccess && total)
-    e1 = hipMemcpyAsync(h->d_fv + base, weights + vptr[0], sizeof(double) * total, hipMemcpyHostToDevice, h->stream);
+    e1 = hipMemcpyAsync(h->fwd.fv.get() + base, weights + vptr[0], sizeof(double) * total, hipMemcpyHostToDevice,
+                        h->stream);
   if (e1 == hipSuccess) e1 = hipStreamSynchronize(h->stream);  // the caller's arrays are free again
   if (e1 != hipSuccess) {
-    h->h_fptr.resize(m0);  // the entries were not added
+    h->fwd.h_fptr.resize(m0);  // the entries were not added
     return kmx::fail(KMX_EHIP, std::string("kmx_bow_add_entries: ") + hipGetErrorString(e1));
   }
   h->n_entries += n;
@@ -1637,7 +1522,7 @@ extern "C" int kmx_bow_add_entries(kmx_bow* h, int32_t n, const int64_t* vptr, c
 extern "C" int kmx_bow_add_from_voc(kmx_bow* h, kmx_voc* voc, int32_t* first_id_out, int32_t* n_out) {
   KMX_GUARD_BEGIN
   KMX_CHECK(h && voc, KMX_EINVAL, "null handle");
-  KMX_CHECK(h->d_ptr, KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
+  KMX_CHECK(h->db.ptr.get(), KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
   kmx::VocBatchView vb;
   if (int rc = kmx::voc_batch_view(voc, &vb)) return rc;
   KMX_CHECK(vb.device == h->device, KMX_EINVAL, "the vocabulary is on another device");
@@ -1645,7 +1530,7 @@ extern "C" int kmx_bow_add_from_voc(kmx_bow* h, kmx_voc* voc, int32_t* first_id_
   KMX_CHECK(vb.n_frames > 0 && vb.stride > 0 && vb.nnz && vb.words && vb.weights, KMX_ESTATE,
             "the vocabulary holds no transformed batch");
   const int n = vb.n_frames;
-  const int64_t base = h->h_fptr.back(), most = (int64_t)n * vb.stride;  // a frame has <= stride words
+  const int64_t base = h->fwd.h_fptr.back(), most = (int64_t)n * vb.stride;  // a frame has <= stride words
   KMX_CHECK(n < INT32_MAX - h->n_entries, KMX_EINVAL, "database too large (entries must fit int32)");
   KMX_CHECK(most < (int64_t)INT32_MAX - base, KMX_EINVAL, "database too large (postings must fit int32)");
   KMX_HIP(hipSetDevice(h->device));
@@ -1653,23 +1538,23 @@ extern "C" int kmx_bow_add_from_voc(kmx_bow* h, kmx_voc* voc, int32_t* first_id_
   // after the transform, which runs on the vocabulary's stream
   KMX_HIP(hipEventRecord(h->ev, vb.stream));
   KMX_HIP(hipStreamWaitEvent(h->stream, h->ev, 0));
-  long long* fnew = h->d_fptr + h->n_entries;
+  long long* fnew = h->fwd.fptr.get() + h->n_entries;
   // no weight check here (bow_check_csr's "finite and > 0"): k_voc_reduce keeps
   // only leaves with a positive weight and divides by their positive sum
   hipLaunchKernelGGL(k_bow_scan_len<0>, dim3(1), dim3(TL_BLOCK), 0, h->stream, n, vb.nnz,
                      (const long long*)nullptr, fnew);
   KMX_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_bow_voc_compact, dim3(n), dim3(256), 0, h->stream, vb.nnz, (const unsigned*)vb.words,
-                     vb.weights, vb.stride, (const long long*)fnew, h->d_fw, h->d_fv);
+                     vb.weights, vb.stride, (const long long*)fnew, h->fwd.fw.get(), h->fwd.fv.get());
   KMX_HIP(hipGetLastError());
   // the new entries' offsets come back to the host mirror: 8 bytes per entry, no words or weights
-  const size_t m0 = h->h_fptr.size();
-  h->h_fptr.resize(m0 + n);
-  hipError_t e1 = hipMemcpyAsync(h->h_fptr.data() + m0, fnew + 1, sizeof(long long) * n, hipMemcpyDeviceToHost,
+  const size_t m0 = h->fwd.h_fptr.size();
+  h->fwd.h_fptr.resize(m0 + n);
+  hipError_t e1 = hipMemcpyAsync(h->fwd.h_fptr.data() + m0, fnew + 1, sizeof(long long) * n, hipMemcpyDeviceToHost,
                                  h->stream);
   if (e1 == hipSuccess) e1 = hipStreamSynchronize(h->stream);
   if (e1 != hipSuccess) {
-    h->h_fptr.resize(m0);
+    h->fwd.h_fptr.resize(m0);
     return kmx::fail(KMX_EHIP, std::string("kmx_bow_add_from_voc: ") + hipGetErrorString(e1));
   }
   if (first_id_out) *first_id_out = h->n_entries;
@@ -1684,16 +1569,16 @@ extern "C" int kmx_bow_get_entries(kmx_bow* h, int32_t first, int32_t n, int64_t
                                    double* weights_out, int64_t cap) {
   KMX_GUARD_BEGIN
   KMX_CHECK(h && vptr_out, KMX_EINVAL, "null argument");
-  KMX_CHECK(h->d_ptr, KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
+  KMX_CHECK(h->db.ptr.get(), KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
   KMX_CHECK(first >= 0 && n >= 0 && (int64_t)first + n <= h->n_entries, KMX_EINVAL, "entry range outside the database");
-  const int64_t p0 = h->h_fptr[first], total = h->h_fptr[(size_t)first + n] - p0;
-  for (int i = 0; i <= n; ++i) vptr_out[i] = h->h_fptr[(size_t)first + i] - p0;
+  const int64_t p0 = h->fwd.h_fptr[first], total = h->fwd.h_fptr[(size_t)first + n] - p0;
+  for (int i = 0; i <= n; ++i) vptr_out[i] = h->fwd.h_fptr[(size_t)first + i] - p0;
   if (!words_out) return KMX_OK;  // sizes only
   KMX_CHECK(weights_out && cap >= total, KMX_EINVAL, "output arrays too small (vptr_out[n] words)");
   if (total == 0) return KMX_OK;
   KMX_HIP(hipSetDevice(h->device));
-  KMX_HIP(hipMemcpyAsync(words_out, h->d_fw + p0, sizeof(unsigned) * total, hipMemcpyDeviceToHost, h->stream));
-  KMX_HIP(hipMemcpyAsync(weights_out, h->d_fv + p0, sizeof(double) * total, hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(words_out, h->fwd.fw.get() + p0, sizeof(unsigned) * total, hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(weights_out, h->fwd.fv.get() + p0, sizeof(double) * total, hipMemcpyDeviceToHost, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   return KMX_OK;
   KMX_GUARD_END
@@ -1702,20 +1587,18 @@ extern "C" int kmx_bow_get_entries(kmx_bow* h, int32_t first, int32_t n, int64_t
 namespace {
 // Room for nq queries of nw words in all and their K results each.
 int bow_reserve_queries(kmx_bow* h, size_t nq, size_t nw, int32_t K) {
-  if (nq + 1 > h->qcap || nw > h->wcap || nq * K > h->rcap) {
+  if (nq + 1 > h->qry.qptr.cap() || nw > h->qry.qw.cap() || nq * K > h->qry.id.cap()) {
     KMX_HIP(hipStreamSynchronize(h->stream));  // a query in flight uses the old buffers
-    bow_free_q(h);
-    h->qcap = std::max<size_t>(nq + 1, 1024);
-    h->wcap = std::max<size_t>(nw, 1);
-    h->rcap = std::max<size_t>(nq * K, 1);
+    h->qry = BowQuerySet();  // the old set goes first; a failure below leaves the handle without one
+    const size_t qcap = std::max<size_t>(nq + 1, 1024), wcap = std::max<size_t>(nw, 1);
+    const size_t rcap = std::max<size_t>(nq * K, 1);
+    BowQuerySet b;
     int rc;
-    if ((rc = bow_alloc(&h->d_qptr, h->qcap)) || (rc = bow_alloc(&h->d_qw, h->wcap)) ||
-        (rc = bow_alloc(&h->d_qv, h->wcap)) || (rc = bow_alloc(&h->d_maxid, h->qcap)) ||
-        (rc = bow_alloc(&h->d_n, h->qcap)) || (rc = bow_alloc(&h->d_id, h->rcap)) ||
-        (rc = bow_alloc(&h->d_score, h->rcap))) {
-      bow_free_q(h);
+    if ((rc = b.qptr.alloc(qcap)) || (rc = b.qw.alloc(wcap)) || (rc = b.qv.alloc(wcap)) ||
+        (rc = b.maxid.alloc(qcap)) || (rc = b.n.alloc(qcap)) || (rc = b.id.alloc(rcap)) ||
+        (rc = b.score.alloc(rcap)))
       return rc;
-    }
+    h->qry = std::move(b);
   }
   return KMX_OK;
 }
@@ -1724,12 +1607,12 @@ int bow_upload_queries(kmx_bow* h, int32_t nq, const int64_t* qptr, const uint32
                        const int32_t* max_id, int32_t K) {
   const size_t nw = (size_t)qptr[nq];
   if (int rc = bow_reserve_queries(h, (size_t)nq, nw, K)) return rc;
-  KMX_HIP(hipMemcpyAsync(h->d_qptr, qptr, sizeof(long long) * (nq + 1), hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->qry.qptr.get(), qptr, sizeof(long long) * (nq + 1), hipMemcpyHostToDevice, h->stream));
   if (nw) {
-    KMX_HIP(hipMemcpyAsync(h->d_qw, words, sizeof(unsigned) * nw, hipMemcpyHostToDevice, h->stream));
-    KMX_HIP(hipMemcpyAsync(h->d_qv, weights, sizeof(double) * nw, hipMemcpyHostToDevice, h->stream));
+    KMX_HIP(hipMemcpyAsync(h->qry.qw.get(), words, sizeof(unsigned) * nw, hipMemcpyHostToDevice, h->stream));
+    KMX_HIP(hipMemcpyAsync(h->qry.qv.get(), weights, sizeof(double) * nw, hipMemcpyHostToDevice, h->stream));
   }
-  if (max_id) KMX_HIP(hipMemcpyAsync(h->d_maxid, max_id, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
+  if (max_id) KMX_HIP(hipMemcpyAsync(h->qry.maxid.get(), max_id, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
   return KMX_OK;
 }
 
@@ -1739,26 +1622,28 @@ int bow_launch_query(kmx_bow* h, int32_t nq, bool has_max_id, int32_t max_result
   // only after an add whose seal failed: k_bow_tail holds TAIL_MAX candidates, so seal first
   if (h->n_entries - h->n_sealed > TAIL_MAX)
     if (int rc = bow_seal(h)) return rc;
-  KMX_HIP(hipMemsetAsync(h->d_err, 0, 2 * sizeof(int), h->stream));  // error flag, query counter
-  BowDb db{h->d_ptr, h->d_ent, h->d_wt, h->n_words, h->n_sealed};
-  const int grid = std::min(nq, h->n_wg);
-  const int* mid = has_max_id ? (const int*)h->d_maxid : nullptr;
+  KMX_HIP(hipMemsetAsync(h->d_err.get(), 0, 2 * sizeof(int), h->stream));  // error flag, query counter
+  BowDb db{h->db.ptr.get(), h->db.ent.get(), h->db.wt.get(), h->n_words, h->n_sealed};
+  const int grid = std::min(nq, h->db.n_wg);
+  const int* mid = has_max_id ? (const int*)h->qry.maxid.get() : nullptr;
   if (h->lds) {
     hipLaunchKernelGGL(k_bow_query_lds, dim3(grid), dim3(LW_BLOCK), LDS_BOW, h->stream, db,
-                       (const int*)h->d_cptr, h->nch, h->ch, nq, (const long long*)h->d_qptr,
-                       (const unsigned*)h->d_qw, (const double*)h->d_qv, mid, max_results, h->d_n, h->d_id,
-                       h->d_score, h->d_err, h->d_err + 1);
+                       (const int*)h->db.cptr.get(), h->nch, h->ch, nq, (const long long*)h->qry.qptr.get(),
+                       (const unsigned*)h->qry.qw.get(), (const double*)h->qry.qv.get(), mid, max_results,
+                       h->qry.n.get(), h->qry.id.get(), h->qry.score.get(), h->d_err.get(), h->d_err.get() + 1);
   } else {
     hipLaunchKernelGGL(k_bow_query, dim3(grid), dim3(BOW_BLOCK), 0, h->stream, db, nq,
-                       (const long long*)h->d_qptr, (const unsigned*)h->d_qw, (const double*)h->d_qv, mid,
-                       max_results, h->d_acc, h->d_touched, h->d_n, h->d_id, h->d_score, h->d_err, h->d_err + 1);
+                       (const long long*)h->qry.qptr.get(), (const unsigned*)h->qry.qw.get(),
+                       (const double*)h->qry.qv.get(), mid, max_results, h->db.acc.get(), h->db.touched.get(),
+                       h->qry.n.get(), h->qry.id.get(), h->qry.score.get(), h->d_err.get(), h->d_err.get() + 1);
   }
   KMX_HIP(hipGetLastError());
   if (h->n_entries > h->n_sealed) {
-    BowFwd f{h->d_fptr, h->d_fw, h->d_fv};
-    hipLaunchKernelGGL(k_bow_tail, dim3(std::min(nq, 4096)), dim3(TL_BLOCK), 0, h->stream, f, h->n_sealed,
-                       h->n_entries, nq, (const long long*)h->d_qptr, (const unsigned*)h->d_qw,
-                       (const double*)h->d_qv, mid, max_results, h->d_n, h->d_id, h->d_score);
+    BowFwd f{h->fwd.fptr.get(), h->fwd.fw.get(), h->fwd.fv.get()};
+    hipLaunchKernelGGL(k_bow_tail, dim3(std::min(nq, 4096)), dim3(TL_BLOCK), 0, h->stream, f, h->n_sealed, h->n_entries,
+                       nq, (const long long*)h->qry.qptr.get(), (const unsigned*)h->qry.qw.get(),
+                       (const double*)h->qry.qv.get(), mid, max_results, h->qry.n.get(), h->qry.id.get(),
+                       h->qry.score.get());
     KMX_HIP(hipGetLastError());
   }
   return KMX_OK;
@@ -1767,27 +1652,26 @@ int bow_launch_query(kmx_bow* h, int32_t nq, bool has_max_id, int32_t max_result
 int bow_fetch_results(kmx_bow* h, int32_t nq, int32_t max_results, int32_t* out_n, int32_t* out_ids,
                       double* out_scores) {
   int err = 0;
-  KMX_HIP(hipMemcpyAsync(out_n, h->d_n, sizeof(int) * nq, hipMemcpyDeviceToHost, h->stream));
-  KMX_HIP(hipMemcpyAsync(out_ids, h->d_id, sizeof(int) * (size_t)nq * max_results, hipMemcpyDeviceToHost, h->stream));
-  KMX_HIP(hipMemcpyAsync(out_scores, h->d_score, sizeof(double) * (size_t)nq * max_results, hipMemcpyDeviceToHost,
+  KMX_HIP(hipMemcpyAsync(out_n, h->qry.n.get(), sizeof(int) * nq, hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(out_ids, h->qry.id.get(), sizeof(int) * (size_t)nq * max_results, hipMemcpyDeviceToHost,
                          h->stream));
-  KMX_HIP(hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(out_scores, h->qry.score.get(), sizeof(double) * (size_t)nq * max_results,
+                         hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(&err, h->d_err.get(), sizeof(int), hipMemcpyDeviceToHost, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   KMX_CHECK(!err, KMX_EUNSUP, "too many exactly tied scores at the max_results cut");
   return KMX_OK;
 }
 
 int bow_reserve_ids(kmx_bow* h, size_t n) {
-  if (n <= h->ecap) return KMX_OK;
+  if (n <= h->ids.cap()) return KMX_OK;
   KMX_HIP(hipStreamSynchronize(h->stream));
-  bow_free_e(h);
+  h->ids = BowIdSet();
   const size_t cap = std::max<size_t>(n, 1024);
+  BowIdSet b;
   int rc;
-  if ((rc = bow_alloc(&h->d_eid, 2 * cap)) || (rc = bow_alloc(&h->d_eout, cap))) {
-    bow_free_e(h);
-    return rc;
-  }
-  h->ecap = cap;
+  if ((rc = b.eid.alloc(2 * cap)) || (rc = b.eout.alloc(cap))) return rc;
+  h->ids = std::move(b);
   return KMX_OK;
 }
 }  // namespace
@@ -1795,7 +1679,7 @@ int bow_reserve_ids(kmx_bow* h, size_t n) {
 extern "C" int kmx_bow_query_async(kmx_bow* h, int32_t nq, const int64_t* qptr, const uint32_t* words,
                                    const double* weights, const int32_t* max_id, int32_t max_results) {
   KMX_GUARD_BEGIN
-  KMX_CHECK(h && h->d_ptr, KMX_ESTATE, "kmx_bow_set_database first");
+  KMX_CHECK(h && h->db.ptr.get(), KMX_ESTATE, "kmx_bow_set_database first");
   KMX_CHECK(nq >= 0 && qptr && max_results > 0 && max_results <= MAX_RESULTS, KMX_EINVAL,
             "bad argument (max_results in [1, 256])");
   KMX_HIP(hipSetDevice(h->device));
@@ -1820,14 +1704,15 @@ extern "C" int kmx_bow_query(kmx_bow* h, int32_t nq, const int64_t* qptr, const 
 extern "C" int kmx_bow_query_entries_async(kmx_bow* h, kmx_bow* src, int32_t nq, const int32_t* entry_ids,
                                            const int32_t* max_id, int32_t max_results) {
   KMX_GUARD_BEGIN
-  KMX_CHECK(h && h->d_ptr && src && src->d_ptr, KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
+  KMX_CHECK(h && h->db.ptr.get() && src && src->db.ptr.get(), KMX_ESTATE,
+            "kmx_bow_set_database or kmx_bow_reset first");
   KMX_CHECK(nq >= 0 && (nq == 0 || entry_ids) && max_results > 0 && max_results <= MAX_RESULTS, KMX_EINVAL,
             "bad argument (max_results in [1, 256])");
   KMX_CHECK(src->device == h->device, KMX_EINVAL, "the source database is on another device");
   size_t nw = 0;
   for (int q = 0; q < nq; ++q) {
     KMX_CHECK(entry_ids[q] >= 0 && entry_ids[q] < src->n_entries, KMX_EINVAL, "entry id outside the source database");
-    nw += (size_t)(src->h_fptr[(size_t)entry_ids[q] + 1] - src->h_fptr[entry_ids[q]]);
+    nw += (size_t)(src->fwd.h_fptr[(size_t)entry_ids[q] + 1] - src->fwd.h_fptr[entry_ids[q]]);
   }
   if (nq == 0) return KMX_OK;
   KMX_HIP(hipSetDevice(h->device));
@@ -1837,14 +1722,14 @@ extern "C" int kmx_bow_query_entries_async(kmx_bow* h, kmx_bow* src, int32_t nq,
     KMX_HIP(hipEventRecord(h->ev, src->stream));
     KMX_HIP(hipStreamWaitEvent(h->stream, h->ev, 0));
   }
-  KMX_HIP(hipMemcpyAsync(h->d_eid, entry_ids, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
-  if (max_id) KMX_HIP(hipMemcpyAsync(h->d_maxid, max_id, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
-  BowFwd f{src->d_fptr, src->d_fw, src->d_fv};
-  hipLaunchKernelGGL(k_bow_scan_len<1>, dim3(1), dim3(TL_BLOCK), 0, h->stream, nq, (const int*)h->d_eid, f.fptr,
-                     h->d_qptr);
+  KMX_HIP(hipMemcpyAsync(h->ids.eid.get(), entry_ids, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
+  if (max_id) KMX_HIP(hipMemcpyAsync(h->qry.maxid.get(), max_id, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
+  BowFwd f{src->fwd.fptr.get(), src->fwd.fw.get(), src->fwd.fv.get()};
+  hipLaunchKernelGGL(k_bow_scan_len<1>, dim3(1), dim3(TL_BLOCK), 0, h->stream, nq, (const int*)h->ids.eid.get(), f.fptr,
+                     h->qry.qptr.get());
   KMX_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_bow_gather, dim3(nq), dim3(256), 0, h->stream, f, (const int*)h->d_eid,
-                     (const long long*)h->d_qptr, h->d_qw, h->d_qv);
+  hipLaunchKernelGGL(k_bow_gather, dim3(nq), dim3(256), 0, h->stream, f, (const int*)h->ids.eid.get(),
+                     (const long long*)h->qry.qptr.get(), h->qry.qw.get(), h->qry.qv.get());
   KMX_HIP(hipGetLastError());
   return bow_launch_query(h, nq, max_id != nullptr, max_results);
   KMX_GUARD_END
@@ -1865,8 +1750,8 @@ extern "C" int kmx_bow_fetch(kmx_bow* h, int32_t nq, int32_t max_results, int32_
                              double* out_scores) {
   KMX_GUARD_BEGIN
   KMX_CHECK(h && out_n && out_ids && out_scores, KMX_EINVAL, "null argument");
-  KMX_CHECK(nq >= 0 && max_results > 0 && (size_t)nq + 1 <= h->qcap && (size_t)nq * max_results <= h->rcap,
-            KMX_EINVAL, "no enqueued query of this shape");
+  KMX_CHECK(nq >= 0 && max_results > 0 && (size_t)nq + 1 <= h->qry.qptr.cap() &&
+            (size_t)nq * max_results <= h->qry.id.cap(), KMX_EINVAL, "no enqueued query of this shape");
   if (nq == 0) return KMX_OK;
   KMX_HIP(hipSetDevice(h->device));
   return bow_fetch_results(h, nq, max_results, out_n, out_ids, out_scores);
@@ -1877,20 +1762,22 @@ extern "C" int kmx_bow_score_entries(kmx_bow* src, int32_t n, const int32_t* a_i
                                      double* out) {
   KMX_GUARD_BEGIN
   KMX_CHECK(src && n >= 0 && (n == 0 || (a_ids && b_ids && out)), KMX_EINVAL, "bad argument");
-  KMX_CHECK(src->d_ptr, KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
+  KMX_CHECK(src->db.ptr.get(), KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
   for (int i = 0; i < n; ++i)
     KMX_CHECK(a_ids[i] >= -1 && a_ids[i] < src->n_entries && b_ids[i] >= -1 && b_ids[i] < src->n_entries,
               KMX_EINVAL, "entry id outside the database (-1: no entry)");
   if (n == 0) return KMX_OK;
   KMX_HIP(hipSetDevice(src->device));
   if (int rc = bow_reserve_ids(src, (size_t)n)) return rc;
-  KMX_HIP(hipMemcpyAsync(src->d_eid, a_ids, sizeof(int) * n, hipMemcpyHostToDevice, src->stream));
-  KMX_HIP(hipMemcpyAsync(src->d_eid + src->ecap, b_ids, sizeof(int) * n, hipMemcpyHostToDevice, src->stream));
-  BowFwd f{src->d_fptr, src->d_fw, src->d_fv};
+  KMX_HIP(hipMemcpyAsync(src->ids.eid.get(), a_ids, sizeof(int) * n, hipMemcpyHostToDevice, src->stream));
+  KMX_HIP(hipMemcpyAsync(src->ids.eid.get() + src->ids.cap(), b_ids, sizeof(int) * n, hipMemcpyHostToDevice,
+                         src->stream));
+  BowFwd f{src->fwd.fptr.get(), src->fwd.fw.get(), src->fwd.fv.get()};
   hipLaunchKernelGGL(k_bow_entry_score, dim3((n + 255) / 256), dim3(256), 0, src->stream, n, f,
-                     (const int*)src->d_eid, (const int*)(src->d_eid + src->ecap), src->d_eout);
+                     (const int*)src->ids.eid.get(), (const int*)(src->ids.eid.get() + src->ids.cap()),
+                     src->ids.eout.get());
   KMX_HIP(hipGetLastError());
-  KMX_HIP(hipMemcpyAsync(out, src->d_eout, sizeof(double) * n, hipMemcpyDeviceToHost, src->stream));
+  KMX_HIP(hipMemcpyAsync(out, src->ids.eout.get(), sizeof(double) * n, hipMemcpyDeviceToHost, src->stream));
   KMX_HIP(hipStreamSynchronize(src->stream));
   return KMX_OK;
   KMX_GUARD_END
@@ -1905,28 +1792,23 @@ size_t det_bytes(size_t nq) { return det_cand_off(nq) + 2 * sizeof(int) * nq; }
 static_assert(sizeof(kmx_bow_detect_record) == 48, "kmx_bow_detect_record is 48 bytes");
 
 int bow_reserve_detect(kmx_bow* h, size_t nq) {
-  if (nq <= h->dcap) return KMX_OK;
+  if (nq <= h->det.cap()) return KMX_OK;
   KMX_HIP(hipStreamSynchronize(h->stream));
-  bow_free_d(h);
+  h->det = BowDetSet();
   const size_t cap = std::max<size_t>(nq, 1024);
+  BowDetSet b;
   int rc;
-  if ((rc = bow_alloc(&h->d_hasprev, 2 * cap)) || (rc = bow_alloc(&h->d_tin, cap)) ||
-      (rc = bow_alloc(&h->d_dout, det_bytes(cap)))) {
-    bow_free_d(h);
+  if ((rc = b.hasprev.alloc(2 * cap)) || (rc = b.tin.alloc(cap)) || (rc = b.dout.alloc(det_bytes(cap))) ||
+      (rc = b.h_dout.alloc(det_bytes(cap))))
     return rc;
-  }
-  if (hipHostMalloc(reinterpret_cast<void**>(&h->h_dout), det_bytes(cap), hipHostMallocDefault) != hipSuccess) {
-    h->h_dout = nullptr;
-    bow_free_d(h);
-    return kmx::fail(KMX_ENOMEM, "hipHostMalloc failed");
-  }
-  h->dcap = cap;
+  h->det = std::move(b);
   return KMX_OK;
 }
 
 int bow_time(kmx_bow* h, int k) {  // event k of the enqueued detection, when timing is on
   if (!h->timing) return KMX_OK;
-  if (!h->tev[k]) KMX_HIP(hipEventCreate(&h->tev[k]));
+  if (!h->tev[k])
+    if (int rc = h->tev[k].create()) return rc;
   KMX_HIP(hipEventRecord(h->tev[k], h->stream));
   return KMX_OK;
 }
@@ -1937,36 +1819,37 @@ int bow_time(kmx_bow* h, int k) {  // event k of the enqueued detection, when ti
 int bow_launch_decide(kmx_bow* h, int32_t nq, int32_t K, int32_t mode, const kmx_bow_detect_params* p,
                       const int* qids, const int* n, const int* ids, const double* scores, const double* nss,
                       const int* has_prev, const int* qerr, int* state) {
-  char* out = h->d_dout;
+  char* out = h->det.dout.get();
   kmx_bow_detect_record* rec = reinterpret_cast<kmx_bow_detect_record*>(out);
   int* hdr = reinterpret_cast<int*>(out + det_hdr_off((size_t)nq));
   int* cand = reinterpret_cast<int*>(out + det_cand_off((size_t)nq));
   const BowDecide d{p->use_nss, p->alpha, p->min_nss_factor, p->max_intraisland_gap, p->min_matches_per_island};
-  hipLaunchKernelGGL(k_bow_decide, dim3(std::min(nq, 1 << 20)), dim3(DEC_WAVE), 0, h->stream, nq, K, mode, d, qids,
-                     n, ids, scores, nss, has_prev, rec, h->d_tin, h->d_hasprev + h->dcap, qerr, hdr);
+  hipLaunchKernelGGL(k_bow_decide, dim3(std::min(nq, 1 << 20)), dim3(DEC_WAVE), 0, h->stream, nq, K, mode, d, qids, n,
+                     ids, scores, nss, has_prev, rec, h->det.tin.get(), h->det.hasprev.get() + h->det.cap(), qerr, hdr);
   KMX_HIP(hipGetLastError());
   if (int rc = bow_time(h, 2)) return rc;
   if (mode == KMX_BOW_MODE_INTRA) {
     hipLaunchKernelGGL(k_bow_temporal, dim3(1), dim3(DEC_WAVE), 0, h->stream, nq, p->max_nrFrames_between_queries,
-                       p->max_nrFrames_between_islands, p->min_temporal_matches, (const int4*)h->d_tin,
-                       (const int*)(h->d_hasprev + h->dcap), rec, state,
+                       p->max_nrFrames_between_islands, p->min_temporal_matches, (const int4*)h->det.tin.get(),
+                       (const int*)(h->det.hasprev.get() + h->det.cap()), rec, state,
                        cand, hdr);
     KMX_HIP(hipGetLastError());
   }
   if (int rc = bow_time(h, 3)) return rc;
-  KMX_HIP(hipMemcpyAsync(h->h_dout, out, det_bytes((size_t)nq), hipMemcpyDeviceToHost, h->stream));
-  h->det_nq = nq;
+  KMX_HIP(hipMemcpyAsync(h->det.h_dout.get(), out, det_bytes((size_t)nq), hipMemcpyDeviceToHost, h->stream));
+  h->det.nq = nq;
   return KMX_OK;
 }
 
 int bow_fetch_decide(kmx_bow* h, int32_t nq, kmx_bow_detect_record* records_out, int32_t* cand_out,
                      int32_t* n_cand_out) {
   KMX_HIP(hipStreamSynchronize(h->stream));
-  const int* hdr = reinterpret_cast<const int*>(h->h_dout + det_hdr_off((size_t)nq));
+  const int* hdr = reinterpret_cast<const int*>(h->det.h_dout.get() + det_hdr_off((size_t)nq));
   KMX_CHECK(!hdr[1], KMX_EUNSUP, "too many exactly tied scores at the max_results cut");
   const int nc = std::max(0, std::min(hdr[0], nq));
-  std::copy_n(reinterpret_cast<const kmx_bow_detect_record*>(h->h_dout), nq, records_out);
-  if (cand_out) std::copy_n(reinterpret_cast<const int*>(h->h_dout + det_cand_off((size_t)nq)), 2 * (size_t)nc, cand_out);
+  std::copy_n(reinterpret_cast<const kmx_bow_detect_record*>(h->det.h_dout.get()), nq, records_out);
+  if (cand_out) std::copy_n(reinterpret_cast<const int*>(h->det.h_dout.get() + det_cand_off((size_t)nq)),
+                            2 * (size_t)nc, cand_out);
   if (n_cand_out) *n_cand_out = nc;
   return KMX_OK;
 }
@@ -1979,7 +1862,7 @@ extern "C" int kmx_bow_detect_entries_async(kmx_bow* h, kmx_bow* src, int32_t nq
   if (!src) src = h;
   std::string err;
   if (int rc = kmx::bow_check_detect_params(params, mode, MAX_RESULTS, &err)) return kmx::fail(rc, err);
-  KMX_CHECK(h->d_ptr && src->d_ptr, KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
+  KMX_CHECK(h->db.ptr.get() && src->db.ptr.get(), KMX_ESTATE, "kmx_bow_set_database or kmx_bow_reset first");
   KMX_CHECK(nq >= 0 && (nq == 0 || entry_ids), KMX_EINVAL, "bad argument");
   KMX_CHECK(src->device == h->device, KMX_EINVAL, "the source database is on another device");
   KMX_CHECK(mode == KMX_BOW_MODE_INTER || src == h, KMX_EINVAL, "intra mode queries the database's own entries");
@@ -1987,12 +1870,12 @@ extern "C" int kmx_bow_detect_entries_async(kmx_bow* h, kmx_bow* src, int32_t nq
   bool consecutive = true;  // a keyframe stream: the ids are made on the device, not uploaded
   for (int q = 0; q < nq; ++q) {
     KMX_CHECK(entry_ids[q] >= 0 && entry_ids[q] < src->n_entries, KMX_EINVAL, "entry id outside the source database");
-    nw += (size_t)(src->h_fptr[(size_t)entry_ids[q] + 1] - src->h_fptr[entry_ids[q]]);
+    nw += (size_t)(src->fwd.h_fptr[(size_t)entry_ids[q] + 1] - src->fwd.h_fptr[entry_ids[q]]);
     consecutive = consecutive && entry_ids[q] - entry_ids[0] == q;
   }
-  h->det_nq = -1;
+  h->det.nq = -1;
   if (nq == 0) {
-    h->det_nq = 0;
+    h->det.nq = 0;
     return KMX_OK;
   }
   const int32_t K = params->max_db_results;
@@ -2008,23 +1891,24 @@ extern "C" int kmx_bow_detect_entries_async(kmx_bow* h, kmx_bow* src, int32_t nq
   }
   if ((rc = bow_time(h, 0))) return rc;
   if (!consecutive)
-    KMX_HIP(hipMemcpyAsync(h->d_eid, entry_ids, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
-  BowFwd f{src->d_fptr, src->d_fw, src->d_fv};
+    KMX_HIP(hipMemcpyAsync(h->ids.eid.get(), entry_ids, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
+  BowFwd f{src->fwd.fptr.get(), src->fwd.fw.get(), src->fwd.fv.get()};
   hipLaunchKernelGGL(k_bow_detect_prep, dim3((nq + 255) / 256), dim3(256), 0, h->stream, nq, mode,
                      params->recent_frames_window, params->use_nss, f, entry_ids[0],
-                     consecutive ? (const int*)nullptr : (const int*)h->d_eid, h->d_eid, h->d_hasprev, h->d_maxid,
-                     h->d_eout);
+                     consecutive ? (const int*)nullptr : (const int*)h->ids.eid.get(), h->ids.eid.get(),
+                     h->det.hasprev.get(), h->qry.maxid.get(), h->ids.eout.get());
   KMX_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_bow_scan_len<1>, dim3(1), dim3(TL_BLOCK), 0, h->stream, nq, (const int*)h->d_eid, f.fptr,
-                     h->d_qptr);
+  hipLaunchKernelGGL(k_bow_scan_len<1>, dim3(1), dim3(TL_BLOCK), 0, h->stream, nq, (const int*)h->ids.eid.get(), f.fptr,
+                     h->qry.qptr.get());
   KMX_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_bow_gather, dim3(nq), dim3(256), 0, h->stream, f, (const int*)h->d_eid,
-                     (const long long*)h->d_qptr, h->d_qw, h->d_qv);
+  hipLaunchKernelGGL(k_bow_gather, dim3(nq), dim3(256), 0, h->stream, f, (const int*)h->ids.eid.get(),
+                     (const long long*)h->qry.qptr.get(), h->qry.qw.get(), h->qry.qv.get());
   KMX_HIP(hipGetLastError());
   if ((rc = bow_launch_query(h, nq, intra, K))) return rc;
   if ((rc = bow_time(h, 1))) return rc;
-  return bow_launch_decide(h, nq, K, mode, params, h->d_eid, h->d_n, h->d_id, h->d_score,
-                           params->use_nss ? h->d_eout : nullptr, h->d_hasprev, h->d_err, h->d_tstate);
+  return bow_launch_decide(h, nq, K, mode, params, h->ids.eid.get(), h->qry.n.get(), h->qry.id.get(),
+                           h->qry.score.get(), params->use_nss ? h->ids.eout.get() : nullptr, h->det.hasprev.get(),
+                           h->d_err.get(), h->d_tstate.get());
   KMX_GUARD_END
 }
 
@@ -2032,7 +1916,7 @@ extern "C" int kmx_bow_detect_fetch(kmx_bow* h, int32_t nq, kmx_bow_detect_recor
                                     int32_t* n_cand_out) {
   KMX_GUARD_BEGIN
   KMX_CHECK(h && nq >= 0 && (nq == 0 || records_out), KMX_EINVAL, "bad argument");
-  KMX_CHECK(nq == h->det_nq, KMX_EINVAL, "no enqueued detection of this size");
+  KMX_CHECK(nq == h->det.nq, KMX_EINVAL, "no enqueued detection of this size");
   if (n_cand_out) *n_cand_out = 0;
   if (nq == 0) return KMX_OK;
   KMX_HIP(hipSetDevice(h->device));
@@ -2067,20 +1951,23 @@ extern "C" int kmx_bow_decide_results(kmx_bow* h, int32_t nq, int32_t K, const i
       (rc = bow_reserve_detect(h, (size_t)nq)))
     return rc;
   const size_t rows = (size_t)nq * K;
-  KMX_HIP(hipMemcpyAsync(h->d_n, n, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
-  KMX_HIP(hipMemcpyAsync(h->d_id, ids, sizeof(int) * rows, hipMemcpyHostToDevice, h->stream));
-  KMX_HIP(hipMemcpyAsync(h->d_score, scores, sizeof(double) * rows, hipMemcpyHostToDevice, h->stream));
-  if (query_ids) KMX_HIP(hipMemcpyAsync(h->d_eid, query_ids, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
-  if (nss) KMX_HIP(hipMemcpyAsync(h->d_eout, nss, sizeof(double) * nq, hipMemcpyHostToDevice, h->stream));
-  if (has_prev) KMX_HIP(hipMemcpyAsync(h->d_hasprev, has_prev, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
-  int* state = h->d_tstate;
+  KMX_HIP(hipMemcpyAsync(h->qry.n.get(), n, sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->qry.id.get(), ids, sizeof(int) * rows, hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->qry.score.get(), scores, sizeof(double) * rows, hipMemcpyHostToDevice, h->stream));
+  if (query_ids) KMX_HIP(hipMemcpyAsync(h->ids.eid.get(), query_ids, sizeof(int) * nq, hipMemcpyHostToDevice,
+                                        h->stream));
+  if (nss) KMX_HIP(hipMemcpyAsync(h->ids.eout.get(), nss, sizeof(double) * nq, hipMemcpyHostToDevice, h->stream));
+  if (has_prev) KMX_HIP(hipMemcpyAsync(h->det.hasprev.get(), has_prev, sizeof(int) * nq, hipMemcpyHostToDevice,
+                                       h->stream));
+  int* state = h->d_tstate.get();
   if (!use_state) {  // a pass of its own: from zeros, in the scratch half
     state += 4;
     KMX_HIP(hipMemsetAsync(state, 0, 4 * sizeof(int), h->stream));
   }
   if ((rc = bow_time(h, 0)) || (rc = bow_time(h, 1))) return rc;
-  if ((rc = bow_launch_decide(h, nq, K, mode, params, query_ids ? h->d_eid : nullptr, h->d_n, h->d_id, h->d_score,
-                              nss ? h->d_eout : nullptr, has_prev ? h->d_hasprev : nullptr, nullptr, state)))
+  if ((rc = bow_launch_decide(h, nq, K, mode, params, query_ids ? h->ids.eid.get() : nullptr, h->qry.n.get(),
+                              h->qry.id.get(), h->qry.score.get(), nss ? h->ids.eout.get() : nullptr,
+                              has_prev ? h->det.hasprev.get() : nullptr, nullptr, state)))
     return rc;
   return bow_fetch_decide(h, nq, records_out, nullptr, nullptr);
   KMX_GUARD_END
@@ -2090,7 +1977,7 @@ extern "C" int kmx_bow_get_temporal_state(kmx_bow* h, int32_t* state4_out) {
   KMX_GUARD_BEGIN
   KMX_CHECK(h && state4_out, KMX_EINVAL, "null argument");
   KMX_HIP(hipSetDevice(h->device));
-  KMX_HIP(hipMemcpyAsync(state4_out, h->d_tstate, 4 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(state4_out, h->d_tstate.get(), 4 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   return KMX_OK;
   KMX_GUARD_END
@@ -2100,7 +1987,7 @@ extern "C" int kmx_bow_set_temporal_state(kmx_bow* h, const int32_t* state4) {
   KMX_GUARD_BEGIN
   KMX_CHECK(h && state4, KMX_EINVAL, "null argument");
   KMX_HIP(hipSetDevice(h->device));
-  KMX_HIP(hipMemcpyAsync(h->d_tstate, state4, 4 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->d_tstate.get(), state4, 4 * sizeof(int), hipMemcpyHostToDevice, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));  // the caller's array is free again
   return KMX_OK;
   KMX_GUARD_END
@@ -2143,34 +2030,32 @@ extern "C" int kmx_bow_score_pairs(kmx_bow* h, int32_t n, const int64_t* aptr, c
   if (n == 0) return KMX_OK;
   KMX_HIP(hipSetDevice(h->device));
   const size_t na = (size_t)aptr[n], nb = (size_t)bptr[n];
-  if ((size_t)n + 1 > h->pcap || std::max(na, nb) > h->pwcap) {
-    bow_free_p(h);
-    h->pcap = std::max<size_t>(n + 1, 1024);
-    h->pwcap = std::max<size_t>(std::max(na, nb), 1);
+  if ((size_t)n + 1 > h->pair.aptr.cap() || std::max(na, nb) > h->pair.aw.cap()) {
+    h->pair = BowPairSet();
+    const size_t pcap = std::max<size_t>(n + 1, 1024), pwcap = std::max<size_t>(std::max(na, nb), 1);
+    BowPairSet b;
     int rc;
-    if ((rc = bow_alloc(&h->d_aptr, h->pcap)) || (rc = bow_alloc(&h->d_bptr, h->pcap)) ||
-        (rc = bow_alloc(&h->d_aw, h->pwcap)) || (rc = bow_alloc(&h->d_bw, h->pwcap)) ||
-        (rc = bow_alloc(&h->d_av, h->pwcap)) || (rc = bow_alloc(&h->d_bv, h->pwcap)) ||
-        (rc = bow_alloc(&h->d_pout, h->pcap))) {
-      bow_free_p(h);
+    if ((rc = b.aptr.alloc(pcap)) || (rc = b.bptr.alloc(pcap)) || (rc = b.aw.alloc(pwcap)) ||
+        (rc = b.bw.alloc(pwcap)) || (rc = b.av.alloc(pwcap)) || (rc = b.bv.alloc(pwcap)) || (rc = b.out.alloc(pcap)))
       return rc;
-    }
+    h->pair = std::move(b);
   }
-  KMX_HIP(hipMemcpyAsync(h->d_aptr, aptr, sizeof(long long) * (n + 1), hipMemcpyHostToDevice, h->stream));
-  KMX_HIP(hipMemcpyAsync(h->d_bptr, bptr, sizeof(long long) * (n + 1), hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->pair.aptr.get(), aptr, sizeof(long long) * (n + 1), hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->pair.bptr.get(), bptr, sizeof(long long) * (n + 1), hipMemcpyHostToDevice, h->stream));
   if (na) {
-    KMX_HIP(hipMemcpyAsync(h->d_aw, aw, sizeof(unsigned) * na, hipMemcpyHostToDevice, h->stream));
-    KMX_HIP(hipMemcpyAsync(h->d_av, av, sizeof(double) * na, hipMemcpyHostToDevice, h->stream));
+    KMX_HIP(hipMemcpyAsync(h->pair.aw.get(), aw, sizeof(unsigned) * na, hipMemcpyHostToDevice, h->stream));
+    KMX_HIP(hipMemcpyAsync(h->pair.av.get(), av, sizeof(double) * na, hipMemcpyHostToDevice, h->stream));
   }
   if (nb) {
-    KMX_HIP(hipMemcpyAsync(h->d_bw, bw, sizeof(unsigned) * nb, hipMemcpyHostToDevice, h->stream));
-    KMX_HIP(hipMemcpyAsync(h->d_bv, bv, sizeof(double) * nb, hipMemcpyHostToDevice, h->stream));
+    KMX_HIP(hipMemcpyAsync(h->pair.bw.get(), bw, sizeof(unsigned) * nb, hipMemcpyHostToDevice, h->stream));
+    KMX_HIP(hipMemcpyAsync(h->pair.bv.get(), bv, sizeof(double) * nb, hipMemcpyHostToDevice, h->stream));
   }
   hipLaunchKernelGGL(k_bow_pair_score, dim3((n + 255) / 256), dim3(256), 0, h->stream, n,
-                     (const long long*)h->d_aptr, (const unsigned*)h->d_aw, (const double*)h->d_av,
-                     (const long long*)h->d_bptr, (const unsigned*)h->d_bw, (const double*)h->d_bv, h->d_pout);
+                     (const long long*)h->pair.aptr.get(), (const unsigned*)h->pair.aw.get(),
+                     (const double*)h->pair.av.get(), (const long long*)h->pair.bptr.get(),
+                     (const unsigned*)h->pair.bw.get(), (const double*)h->pair.bv.get(), h->pair.out.get());
   KMX_HIP(hipGetLastError());
-  KMX_HIP(hipMemcpyAsync(out, h->d_pout, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(out, h->pair.out.get(), sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   return KMX_OK;
   KMX_GUARD_END

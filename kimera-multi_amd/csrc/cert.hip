@@ -30,6 +30,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "cert_host.h"
@@ -49,11 +50,7 @@ struct alignas(16) CtRec {
 };
 static_assert(sizeof(CtRec) == 128, "incidence record is 128 bytes");
 
-__device__ __forceinline__ double ct_wave_sum(double v) {  // lane 0 holds the sum; fixed tree
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
+using kmx::wave_sum;  // lane 0 holds the sum; fixed tree
 
 // y = M x for the symmetric 4x4 packed as (00 01 02 03 11 12 13 22 23 33)
 __device__ __forceinline__ void ct_sym4(const double* m, const double* x, double* y) {
@@ -158,7 +155,7 @@ __global__ __launch_bounds__(CT_TILE) void k_ct_point(int n, const int* __restri
     }
   }
   for (int q = 0; q < 3; ++q) {
-    const double v = ct_wave_sum(s[q]);
+    const double v = wave_sum(s[q]);
     if (threadIdx.x == 0) part[(size_t)3 * blockIdx.x + q] = v;
   }
 }
@@ -197,7 +194,7 @@ __global__ __launch_bounds__(CT_TILE) void k_ct_apply(int n, const int* __restri
     }
   }
   if (part) {
-    const double t = ct_wave_sum(s);
+    const double t = wave_sum(s);
     if (threadIdx.x == 0) part[blockIdx.x] = t;
   }
 }
@@ -211,7 +208,7 @@ __global__ __launch_bounds__(64) void k_ct_reduce(int n_tiles, int nq, const dou
   for (int q = 0; q < nq; ++q) {
     double v = 0.0;
     for (int t = lane; t < n_tiles; t += 64) v += part[(size_t)nq * t + q];
-    v = ct_wave_sum(v);
+    v = wave_sum(v);
     if (lane == 0) out[q] = root ? sqrt(v) : v;
   }
 }
@@ -237,7 +234,7 @@ __global__ __launch_bounds__(CT_TILE) void k_ct_update(int n, const double* __re
       if (ACC) y[k] += sj * v;
     }
   }
-  const double t = ct_wave_sum(s);
+  const double t = wave_sum(s);
   if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 
@@ -247,7 +244,7 @@ __global__ __launch_bounds__(CT_TILE) void k_ct_norm2(int n, const double* __res
   double s = 0.0;
   if (p < n)
     for (int c = 0; c < 4; ++c) s += u[(size_t)4 * p + c] * u[(size_t)4 * p + c];
-  const double t = ct_wave_sum(s);
+  const double t = wave_sum(s);
   if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 
@@ -364,53 +361,33 @@ __global__ __launch_bounds__(CT_TILE) void k_ct_cost(int n, const int* __restric
       for (int c = 0; c < 4; ++c) s += x[a][c] * (g[a][c] + v[c]);
     }
   }
-  const double t = ct_wave_sum(s);
+  const double t = wave_sum(s);
   if (threadIdx.x == 0) part[(size_t)gridDim.y * blockIdx.x + blockIdx.y] = t;
 }
 
-struct CtDev {
-  int* ptr = nullptr;
-  CtRec* rec = nullptr;
-  double *wkt = nullptr, *X = nullptr, *Dm = nullptr, *Lam = nullptr, *part = nullptr, *scal = nullptr;
-  double* vec[3] = {nullptr, nullptr, nullptr};
-  double *y = nullptr, *alpha = nullptr, *B = nullptr, *sv = nullptr;
-  int coef_cap = 0;
+struct CtDev {  // what set_graph puts on the device; replaced as a whole
+  kmx::DevBuf<int> ptr;
+  kmx::DevBuf<CtRec> rec;
+  kmx::DevBuf<double> wkt, X, Dm, Lam, part, scal;
+  kmx::DevBuf<double> vec[3];
+  kmx::DevBuf<double> y;
+  // min_eig's coefficients, max_steps + 1 each, allocated by its first call and regrown together (sv last)
+  kmx::DevBuf<double> alpha, B, sv;
   // the escape step: the candidates [n_alpha][n][r + 1][4] (grown on demand), the tile partials
   // [n_tiles][CT_MAX_ALPHA], and the step lengths [0..7] with the costs [8..15]
-  double *cand = nullptr, *epart = nullptr, *esc = nullptr;
-  size_t cand_cap = 0;
+  kmx::DevBuf<double> cand, epart, esc;
 };
-
-void ct_free(CtDev& d) {
-  void* ptrs[] = {d.ptr, d.rec, d.wkt, d.X, d.Dm, d.Lam, d.part, d.scal, d.vec[0], d.vec[1], d.vec[2],
-                  d.y, d.alpha, d.B, d.sv, d.cand, d.epart, d.esc};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  d = CtDev();
-}
-
-template <class T>
-int ct_alloc(T** p, size_t count) {
-  if (hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
-    *p = nullptr;
-    return kmx::fail(KMX_ENOMEM, "hipMalloc failed");
-  }
-  return KMX_OK;
-}
 
 enum { EV_POINT0, EV_POINT1, EV_A, EV_B, EV_C, EV_D, EV_COUNT };  // EV_A..EV_D: min_eig's, and escape's
 
 }  // namespace
 
-struct kmx_cert {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+struct kmx_cert : kmx::StreamCore {
   bool have_graph = false, have_point = false;
   int r = 0;
   kmx::CertGraph g;
   CtDev dev;
-  hipEvent_t ev[EV_COUNT] = {};
+  kmx::Event ev[EV_COUNT];
   bool timed_point = false;
   // the last min_eig's: device ms of the Lanczos steps, of the vector pass, of the transfers (HIP events,
   // summed over the batches), and host ms of the decisions and of the whole call (the host clock)
@@ -430,9 +407,9 @@ int ct_upload_weights(kmx_cert* h, CtDev& d, const kmx::CertGraph& g, const doub
   kmx::cert_record_weights(g, weight, &wkt);
   const int64_t nrec = (int64_t)g.inc_edge.size();
   if (nrec > 0) {
-    KMX_HIP(hipMemcpyAsync(d.wkt, wkt.data(), wkt.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_ct_weights, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, h->stream, nrec, d.wkt,
-                       d.rec);
+    KMX_HIP(hipMemcpyAsync(d.wkt.get(), wkt.data(), wkt.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_ct_weights, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, h->stream, nrec, d.wkt.get(),
+                       d.rec.get());
     KMX_HIP(hipGetLastError());
   }
   KMX_HIP(hipStreamSynchronize(h->stream));  // wkt is a host temporary
@@ -447,7 +424,8 @@ int ct_run_point(kmx_cert* h) {
   hipStream_t s = h->stream;
 #define KMX_CT_POINT(RR)                                                                                       \
   case RR:                                                                                                     \
-    hipLaunchKernelGGL((k_ct_point<RR>), gt, wave, 0, s, g.n, d.ptr, d.rec, d.X, d.Dm, d.Lam, d.part);         \
+    hipLaunchKernelGGL((k_ct_point<RR>), gt, wave, 0, s, g.n, d.ptr.get(), d.rec.get(), d.X.get(), d.Dm.get(), \
+                       d.Lam.get(), d.part.get());                                                             \
     break;
   switch (h->r) {
     KMX_CT_POINT(3)
@@ -460,7 +438,7 @@ int ct_run_point(kmx_cert* h) {
       return kmx::fail(KMX_EINVAL, "r outside 3..8");
   }
 #undef KMX_CT_POINT
-  hipLaunchKernelGGL(k_ct_reduce, dim3(1), dim3(64), 0, s, g.n_tiles, 3, d.part, d.scal, 0);
+  hipLaunchKernelGGL(k_ct_reduce, dim3(1), dim3(64), 0, s, g.n_tiles, 3, d.part.get(), d.scal.get(), 0);
   KMX_HIP(hipGetLastError());
   return KMX_OK;
 }
@@ -473,13 +451,15 @@ void ct_enqueue_steps(kmx_cert* h, int j0, int k) {
   const dim3 gt(g.n_tiles), wave(CT_TILE);
   hipStream_t s = h->stream;
   for (int j = j0; j < j0 + k; ++j) {
-    const double* u = d.vec[j % 3];
-    const double* up = d.vec[(j + 2) % 3];
-    double* w = d.vec[(j + 1) % 3];
-    hipLaunchKernelGGL(k_ct_apply, gt, wave, 0, s, g.n, d.ptr, d.rec, d.Dm, u, up, d.B, j, w, d.part);
-    hipLaunchKernelGGL(k_ct_reduce, dim3(1), dim3(64), 0, s, g.n_tiles, 1, d.part, d.alpha + j, 0);
-    hipLaunchKernelGGL((k_ct_update<ACC>), gt, wave, 0, s, g.n, u, d.B, d.alpha, j, w, d.part, d.sv, d.y);
-    hipLaunchKernelGGL(k_ct_reduce, dim3(1), dim3(64), 0, s, g.n_tiles, 1, d.part, d.B + j + 1, 1);
+    const double* u = d.vec[j % 3].get();
+    const double* up = d.vec[(j + 2) % 3].get();
+    double* w = d.vec[(j + 1) % 3].get();
+    hipLaunchKernelGGL(k_ct_apply, gt, wave, 0, s, g.n, d.ptr.get(), d.rec.get(), d.Dm.get(), u, up, d.B.get(), j, w,
+                       d.part.get());
+    hipLaunchKernelGGL(k_ct_reduce, dim3(1), dim3(64), 0, s, g.n_tiles, 1, d.part.get(), d.alpha.get() + j, 0);
+    hipLaunchKernelGGL((k_ct_update<ACC>), gt, wave, 0, s, g.n, u, d.B.get(), d.alpha.get(), j, w, d.part.get(),
+                       d.sv.get(), d.y.get());
+    hipLaunchKernelGGL(k_ct_reduce, dim3(1), dim3(64), 0, s, g.n_tiles, 1, d.part.get(), d.B.get() + j + 1, 1);
   }
 }
 
@@ -488,8 +468,8 @@ int ct_start_norm(kmx_cert* h) {
   CtDev& d = h->dev;
   const kmx::CertGraph& g = h->g;
   hipStream_t s = h->stream;
-  hipLaunchKernelGGL(k_ct_norm2, dim3(g.n_tiles), dim3(CT_TILE), 0, s, g.n, d.vec[0], d.part);
-  hipLaunchKernelGGL(k_ct_reduce, dim3(1), dim3(64), 0, s, g.n_tiles, 1, d.part, d.B, 1);
+  hipLaunchKernelGGL(k_ct_norm2, dim3(g.n_tiles), dim3(CT_TILE), 0, s, g.n, d.vec[0].get(), d.part.get());
+  hipLaunchKernelGGL(k_ct_reduce, dim3(1), dim3(64), 0, s, g.n_tiles, 1, d.part.get(), d.B.get(), 1);
   KMX_HIP(hipGetLastError());
   return KMX_OK;
 }
@@ -511,47 +491,21 @@ double ct_now_ms() {
 extern "C" int kmx_cert_create(int device, kmx_cert** out) {
   KMX_GUARD_BEGIN
   KMX_CHECK(out, KMX_EINVAL, "null argument");
-  int ndev = 0;
-  KMX_HIP(hipGetDeviceCount(&ndev));
-  KMX_CHECK(device >= 0 && device < ndev, KMX_EINVAL, "bad HIP device ordinal");
-  KMX_HIP(hipSetDevice(device));
-  kmx_cert* h = new kmx_cert();
-  h->device = device;
-  bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
-  h->own_stream = ok;
-  for (int k = 0; ok && k < EV_COUNT; ++k) ok = hipEventCreate(&h->ev[k]) == hipSuccess;
-  if (!ok) {
-    for (hipEvent_t e : h->ev)
-      if (e) (void)hipEventDestroy(e);
-    if (h->own_stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-    return kmx::fail(KMX_EHIP, "hipStreamCreate / hipEventCreate failed");
-  }
-  *out = h;
+  std::unique_ptr<kmx_cert> h(new kmx_cert());
+  int rc;
+  if ((rc = h->open(device)) || (rc = kmx::create_events(h->ev))) return rc;
+  *out = h.release();
   return KMX_OK;
   KMX_GUARD_END
 }
 
 extern "C" int kmx_cert_destroy(kmx_cert* h) {
-  if (!h) return KMX_OK;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  ct_free(h->dev);
-  for (hipEvent_t e : h->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-  return KMX_OK;
+  return kmx::destroy(h);
 }
 
 extern "C" int kmx_cert_set_stream(kmx_cert* h, void* s) {
   KMX_CHECK(h, KMX_EINVAL, "null handle");
-  KMX_HIP(hipSetDevice(h->device));
-  if (h->stream) KMX_HIP(hipStreamSynchronize(h->stream));
-  if (h->own_stream && h->stream) KMX_HIP(hipStreamDestroy(h->stream));
-  h->own_stream = false;
-  h->stream = reinterpret_cast<hipStream_t>(s);
-  return KMX_OK;
+  return h->adopt(s, true);
 }
 
 extern "C" int kmx_cert_set_graph(kmx_cert* h, int32_t n_poses, int64_t n_edges, const int32_t* src,
@@ -578,27 +532,23 @@ extern "C" int kmx_cert_set_graph(kmx_cert* h, int32_t n_poses, int64_t n_edges,
     c.pad0 = 0;
     c.pad1 = 0.0;
   }
+  // built aside, committed by the move below: an error or an exception on its way to KMX_GUARD_END frees only d
   CtDev d;
   int rc = KMX_OK;
-  if ((rc = ct_alloc(&d.ptr, n + 1)) || (rc = ct_alloc(&d.rec, nrec)) || (rc = ct_alloc(&d.wkt, 2 * nrec)) ||
-      (rc = ct_alloc(&d.X, n * 32)) || (rc = ct_alloc(&d.Dm, n * 10)) || (rc = ct_alloc(&d.Lam, n * 9)) ||
-      (rc = ct_alloc(&d.part, (size_t)3 * g.n_tiles)) || (rc = ct_alloc(&d.scal, 4)) ||
-      (rc = ct_alloc(&d.vec[0], 4 * n)) || (rc = ct_alloc(&d.vec[1], 4 * n)) || (rc = ct_alloc(&d.vec[2], 4 * n)) ||
-      (rc = ct_alloc(&d.y, 4 * n)) || (rc = ct_alloc(&d.epart, (size_t)kmx::CT_MAX_ALPHA * g.n_tiles)) ||
-      (rc = ct_alloc(&d.esc, 2 * (size_t)kmx::CT_MAX_ALPHA))) {
-    ct_free(d);
+  if ((rc = d.ptr.alloc(n + 1)) || (rc = d.rec.alloc(nrec)) || (rc = d.wkt.alloc(2 * nrec)) ||
+      (rc = d.X.alloc(n * 32)) || (rc = d.Dm.alloc(n * 10)) || (rc = d.Lam.alloc(n * 9)) ||
+      (rc = d.part.alloc((size_t)3 * g.n_tiles)) || (rc = d.scal.alloc(4)) || (rc = d.vec[0].alloc(4 * n)) ||
+      (rc = d.vec[1].alloc(4 * n)) || (rc = d.vec[2].alloc(4 * n)) || (rc = d.y.alloc(4 * n)) ||
+      (rc = d.epart.alloc((size_t)kmx::CT_MAX_ALPHA * g.n_tiles)) || (rc = d.esc.alloc(2 * (size_t)kmx::CT_MAX_ALPHA)))
     return rc;
-  }
-  hipError_t e1 = hipMemcpyAsync(d.ptr, g.inc_ptr.data(), (n + 1) * sizeof(int), hipMemcpyHostToDevice, s);
-  hipError_t e2 = nrec ? hipMemcpyAsync(d.rec, recs.data(), nrec * sizeof(CtRec), hipMemcpyHostToDevice, s)
+  hipError_t e1 = hipMemcpyAsync(d.ptr.get(), g.inc_ptr.data(), (n + 1) * sizeof(int), hipMemcpyHostToDevice, s);
+  hipError_t e2 = nrec ? hipMemcpyAsync(d.rec.get(), recs.data(), nrec * sizeof(CtRec), hipMemcpyHostToDevice, s)
                        : hipSuccess;
   if (e1 != hipSuccess || e2 != hipSuccess || (rc = ct_upload_weights(h, d, g, weight))) {
-    (void)hipStreamSynchronize(s);
-    ct_free(d);
+    (void)hipStreamSynchronize(s);  // the uploads read g and recs
     return rc ? rc : kmx::fail(KMX_EHIP, "hipMemcpyAsync failed");
   }
-  ct_free(h->dev);
-  h->dev = d;
+  h->dev = std::move(d);
   h->g = std::move(g);
   h->have_graph = true;
   h->have_point = false;
@@ -624,7 +574,7 @@ extern "C" int kmx_cert_set_weights(kmx_cert* h, const double* weight) {
   if (int rc = ct_upload_weights(h, h->dev, h->g, weight)) return rc;
   if (h->have_point) {  // D - Lambda and the point's cost follow the weights
     if (int rc = ct_run_point(h)) return rc;
-    KMX_HIP(hipMemcpyAsync(&h->cost, h->dev.scal, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    KMX_HIP(hipMemcpyAsync(&h->cost, h->dev.scal.get(), sizeof(double), hipMemcpyDeviceToHost, h->stream));
     KMX_HIP(hipStreamSynchronize(h->stream));
   }
   return KMX_OK;
@@ -643,7 +593,7 @@ extern "C" int kmx_cert_set_point(kmx_cert* h, int32_t r, const double* X, kmx_c
   hipStream_t s = h->stream;
   CtDev& d = h->dev;
   const int r_before = h->r;
-  KMX_HIP(hipMemcpyAsync(d.X, X, cnt * sizeof(double), hipMemcpyHostToDevice, s));
+  KMX_HIP(hipMemcpyAsync(d.X.get(), X, cnt * sizeof(double), hipMemcpyHostToDevice, s));
   h->r = r;
   h->have_point = false;  // the device's copy is being replaced
   h->n_esc = 0;
@@ -654,7 +604,7 @@ extern "C" int kmx_cert_set_point(kmx_cert* h, int32_t r, const double* X, kmx_c
   }
   KMX_HIP(hipEventRecord(h->ev[EV_POINT1], s));
   double sc[3] = {0.0, 0.0, 0.0};
-  KMX_HIP(hipMemcpyAsync(sc, d.scal, sizeof(sc), hipMemcpyDeviceToHost, s));
+  KMX_HIP(hipMemcpyAsync(sc, d.scal.get(), sizeof(sc), hipMemcpyDeviceToHost, s));
   KMX_HIP(hipStreamSynchronize(s));
   h->have_point = true;
   h->timed_point = true;
@@ -685,27 +635,25 @@ extern "C" int kmx_cert_escape(kmx_cert* h, const double* y, int32_t n_alpha, co
   hipStream_t s = h->stream;
   KMX_HIP(hipStreamSynchronize(s));
   const size_t need = (size_t)n_alpha * g.n * (size_t)(r + 1) * 4;
-  if (d.cand_cap < need) {  // the last escape's candidates go with the buffer
+  if (d.cand.cap() < need) {  // the last escape's candidates go with the buffer, which goes before its successor comes
     h->n_esc = 0;
-    if (d.cand) (void)hipFree(d.cand);
-    d.cand = nullptr;
-    d.cand_cap = 0;
-    if (int rc = ct_alloc(&d.cand, need)) return rc;
-    d.cand_cap = need;
+    d.cand.reset();
+    if (int rc = d.cand.alloc(need)) return rc;
   }
   h->n_esc = 0;  // the buffer is being overwritten
   h->ms_esc = h->ms_esc_xfer = 0.0;
-  double* d_alpha = d.esc;
-  double* d_cost = d.esc + kmx::CT_MAX_ALPHA;
+  double* d_alpha = d.esc.get();
+  double* d_cost = d.esc.get() + kmx::CT_MAX_ALPHA;
   KMX_HIP(hipEventRecord(h->ev[EV_A], s));
-  KMX_HIP(hipMemcpyAsync(d.y, y, N * sizeof(double), hipMemcpyHostToDevice, s));
+  KMX_HIP(hipMemcpyAsync(d.y.get(), y, N * sizeof(double), hipMemcpyHostToDevice, s));
   KMX_HIP(hipMemcpyAsync(d_alpha, alpha, (size_t)n_alpha * sizeof(double), hipMemcpyHostToDevice, s));
   KMX_HIP(hipEventRecord(h->ev[EV_B], s));
   const dim3 grid(g.n_tiles, n_alpha), wave(CT_TILE);
 #define KMX_CT_ESCAPE(RR)                                                                                  \
   case RR:                                                                                                 \
-    hipLaunchKernelGGL((k_ct_lift<RR>), grid, wave, 0, s, g.n, d.X, d.y, d_alpha, d.cand);                 \
-    hipLaunchKernelGGL((k_ct_cost<RR + 1>), grid, wave, 0, s, g.n, d.ptr, d.rec, d.cand, d.epart);         \
+    hipLaunchKernelGGL((k_ct_lift<RR>), grid, wave, 0, s, g.n, d.X.get(), d.y.get(), d_alpha, d.cand.get());\
+    hipLaunchKernelGGL((k_ct_cost<RR + 1>), grid, wave, 0, s, g.n, d.ptr.get(), d.rec.get(), d.cand.get(), \
+                       d.epart.get());                                                                     \
     break;
   switch (r) {
     KMX_CT_ESCAPE(3)
@@ -717,7 +665,7 @@ extern "C" int kmx_cert_escape(kmx_cert* h, const double* y, int32_t n_alpha, co
       return kmx::fail(KMX_EINVAL, "r outside 3..7");
   }
 #undef KMX_CT_ESCAPE
-  hipLaunchKernelGGL(k_ct_reduce, dim3(1), dim3(64), 0, s, g.n_tiles, n_alpha, d.epart, d_cost, 0);
+  hipLaunchKernelGGL(k_ct_reduce, dim3(1), dim3(64), 0, s, g.n_tiles, n_alpha, d.epart.get(), d_cost, 0);
   KMX_HIP(hipGetLastError());
   KMX_HIP(hipEventRecord(h->ev[EV_C], s));
   double cost[kmx::CT_MAX_ALPHA];
@@ -745,17 +693,17 @@ extern "C" int kmx_cert_escape_commit(kmx_cert* h, int32_t k, double* X_out, kmx
   const size_t cnt = (size_t)h->g.n * (size_t)r1 * 4;
   KMX_HIP(hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  const double* src = d.cand + (size_t)k * cnt;
+  const double* src = d.cand.get() + (size_t)k * cnt;
   KMX_HIP(hipMemcpyAsync(X_out, src, cnt * sizeof(double), hipMemcpyDeviceToHost, s));
   h->have_point = false;  // the device's copy is being replaced
   h->n_esc = 0;
-  KMX_HIP(hipMemcpyAsync(d.X, src, cnt * sizeof(double), hipMemcpyDeviceToDevice, s));
+  KMX_HIP(hipMemcpyAsync(d.X.get(), src, cnt * sizeof(double), hipMemcpyDeviceToDevice, s));
   h->r = r1;
   KMX_HIP(hipEventRecord(h->ev[EV_POINT0], s));
   if (int rc = ct_run_point(h)) return rc;
   KMX_HIP(hipEventRecord(h->ev[EV_POINT1], s));
   double sc[3] = {0.0, 0.0, 0.0};
-  KMX_HIP(hipMemcpyAsync(sc, d.scal, sizeof(sc), hipMemcpyDeviceToHost, s));
+  KMX_HIP(hipMemcpyAsync(sc, d.scal.get(), sizeof(sc), hipMemcpyDeviceToHost, s));
   KMX_HIP(hipStreamSynchronize(s));
   h->have_point = true;
   h->timed_point = true;
@@ -783,7 +731,7 @@ extern "C" int kmx_cert_get_lambda(kmx_cert* h, double* out) {
   KMX_CHECK(h && out, KMX_EINVAL, "null argument");
   KMX_CHECK(h->have_point, KMX_ESTATE, "kmx_cert_get_lambda before kmx_cert_set_point");
   KMX_HIP(hipSetDevice(h->device));
-  KMX_HIP(hipMemcpyAsync(out, h->dev.Lam, (size_t)9 * h->g.n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(out, h->dev.Lam.get(), (size_t)9 * h->g.n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   return KMX_OK;
   KMX_GUARD_END
@@ -798,11 +746,11 @@ extern "C" int kmx_cert_apply(kmx_cert* h, const double* v_in, double* out) {
   const size_t bytes = (size_t)4 * g.n * sizeof(double);
   KMX_HIP(hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  KMX_HIP(hipMemcpyAsync(d.vec[0], v_in, bytes, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_ct_apply, dim3(g.n_tiles), dim3(CT_TILE), 0, s, g.n, d.ptr, d.rec, d.Dm, d.vec[0], nullptr,
-                     nullptr, 0, d.vec[1], nullptr);
+  KMX_HIP(hipMemcpyAsync(d.vec[0].get(), v_in, bytes, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_ct_apply, dim3(g.n_tiles), dim3(CT_TILE), 0, s, g.n, d.ptr.get(), d.rec.get(), d.Dm.get(),
+                     d.vec[0].get(), nullptr, nullptr, 0, d.vec[1].get(), nullptr);
   KMX_HIP(hipGetLastError());
-  KMX_HIP(hipMemcpyAsync(out, d.vec[1], bytes, hipMemcpyDeviceToHost, s));
+  KMX_HIP(hipMemcpyAsync(out, d.vec[1].get(), bytes, hipMemcpyDeviceToHost, s));
   KMX_HIP(hipStreamSynchronize(s));
   return KMX_OK;
   KMX_GUARD_END
@@ -821,17 +769,14 @@ extern "C" int kmx_cert_min_eig(kmx_cert* h, const kmx_cert_params* p, kmx_cert_
   KMX_HIP(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   KMX_HIP(hipStreamSynchronize(s));
-  if (d.coef_cap < P.max_steps + 1) {
-    for (double** q : {&d.alpha, &d.B, &d.sv}) {
-      if (*q) (void)hipFree(*q);
-      *q = nullptr;
-    }
-    d.coef_cap = 0;
+  if (d.sv.cap() < (size_t)P.max_steps + 1) {
+    d.alpha.reset();
+    d.B.reset();
+    d.sv.reset();
     int rc = KMX_OK;
-    if ((rc = ct_alloc(&d.alpha, (size_t)P.max_steps + 1)) || (rc = ct_alloc(&d.B, (size_t)P.max_steps + 1)) ||
-        (rc = ct_alloc(&d.sv, (size_t)P.max_steps + 1)))
+    if ((rc = d.alpha.alloc((size_t)P.max_steps + 1)) || (rc = d.B.alloc((size_t)P.max_steps + 1)) ||
+        (rc = d.sv.alloc((size_t)P.max_steps + 1)))
       return rc;
-    d.coef_cap = P.max_steps + 1;
   }
   std::vector<double> u0(N);
   kmx::cert_start_vector(P.seed, N, u0.data());
@@ -842,7 +787,7 @@ extern "C" int kmx_cert_min_eig(kmx_cert* h, const kmx_cert_params* p, kmx_cert_
   const double t_call = ct_now_ms();
   const size_t vbytes = N * sizeof(double);
   KMX_HIP(hipEventRecord(h->ev[EV_A], s));
-  KMX_HIP(hipMemcpyAsync(d.vec[0], u0.data(), vbytes, hipMemcpyHostToDevice, s));
+  KMX_HIP(hipMemcpyAsync(d.vec[0].get(), u0.data(), vbytes, hipMemcpyHostToDevice, s));
   KMX_HIP(hipEventRecord(h->ev[EV_B], s));
   if (int rc = ct_start_norm(h)) return rc;
   kmx::CertScan scan;
@@ -854,8 +799,10 @@ extern "C" int kmx_cert_min_eig(kmx_cert* h, const kmx_cert_params* p, kmx_cert_
     ct_enqueue_steps<false>(h, done, k);
     KMX_HIP(hipGetLastError());
     KMX_HIP(hipEventRecord(h->ev[EV_C], s));
-    KMX_HIP(hipMemcpyAsync(alpha.data() + done, d.alpha + done, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, s));
-    KMX_HIP(hipMemcpyAsync(B.data() + done + 1, d.B + done + 1, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, s));
+    KMX_HIP(hipMemcpyAsync(alpha.data() + done, d.alpha.get() + done, (size_t)k * sizeof(double), hipMemcpyDeviceToHost,
+                           s));
+    KMX_HIP(hipMemcpyAsync(B.data() + done + 1, d.B.get() + done + 1, (size_t)k * sizeof(double), hipMemcpyDeviceToHost,
+                           s));
     KMX_HIP(hipEventRecord(h->ev[EV_D], s));
     KMX_HIP(hipStreamSynchronize(s));
     if (done == 0)
@@ -877,15 +824,15 @@ extern "C" int kmx_cert_min_eig(kmx_cert* h, const kmx_cert_params* p, kmx_cert_
     // the second pass: the same steps from the same start, y = sum_j s_j v_j
     const int ks = scan.res.steps;
     KMX_HIP(hipEventRecord(h->ev[EV_A], s));
-    KMX_HIP(hipMemcpyAsync(d.sv, scan.s.data(), (size_t)ks * sizeof(double), hipMemcpyHostToDevice, s));
-    KMX_HIP(hipMemcpyAsync(d.vec[0], u0.data(), vbytes, hipMemcpyHostToDevice, s));
+    KMX_HIP(hipMemcpyAsync(d.sv.get(), scan.s.data(), (size_t)ks * sizeof(double), hipMemcpyHostToDevice, s));
+    KMX_HIP(hipMemcpyAsync(d.vec[0].get(), u0.data(), vbytes, hipMemcpyHostToDevice, s));
     KMX_HIP(hipEventRecord(h->ev[EV_B], s));
-    KMX_HIP(hipMemsetAsync(d.y, 0, vbytes, s));
+    KMX_HIP(hipMemsetAsync(d.y.get(), 0, vbytes, s));
     if (int rc = ct_start_norm(h)) return rc;
     ct_enqueue_steps<true>(h, 0, ks);
     KMX_HIP(hipGetLastError());
     KMX_HIP(hipEventRecord(h->ev[EV_C], s));
-    KMX_HIP(hipMemcpyAsync(y_out, d.y, vbytes, hipMemcpyDeviceToHost, s));
+    KMX_HIP(hipMemcpyAsync(y_out, d.y.get(), vbytes, hipMemcpyDeviceToHost, s));
     KMX_HIP(hipEventRecord(h->ev[EV_D], s));
     KMX_HIP(hipStreamSynchronize(s));
     if (int rc = ct_span(h, EV_A, EV_B, &h->ms_xfer)) return rc;

@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "chordal_host.h"
@@ -55,11 +56,7 @@ struct ChRob {
 
 constexpr int CH_NPART = 9;  // partial sums per tile: up to 3 quantities x 3 rows
 
-__device__ __forceinline__ double wave_sum(double v) {  // lane 0 holds the sum; fixed tree
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
+using kmx::wave_sum;  // lane 0 holds the sum; fixed tree
 
 struct ChTiles {
   const int *p0, *p1, *block;
@@ -524,12 +521,6 @@ struct ChGnc {  // per incidence record
   const uint8_t* fixed;
 };
 
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
 // The GNC pass: a lane per pose over the tiles. A lane walks its records in
 // CSR order and evaluates each edge in its canonical i -> j orientation (at
 // the source's record R_ij is the stored M transposed: an index swap), so an
@@ -622,16 +613,16 @@ __global__ __launch_bounds__(CH_TILE) void k_ch_gnc(ChTiles T, ChGnc G, const do
   if (MODE == 0) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_down(mx, off, 64));
-    n1 = wave_sum_int(n1);
+    n1 = wave_sum(n1);
     if (threadIdx.x == 0) {
       pmax[tile] = mx;
       pcnt[4 * tile] = n1;
     }
   } else if (MODE == 1) {
-    n1 = wave_sum_int(n1);
-    n0 = wave_sum_int(n0);
-    nf = wave_sum_int(nf);
-    nch = wave_sum_int(nch);
+    n1 = wave_sum(n1);
+    n0 = wave_sum(n0);
+    nf = wave_sum(nf);
+    nch = wave_sum(nch);
     if (threadIdx.x == 0) {
       pcnt[4 * tile] = n1;
       pcnt[4 * tile + 1] = n0;
@@ -672,7 +663,7 @@ __global__ __launch_bounds__(64) void k_ch_decide(const int* __restrict__ tile_p
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_down(mx, off, 64));
-    n1 = wave_sum_int(n1);
+    n1 = wave_sum(n1);
     if (lane != 0) return;
     s->mu = 0.0;
     s->mu_next = 0.0;
@@ -698,7 +689,7 @@ __global__ __launch_bounds__(64) void k_ch_decide(const int* __restrict__ tile_p
     if (!last) {
       for (int t = t0 + lane; t < t1; t += 64)
         for (int q = 0; q < 4; ++q) cnt[q] += pcnt[4 * t + q];
-      for (int q = 0; q < 4; ++q) cnt[q] = wave_sum_int(cnt[q]);
+      for (int q = 0; q < 4; ++q) cnt[q] = wave_sum(cnt[q]);
     }
     if (lane != 0) return;
     if (account) {
@@ -725,67 +716,42 @@ __global__ __launch_bounds__(64) void k_ch_decide(const int* __restrict__ tile_p
   }
 }
 
-struct ChDev {  // what set_graph puts on the device
-  int *tile_p0 = nullptr, *tile_p1 = nullptr, *tile_block = nullptr, *tile_ptr = nullptr, *inc_ptr = nullptr;
-  uint32_t* inc_other = nullptr;
-  double *inc_M = nullptr, *inc_t = nullptr, *wk = nullptr, *wt = nullptr;
-  uint8_t* is_free = nullptr;
-  double *Dk = nullptr, *Dt = nullptr, *xr = nullptr, *xt = nullptr, *r = nullptr, *d = nullptr, *q = nullptr,
-         *bt = nullptr, *part = nullptr;
-  ChScal* sc = nullptr;  // [2][3 nb]: rotations, translations
-  int* ctl = nullptr;    // [2] (block, row) pairs still running, per stage
-  int n_tiles = 0;
-  // the robust solve's (allocated by its first call, ch_robust_alloc)
-  bool have_rob = false;
-  double *rkappa = nullptr, *rtau = nullptr, *rw0 = nullptr;  // [2m] per record
-  uint8_t* rfixed = nullptr;                                  // [2m]
-  double *rg = nullptr, *gwk = nullptr, *gwt = nullptr;       // [2m] g and the records' w0 g kappa / w0 g tau
-  double *gDk = nullptr, *gDt = nullptr;                      // [n]
-  double* xu = nullptr;                                       // [9n] the rotation CG's (unprojected) iterate
-  double *pmax = nullptr, *mu_in = nullptr;                   // [n_tiles], [nb]
-  int* pcnt = nullptr;                                        // [n_tiles][4]
-  ChRob* rb = nullptr;                                        // [nb]
-  int* rctl = nullptr;                                        // blocks still running
+// The robust solve's arrays: allocated as a whole by its first call after
+// set_graph (ch_robust_reserve), freed with the graph.
+struct ChRobDev {
+  kmx::DevBuf<double> rkappa, rtau, rw0;  // [2m] per record
+  kmx::DevBuf<uint8_t> rfixed;            // [2m]
+  kmx::DevBuf<double> rg, gwk, gwt;       // [2m] g and the records' w0 g kappa / w0 g tau
+  kmx::DevBuf<double> gDk, gDt;           // [n]
+  kmx::DevBuf<double> xu;                 // [9n] the rotation CG's (unprojected) iterate
+  kmx::DevBuf<double> pmax, mu_in;        // [n_tiles], [nb]
+  kmx::DevBuf<int> pcnt;                  // [n_tiles][4]
+  kmx::DevBuf<ChRob> rb;                  // [nb]
+  kmx::DevBuf<int> rctl;                  // blocks still running
 };
 
-void ch_free(ChDev& d) {
-  void* ptrs[] = {d.tile_p0, d.tile_p1, d.tile_block, d.tile_ptr, d.inc_ptr, d.inc_other, d.inc_M, d.inc_t,
-                  d.wk, d.wt, d.is_free, d.Dk, d.Dt, d.xr, d.xt, d.r, d.d, d.q, d.bt, d.part, d.sc, d.ctl,
-                  d.rkappa, d.rtau, d.rw0, d.rfixed, d.rg, d.gwk, d.gwt, d.gDk, d.gDt, d.xu, d.pmax, d.mu_in, d.pcnt,
-                  d.rb, d.rctl};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  d = ChDev();
-}
-
-template <class T>
-int ch_alloc(T** p, size_t count) {
-  if (hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
-    *p = nullptr;
-    return kmx::fail(KMX_ENOMEM, "hipMalloc failed");
-  }
-  return KMX_OK;
-}
-
-template <class T>
-int ch_put(T** p, const std::vector<T>& v, hipStream_t s) {
-  if (int rc = ch_alloc(p, v.size())) return rc;
-  if (!v.empty()) KMX_HIP(hipMemcpyAsync(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
-  return KMX_OK;
-}
+struct ChDev {  // what set_graph puts on the device; replaced as a whole
+  kmx::DevBuf<int> tile_p0, tile_p1, tile_block, tile_ptr, inc_ptr;
+  kmx::DevBuf<uint32_t> inc_other;
+  kmx::DevBuf<double> inc_M, inc_t, wk, wt;
+  kmx::DevBuf<uint8_t> is_free;
+  kmx::DevBuf<double> Dk, Dt, xr, xt, r, d, q, bt, part;
+  kmx::DevBuf<ChScal> sc;  // [2][3 nb]: rotations, translations
+  kmx::DevBuf<int> ctl;    // [2] (block, row) pairs still running, per stage
+  int n_tiles = 0;
+  bool have_rob = false;
+  ChRobDev rob;
+};
 
 }  // namespace
 
-struct kmx_chordal {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+struct kmx_chordal : kmx::StreamCore {
   bool have_graph = false;
   kmx::ChordalGraph g;
   ChDev dev;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  kmx::Event ev[5];
   bool timed = false;
-  std::vector<hipEvent_t> rev;  // the robust solve's: start, first solve, end, then a pair per GNC pass
+  std::vector<kmx::Event> rev;  // the robust solve's: start, first solve, end, then a pair per GNC pass
   double rstats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   bool rtimed = false;
 };
@@ -796,11 +762,11 @@ int ch_upload_weights(kmx_chordal* h, ChDev& d, const kmx::ChordalGraph& g, cons
   std::vector<double> wk, wt;
   kmx::chordal_record_weights(g, weight, &wk, &wt);
   if (!wk.empty()) {
-    KMX_HIP(hipMemcpyAsync(d.wk, wk.data(), wk.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    KMX_HIP(hipMemcpyAsync(d.wt, wt.data(), wt.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    KMX_HIP(hipMemcpyAsync(d.wk.get(), wk.data(), wk.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    KMX_HIP(hipMemcpyAsync(d.wt.get(), wt.data(), wt.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   }
-  hipLaunchKernelGGL(k_ch_diag, dim3((g.n + 255) / 256), dim3(256), 0, h->stream, g.n, d.inc_ptr, d.wk, d.wt, d.Dk,
-                     d.Dt);
+  hipLaunchKernelGGL(k_ch_diag, dim3((g.n + 255) / 256), dim3(256), 0, h->stream, g.n, d.inc_ptr.get(), d.wk.get(),
+                     d.wt.get(), d.Dk.get(), d.Dt.get());
   KMX_HIP(hipGetLastError());
   KMX_HIP(hipStreamSynchronize(h->stream));  // wk / wt are host temporaries
   return KMX_OK;
@@ -814,16 +780,16 @@ int ch_stage(kmx_chordal* h, int stage, double* x, const double* rhs, double rto
   ChDev& d = h->dev;
   const kmx::ChordalGraph& g = h->g;
   hipStream_t s = h->stream;
-  const ChTiles T{d.tile_p0, d.tile_p1, d.tile_block};
-  const ChInc I{d.inc_ptr, d.inc_other, w, d.inc_M};
-  ChScal* sc = d.sc + (size_t)stage * 3 * g.nb;
-  int* ctl = d.ctl + stage;
+  const ChTiles T{d.tile_p0.get(), d.tile_p1.get(), d.tile_block.get()};
+  const ChInc I{d.inc_ptr.get(), d.inc_other.get(), w, d.inc_M.get()};
+  ChScal* sc = d.sc.get() + (size_t)stage * 3 * g.nb;
+  int* ctl = d.ctl.get() + stage;
   const double rtol2 = rtol * rtol;
   const dim3 gt(d.n_tiles), gb(g.nb), wave(CH_TILE);
   KMX_HIP(hipMemsetAsync(ctl, 0, sizeof(int), s));
-  hipLaunchKernelGGL((k_ch_apply<W, true>), gt, wave, 0, s, T, I, d.is_free, D, x, rhs, d.r, d.d, sc, ctl, d.part,
-                     rb);
-  hipLaunchKernelGGL((k_ch_reduce<0>), gb, wave, 0, s, d.tile_ptr, d.part, sc, ctl, rtol2, max_it, rb);
+  hipLaunchKernelGGL((k_ch_apply<W, true>), gt, wave, 0, s, T, I, d.is_free.get(), D, x, rhs, d.r.get(), d.d.get(), sc,
+                     ctl, d.part.get(), rb);
+  hipLaunchKernelGGL((k_ch_reduce<0>), gb, wave, 0, s, d.tile_ptr.get(), d.part.get(), sc, ctl, rtol2, max_it, rb);
   KMX_HIP(hipGetLastError());
   for (int done = 0; done < max_it;) {
     int running = 0;
@@ -832,12 +798,15 @@ int ch_stage(kmx_chordal* h, int stage, double* x, const double* rhs, double rto
     if (running == 0) break;
     const int k = std::min(check_every, max_it - done);
     for (int it = 0; it < k; ++it) {
-      hipLaunchKernelGGL((k_ch_apply<W, false>), gt, wave, 0, s, T, I, d.is_free, D, d.d, nullptr, d.q, nullptr, sc,
-                         ctl, d.part, nullptr);
-      hipLaunchKernelGGL((k_ch_reduce<1>), gb, wave, 0, s, d.tile_ptr, d.part, sc, ctl, rtol2, max_it, nullptr);
-      hipLaunchKernelGGL((k_ch_update<W>), gt, wave, 0, s, T, d.is_free, D, x, d.r, d.d, d.q, sc, ctl, d.part);
-      hipLaunchKernelGGL((k_ch_reduce<2>), gb, wave, 0, s, d.tile_ptr, d.part, sc, ctl, rtol2, max_it, nullptr);
-      hipLaunchKernelGGL((k_ch_dir<W>), gt, wave, 0, s, T, d.is_free, D, d.r, d.d, sc, ctl);
+      hipLaunchKernelGGL((k_ch_apply<W, false>), gt, wave, 0, s, T, I, d.is_free.get(), D, d.d.get(), nullptr,
+                         d.q.get(), nullptr, sc, ctl, d.part.get(), nullptr);
+      hipLaunchKernelGGL((k_ch_reduce<1>), gb, wave, 0, s, d.tile_ptr.get(), d.part.get(), sc, ctl, rtol2, max_it,
+                         nullptr);
+      hipLaunchKernelGGL((k_ch_update<W>), gt, wave, 0, s, T, d.is_free.get(), D, x, d.r.get(), d.d.get(), d.q.get(),
+                         sc, ctl, d.part.get());
+      hipLaunchKernelGGL((k_ch_reduce<2>), gb, wave, 0, s, d.tile_ptr.get(), d.part.get(), sc, ctl, rtol2, max_it,
+                         nullptr);
+      hipLaunchKernelGGL((k_ch_dir<W>), gt, wave, 0, s, T, d.is_free.get(), D, d.r.get(), d.d.get(), sc, ctl);
     }
     KMX_HIP(hipGetLastError());
     done += k;
@@ -850,49 +819,21 @@ int ch_stage(kmx_chordal* h, int stage, double* x, const double* rhs, double rto
 extern "C" int kmx_chordal_create(int device, kmx_chordal** out) {
   KMX_GUARD_BEGIN
   KMX_CHECK(out, KMX_EINVAL, "null argument");
-  int ndev = 0;
-  KMX_HIP(hipGetDeviceCount(&ndev));
-  KMX_CHECK(device >= 0 && device < ndev, KMX_EINVAL, "bad HIP device ordinal");
-  KMX_HIP(hipSetDevice(device));
-  kmx_chordal* h = new kmx_chordal();
-  h->device = device;
-  bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
-  h->own_stream = ok;
-  for (int k = 0; ok && k < 5; ++k) ok = hipEventCreate(&h->ev[k]) == hipSuccess;
-  if (!ok) {
-    for (hipEvent_t e : h->ev)
-      if (e) (void)hipEventDestroy(e);
-    if (h->own_stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-    return kmx::fail(KMX_EHIP, "hipStreamCreate / hipEventCreate failed");
-  }
-  *out = h;
+  std::unique_ptr<kmx_chordal> h(new kmx_chordal());
+  int rc;
+  if ((rc = h->open(device)) || (rc = kmx::create_events(h->ev))) return rc;
+  *out = h.release();
   return KMX_OK;
   KMX_GUARD_END
 }
 
 extern "C" int kmx_chordal_destroy(kmx_chordal* h) {
-  if (!h) return KMX_OK;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  ch_free(h->dev);
-  for (hipEvent_t e : h->ev)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : h->rev)
-    if (e) (void)hipEventDestroy(e);
-  if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-  return KMX_OK;
+  return kmx::destroy(h);
 }
 
 extern "C" int kmx_chordal_set_stream(kmx_chordal* h, void* s) {
   KMX_CHECK(h, KMX_EINVAL, "null handle");
-  KMX_HIP(hipSetDevice(h->device));
-  if (h->stream) KMX_HIP(hipStreamSynchronize(h->stream));
-  if (h->own_stream && h->stream) KMX_HIP(hipStreamDestroy(h->stream));
-  h->own_stream = false;
-  h->stream = reinterpret_cast<hipStream_t>(s);
-  return KMX_OK;
+  return h->adopt(s, true);
 }
 
 extern "C" int kmx_chordal_set_graph(kmx_chordal* h, int32_t n_poses, int32_t n_blocks, const int32_t* block_ptr,
@@ -909,30 +850,28 @@ extern "C" int kmx_chordal_set_graph(kmx_chordal* h, int32_t n_poses, int32_t n_
   KMX_HIP(hipSetDevice(h->device));
   KMX_HIP(hipStreamSynchronize(h->stream));
   hipStream_t s = h->stream;
+  // built aside, committed by the move below: an error or an exception on its way to KMX_GUARD_END frees only d
   ChDev d;
   d.n_tiles = (int)g.tile_p0.size();
   const size_t n = (size_t)g.n, nrec = g.inc_other.size();
   int rc = KMX_OK;
-  if ((rc = ch_put(&d.tile_p0, g.tile_p0, s)) || (rc = ch_put(&d.tile_p1, g.tile_p1, s)) ||
-      (rc = ch_put(&d.tile_block, g.tile_block, s)) || (rc = ch_put(&d.tile_ptr, g.tile_ptr, s)) ||
-      (rc = ch_put(&d.inc_ptr, g.inc_ptr, s)) || (rc = ch_put(&d.inc_other, g.inc_other, s)) ||
-      (rc = ch_put(&d.inc_M, g.inc_M, s)) || (rc = ch_put(&d.inc_t, g.inc_t, s)) ||
-      (rc = ch_put(&d.is_free, g.is_free, s)) || (rc = ch_alloc(&d.wk, nrec)) || (rc = ch_alloc(&d.wt, nrec)) ||
-      (rc = ch_alloc(&d.Dk, n)) || (rc = ch_alloc(&d.Dt, n)) || (rc = ch_alloc(&d.xr, 9 * n)) ||
-      (rc = ch_alloc(&d.xt, 3 * n)) || (rc = ch_alloc(&d.r, 9 * n)) || (rc = ch_alloc(&d.d, 9 * n)) ||
-      (rc = ch_alloc(&d.q, 9 * n)) || (rc = ch_alloc(&d.bt, 3 * n)) ||
-      (rc = ch_alloc(&d.part, (size_t)CH_NPART * d.n_tiles)) || (rc = ch_alloc(&d.sc, (size_t)6 * g.nb)) ||
-      (rc = ch_alloc(&d.ctl, 2)) || (rc = ch_upload_weights(h, d, g, weight))) {
-    (void)hipStreamSynchronize(s);
-    ch_free(d);
+  if ((rc = d.tile_p0.put(g.tile_p0, s)) || (rc = d.tile_p1.put(g.tile_p1, s)) ||
+      (rc = d.tile_block.put(g.tile_block, s)) || (rc = d.tile_ptr.put(g.tile_ptr, s)) ||
+      (rc = d.inc_ptr.put(g.inc_ptr, s)) || (rc = d.inc_other.put(g.inc_other, s)) ||
+      (rc = d.inc_M.put(g.inc_M, s)) || (rc = d.inc_t.put(g.inc_t, s)) ||
+      (rc = d.is_free.put(g.is_free, s)) || (rc = d.wk.alloc(nrec)) || (rc = d.wt.alloc(nrec)) ||
+      (rc = d.Dk.alloc(n)) || (rc = d.Dt.alloc(n)) || (rc = d.xr.alloc(9 * n)) || (rc = d.xt.alloc(3 * n)) ||
+      (rc = d.r.alloc(9 * n)) || (rc = d.d.alloc(9 * n)) || (rc = d.q.alloc(9 * n)) || (rc = d.bt.alloc(3 * n)) ||
+      (rc = d.part.alloc((size_t)CH_NPART * d.n_tiles)) || (rc = d.sc.alloc((size_t)6 * g.nb)) ||
+      (rc = d.ctl.alloc(2)) || (rc = ch_upload_weights(h, d, g, weight))) {
+    (void)hipStreamSynchronize(s);  // the uploads read g
     return rc;
   }
   // the incidence arrays are only read on the device from here on; the host
   // keeps what set_weights needs
   g.inc_M = std::vector<double>();
   g.inc_t = std::vector<double>();
-  ch_free(h->dev);
-  h->dev = d;
+  h->dev = std::move(d);
   h->g = std::move(g);
   h->have_graph = true;
   h->timed = false;
@@ -991,24 +930,25 @@ extern "C" int kmx_chordal_solve(kmx_chordal* h, const kmx_chordal_params* p, co
   KMX_HIP(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   KMX_HIP(hipEventRecord(h->ev[0], s));
-  KMX_HIP(hipMemcpyAsync(d.xr, xr.data(), 9 * n * sizeof(double), hipMemcpyHostToDevice, s));
-  KMX_HIP(hipMemcpyAsync(d.xt, xt.data(), 3 * n * sizeof(double), hipMemcpyHostToDevice, s));
+  KMX_HIP(hipMemcpyAsync(d.xr.get(), xr.data(), 9 * n * sizeof(double), hipMemcpyHostToDevice, s));
+  KMX_HIP(hipMemcpyAsync(d.xt.get(), xt.data(), 3 * n * sizeof(double), hipMemcpyHostToDevice, s));
   KMX_HIP(hipEventRecord(h->ev[1], s));
-  int rc = ch_stage<3>(h, 0, d.xr, nullptr, rtol, max_it, check_every, d.wk, d.Dk, nullptr);
+  int rc = ch_stage<3>(h, 0, d.xr.get(), nullptr, rtol, max_it, check_every, d.wk.get(), d.Dk.get(), nullptr);
   if (rc) return rc;
   const dim3 gp((g.n + 255) / 256), bp(256);
-  hipLaunchKernelGGL(k_ch_project, gp, bp, 0, s, g.n, d.is_free, d.xr);
+  hipLaunchKernelGGL(k_ch_project, gp, bp, 0, s, g.n, d.is_free.get(), d.xr.get());
   KMX_HIP(hipGetLastError());
   KMX_HIP(hipEventRecord(h->ev[2], s));
-  hipLaunchKernelGGL(k_ch_rhs_t, gp, bp, 0, s, g.n, d.inc_ptr, d.inc_other, d.wt, d.inc_t, d.is_free, d.xr, d.bt);
+  hipLaunchKernelGGL(k_ch_rhs_t, gp, bp, 0, s, g.n, d.inc_ptr.get(), d.inc_other.get(), d.wt.get(), d.inc_t.get(),
+                     d.is_free.get(), d.xr.get(), d.bt.get());
   KMX_HIP(hipGetLastError());
-  rc = ch_stage<1>(h, 1, d.xt, d.bt, rtol, max_it, check_every, d.wt, d.Dt, nullptr);
+  rc = ch_stage<1>(h, 1, d.xt.get(), d.bt.get(), rtol, max_it, check_every, d.wt.get(), d.Dt.get(), nullptr);
   if (rc) return rc;
   KMX_HIP(hipEventRecord(h->ev[3], s));
   std::vector<ChScal> sc((size_t)6 * g.nb);
-  KMX_HIP(hipMemcpyAsync(R_out, d.xr, 9 * n * sizeof(double), hipMemcpyDeviceToHost, s));
-  KMX_HIP(hipMemcpyAsync(t_out, d.xt, 3 * n * sizeof(double), hipMemcpyDeviceToHost, s));
-  KMX_HIP(hipMemcpyAsync(sc.data(), d.sc, sc.size() * sizeof(ChScal), hipMemcpyDeviceToHost, s));
+  KMX_HIP(hipMemcpyAsync(R_out, d.xr.get(), 9 * n * sizeof(double), hipMemcpyDeviceToHost, s));
+  KMX_HIP(hipMemcpyAsync(t_out, d.xt.get(), 3 * n * sizeof(double), hipMemcpyDeviceToHost, s));
+  KMX_HIP(hipMemcpyAsync(sc.data(), d.sc.get(), sc.size() * sizeof(ChScal), hipMemcpyDeviceToHost, s));
   KMX_HIP(hipEventRecord(h->ev[4], s));
   KMX_HIP(hipStreamSynchronize(s));
   h->timed = true;
@@ -1049,7 +989,7 @@ extern "C" int kmx_chordal_get_timing(kmx_chordal* h, double* ms) {
 namespace {
 
 // The robust solve's device arrays, at its first call after set_graph.
-int ch_robust_alloc(kmx_chordal* h) {
+int ch_robust_reserve(kmx_chordal* h) {
   ChDev& d = h->dev;
   if (d.have_rob) return KMX_OK;
   const kmx::ChordalGraph& g = h->g;
@@ -1059,17 +999,18 @@ int ch_robust_alloc(kmx_chordal* h) {
     rk[k] = g.kappa[g.inc_edge[k]];
     rt[k] = g.tau[g.inc_edge[k]];
   }
+  ChRobDev b;
   int rc = KMX_OK;
-  if ((rc = ch_put(&d.rkappa, rk, h->stream)) || (rc = ch_put(&d.rtau, rt, h->stream)) ||
-      (rc = ch_alloc(&d.rw0, nrec)) || (rc = ch_alloc(&d.rfixed, nrec)) || (rc = ch_alloc(&d.rg, nrec)) ||
-      (rc = ch_alloc(&d.gwk, nrec)) || (rc = ch_alloc(&d.gwt, nrec)) || (rc = ch_alloc(&d.gDk, n)) ||
-      (rc = ch_alloc(&d.gDt, n)) || (rc = ch_alloc(&d.xu, 9 * n)) || (rc = ch_alloc(&d.pmax, (size_t)d.n_tiles)) ||
-      (rc = ch_alloc(&d.mu_in, (size_t)g.nb)) || (rc = ch_alloc(&d.pcnt, (size_t)4 * d.n_tiles)) ||
-      (rc = ch_alloc(&d.rb, (size_t)g.nb)) || (rc = ch_alloc(&d.rctl, 1))) {
+  if ((rc = b.rkappa.put(rk, h->stream)) || (rc = b.rtau.put(rt, h->stream)) || (rc = b.rw0.alloc(nrec)) ||
+      (rc = b.rfixed.alloc(nrec)) || (rc = b.rg.alloc(nrec)) || (rc = b.gwk.alloc(nrec)) ||
+      (rc = b.gwt.alloc(nrec)) || (rc = b.gDk.alloc(n)) || (rc = b.gDt.alloc(n)) || (rc = b.xu.alloc(9 * n)) ||
+      (rc = b.pmax.alloc((size_t)d.n_tiles)) || (rc = b.mu_in.alloc((size_t)g.nb)) ||
+      (rc = b.pcnt.alloc((size_t)4 * d.n_tiles)) || (rc = b.rb.alloc((size_t)g.nb)) || (rc = b.rctl.alloc(1))) {
     (void)hipStreamSynchronize(h->stream);
-    return rc;  // what was allocated is freed with the graph
+    return rc;
   }
   KMX_HIP(hipStreamSynchronize(h->stream));  // rk / rt are host temporaries
+  d.rob = std::move(b);
   d.have_rob = true;
   return KMX_OK;
 }
@@ -1084,15 +1025,18 @@ int ch_robust_upload_edges(kmx_chordal* h, const uint8_t* fixed) {
   for (size_t k = 0; k < nrec; ++k) w0[k] = g.w0[g.inc_edge[k]];
   kmx::chordal_record_fixed(g, fixed, &fx);
   if (nrec) {
-    KMX_HIP(hipMemcpyAsync(d.rw0, w0.data(), nrec * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    KMX_HIP(hipMemcpyAsync(d.rfixed, fx.data(), nrec, hipMemcpyHostToDevice, h->stream));
+    KMX_HIP(hipMemcpyAsync(d.rob.rw0.get(), w0.data(), nrec * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    KMX_HIP(hipMemcpyAsync(d.rob.rfixed.get(), fx.data(), nrec, hipMemcpyHostToDevice, h->stream));
   }
   KMX_HIP(hipStreamSynchronize(h->stream));  // host temporaries
   return KMX_OK;
 }
 
+ChTiles ch_tiles(const ChDev& d) { return ChTiles{d.tile_p0.get(), d.tile_p1.get(), d.tile_block.get()}; }
+
 ChGnc ch_gnc_args(const ChDev& d) {
-  return ChGnc{d.inc_ptr, d.inc_other, d.inc_M, d.inc_t, d.rkappa, d.rtau, d.rw0, d.rfixed};
+  return ChGnc{d.inc_ptr.get(), d.inc_other.get(), d.inc_M.get(), d.inc_t.get(), d.rob.rkappa.get(), d.rob.rtau.get(),
+               d.rob.rw0.get(), d.rob.rfixed.get()};
 }
 
 // A per-record array back to the caller's edges (an edge's two records hold the same bits).
@@ -1103,9 +1047,9 @@ void ch_records_to_edges(const kmx::ChordalGraph& g, const std::vector<double>& 
 
 int ch_event(kmx_chordal* h, size_t k, hipEvent_t* out) {
   while (h->rev.size() <= k) {
-    hipEvent_t e = nullptr;
-    KMX_HIP(hipEventCreate(&e));
-    h->rev.push_back(e);
+    kmx::Event e;
+    if (int rc = e.create()) return rc;
+    h->rev.push_back(std::move(e));
   }
   *out = h->rev[k];
   return KMX_OK;
@@ -1130,26 +1074,26 @@ extern "C" int kmx_chordal_residuals(kmx_chordal* h, const double* R, const doub
       KMX_CHECK(std::isfinite(mu[b]) && mu[b] > 0, KMX_EINVAL, "kmx_chordal_residuals: mu must be finite and > 0");
   const double c = barc > 0 ? barc : 5.0;
   KMX_HIP(hipSetDevice(h->device));
-  if (int rc = ch_robust_alloc(h)) return rc;
+  if (int rc = ch_robust_reserve(h)) return rc;
   if (int rc = ch_robust_upload_edges(h, fixed)) return rc;
   ChDev& d = h->dev;
   hipStream_t s = h->stream;
   // the CG's scratch holds the caller's poses, the robust solve's record
   // weights take r^2 and g: both are rewritten by whoever uses them next
-  KMX_HIP(hipMemcpyAsync(d.r, R, 9 * n * sizeof(double), hipMemcpyHostToDevice, s));
-  KMX_HIP(hipMemcpyAsync(d.q, t, 3 * n * sizeof(double), hipMemcpyHostToDevice, s));
-  if (mu) KMX_HIP(hipMemcpyAsync(d.mu_in, mu, (size_t)g.nb * sizeof(double), hipMemcpyHostToDevice, s));
+  KMX_HIP(hipMemcpyAsync(d.r.get(), R, 9 * n * sizeof(double), hipMemcpyHostToDevice, s));
+  KMX_HIP(hipMemcpyAsync(d.q.get(), t, 3 * n * sizeof(double), hipMemcpyHostToDevice, s));
+  if (mu) KMX_HIP(hipMemcpyAsync(d.rob.mu_in.get(), mu, (size_t)g.nb * sizeof(double), hipMemcpyHostToDevice, s));
   if (d.n_tiles > 0)
-    hipLaunchKernelGGL((k_ch_gnc<2>), dim3(d.n_tiles), dim3(CH_TILE), 0, s, ChTiles{d.tile_p0, d.tile_p1, d.tile_block},
-                       ch_gnc_args(d), d.r, d.q, nullptr, mu ? d.mu_in : nullptr, c * c, nullptr, d.gwk, d.gwt, nullptr,
-                       nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL((k_ch_gnc<2>), dim3(d.n_tiles), dim3(CH_TILE), 0, s, ch_tiles(d), ch_gnc_args(d),
+                       d.r.get(), d.q.get(), nullptr, mu ? d.rob.mu_in.get() : nullptr, c * c, nullptr, d.rob.gwk.get(),
+                       d.rob.gwt.get(), nullptr, nullptr, nullptr, nullptr);
   KMX_HIP(hipGetLastError());
   std::vector<double> rec(nrec);
-  if (nrec) KMX_HIP(hipMemcpyAsync(rec.data(), d.gwk, nrec * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (nrec) KMX_HIP(hipMemcpyAsync(rec.data(), d.rob.gwk.get(), nrec * sizeof(double), hipMemcpyDeviceToHost, s));
   KMX_HIP(hipStreamSynchronize(s));
   ch_records_to_edges(g, rec, r2_out);
   if (g_out) {
-    if (nrec) KMX_HIP(hipMemcpyAsync(rec.data(), d.gwt, nrec * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (nrec) KMX_HIP(hipMemcpyAsync(rec.data(), d.rob.gwt.get(), nrec * sizeof(double), hipMemcpyDeviceToHost, s));
     KMX_HIP(hipStreamSynchronize(s));
     ch_records_to_edges(g, rec, g_out);
   }
@@ -1193,11 +1137,11 @@ extern "C" int kmx_chordal_solve_robust(kmx_chordal* h, const kmx_chordal_params
       for (int k = 0; k < 3; ++k) xt[3 * a + k] = 0.0;
     }
   KMX_HIP(hipSetDevice(h->device));
-  if (int rc = ch_robust_alloc(h)) return rc;
+  if (int rc = ch_robust_reserve(h)) return rc;
   if (int rc = ch_robust_upload_edges(h, fixed)) return rc;
   ChDev& d = h->dev;
   hipStream_t s = h->stream;
-  const ChTiles T{d.tile_p0, d.tile_p1, d.tile_block};
+  const ChTiles T = ch_tiles(d);
   const ChGnc G = ch_gnc_args(d);
   const dim3 gt(d.n_tiles), gb(g.nb), wave(CH_TILE), gp((g.n + 255) / 256), bp(256);
   const double c2 = q.barc * q.barc;
@@ -1210,27 +1154,31 @@ extern "C" int kmx_chordal_solve_robust(kmx_chordal* h, const kmx_chordal_params
   KMX_HIP(hipEventRecord(e_start, s));
   // the start vectors; the first solve's weights are the handle's, copied: the
   // handle's own wk / wt / D are never written here
-  KMX_HIP(hipMemcpyAsync(d.xu, xr.data(), 9 * n * sizeof(double), hipMemcpyHostToDevice, s));
-  KMX_HIP(hipMemcpyAsync(d.xr, d.xu, 9 * n * sizeof(double), hipMemcpyDeviceToDevice, s));
-  KMX_HIP(hipMemcpyAsync(d.xt, xt.data(), 3 * n * sizeof(double), hipMemcpyHostToDevice, s));
+  KMX_HIP(hipMemcpyAsync(d.rob.xu.get(), xr.data(), 9 * n * sizeof(double), hipMemcpyHostToDevice, s));
+  KMX_HIP(hipMemcpyAsync(d.xr.get(), d.rob.xu.get(), 9 * n * sizeof(double), hipMemcpyDeviceToDevice, s));
+  KMX_HIP(hipMemcpyAsync(d.xt.get(), xt.data(), 3 * n * sizeof(double), hipMemcpyHostToDevice, s));
   if (nrec) {
-    KMX_HIP(hipMemcpyAsync(d.gwk, d.wk, nrec * sizeof(double), hipMemcpyDeviceToDevice, s));
-    KMX_HIP(hipMemcpyAsync(d.gwt, d.wt, nrec * sizeof(double), hipMemcpyDeviceToDevice, s));
+    KMX_HIP(hipMemcpyAsync(d.rob.gwk.get(), d.wk.get(), nrec * sizeof(double), hipMemcpyDeviceToDevice, s));
+    KMX_HIP(hipMemcpyAsync(d.rob.gwt.get(), d.wt.get(), nrec * sizeof(double), hipMemcpyDeviceToDevice, s));
   }
-  KMX_HIP(hipMemcpyAsync(d.gDk, d.Dk, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-  KMX_HIP(hipMemcpyAsync(d.gDt, d.Dt, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-  KMX_HIP(hipMemsetAsync(d.rb, 0, (size_t)g.nb * sizeof(ChRob), s));
-  KMX_HIP(hipMemsetAsync(d.rctl, 0, sizeof(int), s));
+  KMX_HIP(hipMemcpyAsync(d.rob.gDk.get(), d.Dk.get(), n * sizeof(double), hipMemcpyDeviceToDevice, s));
+  KMX_HIP(hipMemcpyAsync(d.rob.gDt.get(), d.Dt.get(), n * sizeof(double), hipMemcpyDeviceToDevice, s));
+  KMX_HIP(hipMemsetAsync(d.rob.rb.get(), 0, (size_t)g.nb * sizeof(ChRob), s));
+  KMX_HIP(hipMemsetAsync(d.rob.rctl.get(), 0, sizeof(int), s));
   int solves = 0, running = 0;
   for (int k = 0; k <= q.max_updates; ++k) {
     // 1-4: the rotation stage, the projection, the translations' right-hand side, the translation stage
-    int rc = ch_stage<3>(h, 0, d.xu, nullptr, rtol, max_it, check_every, d.gwk, d.gDk, d.rb);
+    int rc = ch_stage<3>(h, 0, d.rob.xu.get(), nullptr, rtol, max_it, check_every, d.rob.gwk.get(), d.rob.gDk.get(),
+                         d.rob.rb.get());
     if (rc) return rc;
     if (d.n_tiles > 0)
-      hipLaunchKernelGGL(k_ch_project_tiles, gt, wave, 0, s, T, d.rb, d.is_free, d.xu, d.xr, q.start_projected ? 1 : 0);
-    hipLaunchKernelGGL(k_ch_rhs_t, gp, bp, 0, s, g.n, d.inc_ptr, d.inc_other, d.gwt, d.inc_t, d.is_free, d.xr, d.bt);
+      hipLaunchKernelGGL(k_ch_project_tiles, gt, wave, 0, s, T, d.rob.rb.get(), d.is_free.get(), d.rob.xu.get(),
+                         d.xr.get(), q.start_projected ? 1 : 0);
+    hipLaunchKernelGGL(k_ch_rhs_t, gp, bp, 0, s, g.n, d.inc_ptr.get(), d.inc_other.get(), d.rob.gwt.get(),
+                       d.inc_t.get(), d.is_free.get(), d.xr.get(), d.bt.get());
     KMX_HIP(hipGetLastError());
-    rc = ch_stage<1>(h, 1, d.xt, d.bt, rtol, max_it, check_every, d.gwt, d.gDt, d.rb);
+    rc = ch_stage<1>(h, 1, d.xt.get(), d.bt.get(), rtol, max_it, check_every, d.rob.gwt.get(), d.rob.gDt.get(),
+                     d.rob.rb.get());
     if (rc) return rc;
     ++solves;
     if (k == 0) KMX_HIP(hipEventRecord(e_first, s));
@@ -1241,32 +1189,34 @@ extern "C" int kmx_chordal_solve_robust(kmx_chordal* h, const kmx_chordal_params
     KMX_HIP(hipEventRecord(e0, s));
     if (k == 0) {
       if (d.n_tiles > 0)
-        hipLaunchKernelGGL((k_ch_gnc<0>), gt, wave, 0, s, T, G, d.xr, d.xt, d.rb, nullptr, c2, d.rg, nullptr, nullptr,
-                           nullptr, nullptr, d.pmax, d.pcnt);
-      hipLaunchKernelGGL((k_ch_decide<true>), gb, wave, 0, s, d.tile_ptr, d.pmax, d.pcnt, d.rb, d.sc, g.nb, d.rctl, c2,
-                         q.mu_init, q.mu_step, 0, 0);
+        hipLaunchKernelGGL((k_ch_gnc<0>), gt, wave, 0, s, T, G, d.xr.get(), d.xt.get(), d.rob.rb.get(), nullptr, c2,
+                           d.rob.rg.get(), nullptr, nullptr, nullptr, nullptr, d.rob.pmax.get(), d.rob.pcnt.get());
+      hipLaunchKernelGGL((k_ch_decide<true>), gb, wave, 0, s, d.tile_ptr.get(), d.rob.pmax.get(), d.rob.pcnt.get(),
+                         d.rob.rb.get(), d.sc.get(), g.nb, d.rob.rctl.get(), c2, q.mu_init, q.mu_step, 0, 0);
     }
     const int last = k == q.max_updates;
     if (!last && d.n_tiles > 0)
-      hipLaunchKernelGGL((k_ch_gnc<1>), gt, wave, 0, s, T, G, d.xr, d.xt, d.rb, nullptr, c2, d.rg, d.gwk, d.gwt, d.gDk,
-                         d.gDt, d.pmax, d.pcnt);
-    hipLaunchKernelGGL((k_ch_decide<false>), gb, wave, 0, s, d.tile_ptr, d.pmax, d.pcnt, d.rb, d.sc, g.nb, d.rctl, c2,
-                       q.mu_init, q.mu_step, k > 0, last);
+      hipLaunchKernelGGL((k_ch_gnc<1>), gt, wave, 0, s, T, G, d.xr.get(), d.xt.get(), d.rob.rb.get(), nullptr, c2,
+                         d.rob.rg.get(), d.rob.gwk.get(), d.rob.gwt.get(), d.rob.gDk.get(), d.rob.gDt.get(),
+                         d.rob.pmax.get(), d.rob.pcnt.get());
+    hipLaunchKernelGGL((k_ch_decide<false>), gb, wave, 0, s, d.tile_ptr.get(), d.rob.pmax.get(), d.rob.pcnt.get(),
+                       d.rob.rb.get(), d.sc.get(), g.nb, d.rob.rctl.get(), c2, q.mu_init, q.mu_step, k > 0, last);
     KMX_HIP(hipGetLastError());
     KMX_HIP(hipEventRecord(e1, s));
     // 6: the one read of the loop
-    KMX_HIP(hipMemcpyAsync(&running, d.rctl, sizeof(int), hipMemcpyDeviceToHost, s));
+    KMX_HIP(hipMemcpyAsync(&running, d.rob.rctl.get(), sizeof(int), hipMemcpyDeviceToHost, s));
     KMX_HIP(hipStreamSynchronize(s));
     if (running == 0) break;
   }
   std::vector<ChScal> sc((size_t)6 * g.nb);
   std::vector<ChRob> rb((size_t)g.nb);
   std::vector<double> rec(g_out ? nrec : 0);
-  KMX_HIP(hipMemcpyAsync(R_out, d.xr, 9 * n * sizeof(double), hipMemcpyDeviceToHost, s));
-  KMX_HIP(hipMemcpyAsync(t_out, d.xt, 3 * n * sizeof(double), hipMemcpyDeviceToHost, s));
-  KMX_HIP(hipMemcpyAsync(sc.data(), d.sc, sc.size() * sizeof(ChScal), hipMemcpyDeviceToHost, s));
-  KMX_HIP(hipMemcpyAsync(rb.data(), d.rb, rb.size() * sizeof(ChRob), hipMemcpyDeviceToHost, s));
-  if (g_out && nrec) KMX_HIP(hipMemcpyAsync(rec.data(), d.rg, nrec * sizeof(double), hipMemcpyDeviceToHost, s));
+  KMX_HIP(hipMemcpyAsync(R_out, d.xr.get(), 9 * n * sizeof(double), hipMemcpyDeviceToHost, s));
+  KMX_HIP(hipMemcpyAsync(t_out, d.xt.get(), 3 * n * sizeof(double), hipMemcpyDeviceToHost, s));
+  KMX_HIP(hipMemcpyAsync(sc.data(), d.sc.get(), sc.size() * sizeof(ChScal), hipMemcpyDeviceToHost, s));
+  KMX_HIP(hipMemcpyAsync(rb.data(), d.rob.rb.get(), rb.size() * sizeof(ChRob), hipMemcpyDeviceToHost, s));
+  if (g_out && nrec) KMX_HIP(hipMemcpyAsync(rec.data(), d.rob.rg.get(), nrec * sizeof(double), hipMemcpyDeviceToHost,
+                                            s));
   KMX_HIP(hipEventRecord(e_end, s));
   KMX_HIP(hipStreamSynchronize(s));
   if (g_out) ch_records_to_edges(g, rec, g_out);

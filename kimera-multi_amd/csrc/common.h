@@ -1,10 +1,14 @@
-// common.h — internal helpers shared by the dpgo and LCD halves of libkmx.
+// common.h — internal helpers shared by the dpgo and LCD halves of libkmx:
+// the error channel, the views one module gives another, and what every
+// handle is made of (the owning device buffer over HIP, the stream core, the
+// owning event) with the one wave reduction the kernels share.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <string>
 
+#include "devbuf.h"
 #include "kmx_abi.h"
 
 namespace kmx {
@@ -63,3 +67,129 @@ int voc_batch_view(kmx_voc* h, VocBatchView* out);  // voc.hip
   catch (const std::exception& ex) {                                    \
     return kmx::fail(KMX_EINVAL, ex.what());                            \
   }
+
+namespace kmx {
+// devbuf.h's backend over the HIP runtime: a failed allocation is KMX_ENOMEM, a failed copy KMX_EHIP.
+struct HipMem {
+  using stream_t = hipStream_t;
+  static int alloc(void** p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) return 0;
+    *p = nullptr;
+    return fail(KMX_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+  }
+  static void free(void* p) { (void)hipFree(p); }
+  static int copy(void* dst, const void* src, size_t bytes, const hipStream_t* s) {
+    if (s) KMX_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, *s));
+    else KMX_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToDevice));
+    return 0;
+  }
+  static int upload(void* dst, const void* src, size_t bytes, hipStream_t s) {
+    KMX_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+    return 0;
+  }
+};
+template <class T>
+using DevBuf = BasicDevBuf<T, HipMem>;
+
+// Pinned host memory under the same owner (it is only allocated and freed).
+struct HipPinned {
+  using stream_t = hipStream_t;
+  static int alloc(void** p, size_t bytes) {
+    if (hipHostMalloc(p, bytes, hipHostMallocDefault) == hipSuccess) return 0;
+    *p = nullptr;
+    return fail(KMX_ENOMEM, "hipHostMalloc failed");
+  }
+  static void free(void* p) { (void)hipHostFree(p); }
+};
+template <class T>
+using PinnedBuf = BasicDevBuf<T, HipPinned>;
+
+// What every handle begins with. A handle derives from it, so the stream is
+// made before the handle's buffers and events and destroyed after them.
+struct StreamCore {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  StreamCore() = default;
+  StreamCore(const StreamCore&) = delete;
+  StreamCore& operator=(const StreamCore&) = delete;
+  ~StreamCore() { close(); }
+
+  // kmx_*_create: checks the ordinal, makes the device current, creates the handle's own non-blocking stream.
+  int open(int dev) {
+    int ndev = 0;
+    KMX_HIP(hipGetDeviceCount(&ndev));
+    KMX_CHECK(dev >= 0 && dev < ndev, KMX_EINVAL, "bad HIP device ordinal");
+    KMX_HIP(hipSetDevice(dev));
+    device = dev;
+    KMX_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess, KMX_EHIP,
+              "hipStreamCreate failed");
+    own_stream = true;
+    return 0;
+  }
+  // kmx_*_set_stream: a stream of the handle's own is synchronised and
+  // destroyed, a borrowed one synchronised only if sync_borrowed; then s is held.
+  int adopt(void* s, bool sync_borrowed) {
+    KMX_HIP(hipSetDevice(device));
+    if (stream && (own_stream || sync_borrowed)) KMX_HIP(hipStreamSynchronize(stream));
+    if (stream && own_stream) KMX_HIP(hipStreamDestroy(stream));
+    own_stream = false;
+    stream = reinterpret_cast<hipStream_t>(s);
+    return 0;
+  }
+  // Destroys a stream of the handle's own. Whoever deletes the handle has
+  // synchronised first (destroy, below); a create that fails has enqueued nothing.
+  void close() {
+    if (stream && own_stream) (void)hipStreamDestroy(stream);
+    stream = nullptr;
+    own_stream = false;
+  }
+};
+
+// kmx_*_destroy: the device current, the stream's work done, then the members free what they hold.
+template <class H>
+int destroy(H* h) {
+  if (!h) return KMX_OK;
+  (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  delete h;
+  return KMX_OK;
+}
+
+// One owned event (null until create); arrays and vectors of it replace the create / destroy loops.
+class Event {
+ public:
+  Event() = default;
+  Event(Event&& o) noexcept : e_(o.e_) { o.e_ = nullptr; }
+  Event& operator=(Event&&) = delete;
+  ~Event() {
+    if (e_) (void)hipEventDestroy(e_);
+  }
+  int create(unsigned flags = hipEventDefault) {
+    if (hipEventCreateWithFlags(&e_, flags) == hipSuccess) return 0;
+    e_ = nullptr;
+    return fail(KMX_EHIP, "hipEventCreate failed");
+  }
+  operator hipEvent_t() const { return e_; }
+
+ private:
+  hipEvent_t e_ = nullptr;
+};
+template <size_t N>
+int create_events(Event (&ev)[N]) {
+  for (Event& e : ev)
+    if (int rc = e.create()) return rc;
+  return 0;
+}
+
+#ifdef __HIPCC__
+// The 64-lane sum in a fixed tree; lane 0 holds it.
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+#endif
+}  // namespace kmx

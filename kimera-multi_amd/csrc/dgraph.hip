@@ -23,6 +23,7 @@
 // that the host reads once per outer iteration.
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <vector>
 
 #include "common.h"
@@ -38,11 +39,7 @@ struct DgState {
   int accepted, stop, iter, n_accepted;
 };
 
-__device__ __forceinline__ double wave_sum(double v) {  // lane 0 holds the sum; fixed tree
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
+using kmx::wave_sum;  // lane 0 holds the sum; fixed tree
 
 __host__ __device__ constexpr int tri(int i, int j) { return i * 6 - i * (i - 1) / 2 + (j - i); }  // i <= j
 
@@ -534,53 +531,25 @@ __global__ void k_dg_decide(DgState* __restrict__ st, double factor, double lmin
   st->stop = stop;
 }
 
-struct DgDev {
-  int *ptr = nullptr;
-  uint32_t* other = nullptr;
-  double *rec_w = nullptr, *rec_d = nullptr, *rec_a = nullptr;
-  double *Rrest = nullptr, *g = nullptr, *R = nullptr, *t = nullptr, *Rt = nullptr, *tt = nullptr;
-  uint8_t* mode = nullptr;
-  double *Rhat = nullptr, *that = nullptr, *kappa = nullptr, *tau = nullptr;
-  double *b = nullptr, *blk = nullptr, *Minv = nullptr, *x = nullptr, *r = nullptr, *z = nullptr, *p = nullptr,
-         *q = nullptr, *part = nullptr;
-  DgState* st = nullptr;
+struct DgDev {  // what set_graph puts on the device; replaced as a whole
+  kmx::DevBuf<int> ptr;
+  kmx::DevBuf<uint32_t> other;
+  kmx::DevBuf<double> rec_w, rec_d, rec_a;
+  kmx::DevBuf<double> Rrest, g, R, t, Rt, tt;
+  kmx::DevBuf<uint8_t> mode;
+  kmx::DevBuf<double> Rhat, that, kappa, tau;
+  kmx::DevBuf<double> b, blk, Minv, x, r, z, p, q, part;
+  kmx::DevBuf<DgState> st;
 };
-
-void dg_free(DgDev& d) {
-  void* ptrs[] = {d.ptr, d.other, d.rec_w, d.rec_d, d.rec_a, d.Rrest, d.g,    d.R, d.t, d.Rt, d.tt, d.mode, d.Rhat,
-                  d.that, d.kappa, d.tau,  d.b,     d.blk,   d.Minv,  d.x,    d.r, d.z, d.p,  d.q,  d.part, d.st};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  d = DgDev();
-}
-
-template <class T>
-int dg_alloc(T** p, size_t count) {
-  if (hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
-    *p = nullptr;
-    return kmx::fail(KMX_ENOMEM, "hipMalloc failed");
-  }
-  return KMX_OK;
-}
-
-template <class T>
-int dg_put(T** p, const T* v, size_t count, hipStream_t s) {
-  if (int rc = dg_alloc(p, count)) return rc;
-  if (count) KMX_HIP(hipMemcpyAsync(*p, v, count * sizeof(T), hipMemcpyHostToDevice, s));
-  return KMX_OK;
-}
 
 }  // namespace
 
-struct kmx_dgraph {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+struct kmx_dgraph : kmx::StreamCore {
   bool have_graph = false, have_priors = false;
   kmx::DgGraph G;
   kmx::DgPriors P;
   DgDev dev;
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  kmx::Event ev[6];
   double ms[5] = {0, 0, 0, 0, 0};  // [4]: the product kernel of the last J^T J evaluation
   std::vector<kmx_dgraph_log_entry> log;
 };
@@ -593,11 +562,11 @@ inline dim3 dg_grid(int64_t n, int block) { return dim3((unsigned)((n + block - 
 int dg_linearize(kmx_dgraph* h, int store_cost) {
   DgDev& d = h->dev;
   const int n = h->G.n;
-  const DgRec I{d.ptr, d.other, d.rec_w, d.rec_d, d.rec_a};
-  const DgPrior P{d.mode, d.Rhat, d.that, d.kappa, d.tau};
-  hipLaunchKernelGGL((k_dg_linearize<true>), dim3(h->G.n_tiles), dim3(DG_TILE), 0, h->stream, n, I, P, d.R, d.t, d.b,
-                     d.blk, d.part);
-  hipLaunchKernelGGL((k_dg_reduce<3>), dim3(1), dim3(64), 0, h->stream, d.part, h->G.n_tiles, d.st, 0.0, 0,
+  const DgRec I{d.ptr.get(), d.other.get(), d.rec_w.get(), d.rec_d.get(), d.rec_a.get()};
+  const DgPrior P{d.mode.get(), d.Rhat.get(), d.that.get(), d.kappa.get(), d.tau.get()};
+  hipLaunchKernelGGL((k_dg_linearize<true>), dim3(h->G.n_tiles), dim3(DG_TILE), 0, h->stream, n, I, P, d.R.get(),
+                     d.t.get(), d.b.get(), d.blk.get(), d.part.get());
+  hipLaunchKernelGGL((k_dg_reduce<3>), dim3(1), dim3(64), 0, h->stream, d.part.get(), h->G.n_tiles, d.st.get(), 0.0, 0,
                      store_cost);
   KMX_HIP(hipGetLastError());
   return KMX_OK;
@@ -605,14 +574,14 @@ int dg_linearize(kmx_dgraph* h, int store_cost) {
 
 int dg_pin(kmx_dgraph* h) {
   DgDev& d = h->dev;
-  hipLaunchKernelGGL(k_dg_pin, dg_grid(h->G.n, 256), dim3(256), 0, h->stream, h->G.n, d.mode, d.Rhat, d.that, d.R,
-                     d.t);
+  hipLaunchKernelGGL(k_dg_pin, dg_grid(h->G.n, 256), dim3(256), 0, h->stream, h->G.n, d.mode.get(), d.Rhat.get(),
+                     d.that.get(), d.R.get(), d.t.get());
   KMX_HIP(hipGetLastError());
   return KMX_OK;
 }
 
 int dg_read_state(kmx_dgraph* h, DgState* s) {
-  KMX_HIP(hipMemcpyAsync(s, h->dev.st, sizeof(DgState), hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(s, h->dev.st.get(), sizeof(DgState), hipMemcpyDeviceToHost, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   return KMX_OK;
 }
@@ -622,47 +591,21 @@ int dg_read_state(kmx_dgraph* h, DgState* s) {
 extern "C" int kmx_dgraph_create(int device, kmx_dgraph** out) {
   KMX_GUARD_BEGIN
   KMX_CHECK(out, KMX_EINVAL, "null argument");
-  int ndev = 0;
-  KMX_HIP(hipGetDeviceCount(&ndev));
-  KMX_CHECK(device >= 0 && device < ndev, KMX_EINVAL, "bad HIP device ordinal");
-  KMX_HIP(hipSetDevice(device));
-  kmx_dgraph* h = new kmx_dgraph();
-  h->device = device;
-  bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
-  h->own_stream = ok;
-  for (int k = 0; ok && k < 6; ++k) ok = hipEventCreate(&h->ev[k]) == hipSuccess;
-  if (!ok) {
-    for (hipEvent_t e : h->ev)
-      if (e) (void)hipEventDestroy(e);
-    if (h->own_stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-    return kmx::fail(KMX_EHIP, "hipStreamCreate / hipEventCreate failed");
-  }
-  *out = h;
+  std::unique_ptr<kmx_dgraph> h(new kmx_dgraph());
+  int rc;
+  if ((rc = h->open(device)) || (rc = kmx::create_events(h->ev))) return rc;
+  *out = h.release();
   return KMX_OK;
   KMX_GUARD_END
 }
 
 extern "C" int kmx_dgraph_destroy(kmx_dgraph* h) {
-  if (!h) return KMX_OK;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  dg_free(h->dev);
-  for (hipEvent_t e : h->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-  return KMX_OK;
+  return kmx::destroy(h);
 }
 
 extern "C" int kmx_dgraph_set_stream(kmx_dgraph* h, void* s) {
   KMX_CHECK(h, KMX_EINVAL, "null handle");
-  KMX_HIP(hipSetDevice(h->device));
-  if (h->stream) KMX_HIP(hipStreamSynchronize(h->stream));
-  if (h->own_stream && h->stream) KMX_HIP(hipStreamDestroy(h->stream));
-  h->own_stream = false;
-  h->stream = reinterpret_cast<hipStream_t>(s);
-  return KMX_OK;
+  return h->adopt(s, true);
 }
 
 extern "C" int kmx_dgraph_set_graph(kmx_dgraph* h, int32_t n, const double* Rrest, const double* g, int64_t m,
@@ -671,43 +614,39 @@ extern "C" int kmx_dgraph_set_graph(kmx_dgraph* h, int32_t n, const double* Rres
   KMX_CHECK(h, KMX_EINVAL, "null handle");
   kmx::DgGraph G;
   std::string err;
-  if (int rc = kmx::dg_build(n, Rrest, g, m, src, dst, w, &G, &err)) return kmx::fail(rc, "kmx_dgraph_set_graph: " + err);
+  if (int rc = kmx::dg_build(n, Rrest, g, m, src, dst, w, &G, &err)) return kmx::fail(rc,
+                                                                                      "kmx_dgraph_set_graph: " + err);
   std::vector<double> rec_w;
   kmx::dg_record_weights(G, G.w.data(), &rec_w);
   KMX_HIP(hipSetDevice(h->device));
   KMX_HIP(hipStreamSynchronize(h->stream));
   hipStream_t s = h->stream;
+  // built aside, committed by the move below: an error or an exception on its way to KMX_GUARD_END frees only d
   DgDev d;
   const size_t nn = (size_t)n, nrec = G.inc_other.size(), nt = (size_t)G.n_tiles;
   int rc = KMX_OK;
-  if ((rc = dg_put(&d.ptr, G.inc_ptr.data(), G.inc_ptr.size(), s)) ||
-      (rc = dg_put(&d.other, G.inc_other.data(), nrec, s)) || (rc = dg_put(&d.rec_w, rec_w.data(), nrec, s)) ||
-      (rc = dg_alloc(&d.rec_d, 3 * nrec)) || (rc = dg_alloc(&d.rec_a, 3 * nrec)) ||
-      (rc = dg_put(&d.Rrest, Rrest, 9 * nn, s)) || (rc = dg_put(&d.g, g, 3 * nn, s)) ||
-      (rc = dg_put(&d.R, Rrest, 9 * nn, s)) || (rc = dg_put(&d.t, g, 3 * nn, s)) || (rc = dg_alloc(&d.Rt, 9 * nn)) ||
-      (rc = dg_alloc(&d.tt, 3 * nn)) || (rc = dg_alloc(&d.mode, nn)) || (rc = dg_alloc(&d.Rhat, 9 * nn)) ||
-      (rc = dg_alloc(&d.that, 3 * nn)) || (rc = dg_alloc(&d.kappa, nn)) || (rc = dg_alloc(&d.tau, nn)) ||
-      (rc = dg_alloc(&d.b, 6 * nn)) || (rc = dg_alloc(&d.blk, 21 * nn)) || (rc = dg_alloc(&d.Minv, 21 * nn)) ||
-      (rc = dg_alloc(&d.x, 6 * nn)) || (rc = dg_alloc(&d.r, 6 * nn)) || (rc = dg_alloc(&d.z, 6 * nn)) ||
-      (rc = dg_alloc(&d.p, 6 * nn)) || (rc = dg_alloc(&d.q, 6 * nn)) || (rc = dg_alloc(&d.part, 2 * nt)) ||
-      (rc = dg_alloc(&d.st, 1))) {
-    (void)hipStreamSynchronize(s);
-    dg_free(d);
+  if ((rc = d.ptr.put(G.inc_ptr, s)) || (rc = d.other.put(G.inc_other, s)) ||
+      (rc = d.rec_w.put(rec_w, s)) || (rc = d.rec_d.alloc(3 * nrec)) || (rc = d.rec_a.alloc(3 * nrec)) ||
+      (rc = d.Rrest.put(Rrest, 9 * nn, s)) || (rc = d.g.put(g, 3 * nn, s)) || (rc = d.R.put(Rrest, 9 * nn, s)) ||
+      (rc = d.t.put(g, 3 * nn, s)) || (rc = d.Rt.alloc(9 * nn)) || (rc = d.tt.alloc(3 * nn)) ||
+      (rc = d.mode.alloc(nn)) || (rc = d.Rhat.alloc(9 * nn)) || (rc = d.that.alloc(3 * nn)) ||
+      (rc = d.kappa.alloc(nn)) || (rc = d.tau.alloc(nn)) || (rc = d.b.alloc(6 * nn)) || (rc = d.blk.alloc(21 * nn)) ||
+      (rc = d.Minv.alloc(21 * nn)) || (rc = d.x.alloc(6 * nn)) || (rc = d.r.alloc(6 * nn)) ||
+      (rc = d.z.alloc(6 * nn)) || (rc = d.p.alloc(6 * nn)) || (rc = d.q.alloc(6 * nn)) ||
+      (rc = d.part.alloc(2 * nt)) || (rc = d.st.alloc(1))) {
+    (void)hipStreamSynchronize(s);  // the uploads read the caller's arrays
     return rc;
   }
   hipError_t e = hipSuccess;
   if (n > 0) {
-    hipLaunchKernelGGL(k_dg_edges, dg_grid(n, 256), dim3(256), 0, s, n, d.ptr, d.other, d.Rrest, d.g, d.rec_d);
+    hipLaunchKernelGGL(k_dg_edges, dg_grid(n, 256), dim3(256), 0, s, n, d.ptr.get(), d.other.get(), d.Rrest.get(),
+                       d.g.get(), d.rec_d.get());
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemsetAsync(d.mode, 0, std::max<size_t>(nn, 1), s);
+  if (e == hipSuccess) e = hipMemsetAsync(d.mode.get(), 0, std::max<size_t>(nn, 1), s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);  // the caller's arrays and rec_w are free again
-  if (e != hipSuccess) {
-    dg_free(d);
-    return kmx::fail(KMX_EHIP, std::string("kmx_dgraph_set_graph: ") + hipGetErrorString(e));
-  }
-  dg_free(h->dev);
-  h->dev = d;
+  if (e != hipSuccess) return kmx::fail(KMX_EHIP, std::string("kmx_dgraph_set_graph: ") + hipGetErrorString(e));
+  h->dev = std::move(d);
   h->G = std::move(G);
   h->P = kmx::DgPriors();
   h->have_graph = true;
@@ -732,7 +671,7 @@ extern "C" int kmx_dgraph_set_weights(kmx_dgraph* h, const double* w) {
   kmx::dg_record_weights(G, w, &rec_w);
   KMX_HIP(hipSetDevice(h->device));
   if (!rec_w.empty())
-    KMX_HIP(hipMemcpyAsync(h->dev.rec_w, rec_w.data(), rec_w.size() * sizeof(double), hipMemcpyHostToDevice,
+    KMX_HIP(hipMemcpyAsync(h->dev.rec_w.get(), rec_w.data(), rec_w.size() * sizeof(double), hipMemcpyHostToDevice,
                            h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   if (w)
@@ -760,11 +699,11 @@ extern "C" int kmx_dgraph_set_priors(kmx_dgraph* h, const uint8_t* mode, const d
   hipStream_t s = h->stream;
   DgDev& d = h->dev;
   if (nn) {
-    KMX_HIP(hipMemcpyAsync(d.mode, P.mode.data(), nn, hipMemcpyHostToDevice, s));
-    KMX_HIP(hipMemcpyAsync(d.Rhat, P.Rhat.data(), 9 * nn * sizeof(double), hipMemcpyHostToDevice, s));
-    KMX_HIP(hipMemcpyAsync(d.that, P.that.data(), 3 * nn * sizeof(double), hipMemcpyHostToDevice, s));
-    KMX_HIP(hipMemcpyAsync(d.kappa, P.kappa.data(), nn * sizeof(double), hipMemcpyHostToDevice, s));
-    KMX_HIP(hipMemcpyAsync(d.tau, P.tau.data(), nn * sizeof(double), hipMemcpyHostToDevice, s));
+    KMX_HIP(hipMemcpyAsync(d.mode.get(), P.mode.data(), nn, hipMemcpyHostToDevice, s));
+    KMX_HIP(hipMemcpyAsync(d.Rhat.get(), P.Rhat.data(), 9 * nn * sizeof(double), hipMemcpyHostToDevice, s));
+    KMX_HIP(hipMemcpyAsync(d.that.get(), P.that.data(), 3 * nn * sizeof(double), hipMemcpyHostToDevice, s));
+    KMX_HIP(hipMemcpyAsync(d.kappa.get(), P.kappa.data(), nn * sizeof(double), hipMemcpyHostToDevice, s));
+    KMX_HIP(hipMemcpyAsync(d.tau.get(), P.tau.data(), nn * sizeof(double), hipMemcpyHostToDevice, s));
   }
   KMX_HIP(hipStreamSynchronize(s));
   h->P = std::move(P);
@@ -784,8 +723,8 @@ extern "C" int kmx_dgraph_set_poses(kmx_dgraph* h, const double* R, const double
   KMX_HIP(hipSetDevice(h->device));
   if (nn) {
     const hipMemcpyKind kind = R ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    KMX_HIP(hipMemcpyAsync(h->dev.R, R ? R : h->dev.Rrest, 9 * nn * sizeof(double), kind, h->stream));
-    KMX_HIP(hipMemcpyAsync(h->dev.t, t ? t : h->dev.g, 3 * nn * sizeof(double), kind, h->stream));
+    KMX_HIP(hipMemcpyAsync(h->dev.R.get(), R ? R : h->dev.Rrest.get(), 9 * nn * sizeof(double), kind, h->stream));
+    KMX_HIP(hipMemcpyAsync(h->dev.t.get(), t ? t : h->dev.g.get(), 3 * nn * sizeof(double), kind, h->stream));
   }
   KMX_HIP(hipStreamSynchronize(h->stream));
   return KMX_OK;
@@ -800,8 +739,8 @@ extern "C" int kmx_dgraph_get_poses(kmx_dgraph* h, double* R, double* t) {
   KMX_CHECK(nn == 0 || (R && t), KMX_EINVAL, "null output");
   KMX_HIP(hipSetDevice(h->device));
   if (nn) {
-    KMX_HIP(hipMemcpyAsync(R, h->dev.R, 9 * nn * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    KMX_HIP(hipMemcpyAsync(t, h->dev.t, 3 * nn * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    KMX_HIP(hipMemcpyAsync(R, h->dev.R.get(), 9 * nn * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    KMX_HIP(hipMemcpyAsync(t, h->dev.t.get(), 3 * nn * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   }
   KMX_HIP(hipStreamSynchronize(h->stream));
   return KMX_OK;
@@ -834,19 +773,20 @@ extern "C" int kmx_dgraph_eval(kmx_dgraph* h, int32_t what, const double* v, dou
     return KMX_OK;
   }
   if (what == KMX_DGRAPH_EVAL_GRAD) {
-    KMX_HIP(hipMemcpyAsync(out, d.b, 6 * nn * sizeof(double), hipMemcpyDeviceToHost, s));
+    KMX_HIP(hipMemcpyAsync(out, d.b.get(), 6 * nn * sizeof(double), hipMemcpyDeviceToHost, s));
   } else if (what == KMX_DGRAPH_EVAL_BLOCKS) {
-    KMX_HIP(hipMemcpyAsync(out, d.blk, 21 * nn * sizeof(double), hipMemcpyDeviceToHost, s));
+    KMX_HIP(hipMemcpyAsync(out, d.blk.get(), 21 * nn * sizeof(double), hipMemcpyDeviceToHost, s));
   } else {
-    KMX_HIP(hipMemcpyAsync(d.p, v, 6 * nn * sizeof(double), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_dg_mask, dg_grid(n, 256), dim3(256), 0, s, n, d.mode, d.p);
-    const DgRec I{d.ptr, d.other, d.rec_w, d.rec_d, d.rec_a};
-    const DgPrior P{d.mode, d.Rhat, d.that, d.kappa, d.tau};
+    KMX_HIP(hipMemcpyAsync(d.p.get(), v, 6 * nn * sizeof(double), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_dg_mask, dg_grid(n, 256), dim3(256), 0, s, n, d.mode.get(), d.p.get());
+    const DgRec I{d.ptr.get(), d.other.get(), d.rec_w.get(), d.rec_d.get(), d.rec_a.get()};
+    const DgPrior P{d.mode.get(), d.Rhat.get(), d.that.get(), d.kappa.get(), d.tau.get()};
     KMX_HIP(hipEventRecord(h->ev[0], s));
-    hipLaunchKernelGGL((k_dg_apply<true>), dim3(h->G.n_tiles), dim3(DG_TILE), 0, s, n, I, P, d.p, d.q, d.st, d.part);
+    hipLaunchKernelGGL((k_dg_apply<true>), dim3(h->G.n_tiles), dim3(DG_TILE), 0, s, n, I, P, d.p.get(), d.q.get(),
+                       d.st.get(), d.part.get());
     KMX_HIP(hipGetLastError());
     KMX_HIP(hipEventRecord(h->ev[1], s));
-    KMX_HIP(hipMemcpyAsync(out, d.q, 6 * nn * sizeof(double), hipMemcpyDeviceToHost, s));
+    KMX_HIP(hipMemcpyAsync(out, d.q.get(), 6 * nn * sizeof(double), hipMemcpyDeviceToHost, s));
   }
   KMX_HIP(hipStreamSynchronize(s));
   if (what == KMX_DGRAPH_EVAL_JTJ) {
@@ -876,13 +816,13 @@ extern "C" int kmx_dgraph_solve(kmx_dgraph* h, const kmx_dgraph_params* params, 
   KMX_HIP(hipSetDevice(h->device));
   DgDev& d = h->dev;
   hipStream_t s = h->stream;
-  const DgRec I{d.ptr, d.other, d.rec_w, d.rec_d, d.rec_a};
-  const DgPrior P{d.mode, d.Rhat, d.that, d.kappa, d.tau};
+  const DgRec I{d.ptr.get(), d.other.get(), d.rec_w.get(), d.rec_d.get(), d.rec_a.get()};
+  const DgPrior P{d.mode.get(), d.Rhat.get(), d.that.get(), d.kappa.get(), d.tau.get()};
   const dim3 gt(nt), wave(DG_TILE), gn = dg_grid(n, 256), gn6 = dg_grid(6 * (int64_t)n, 256), b256(256), one(1);
   const double rtol2 = Q.cg_rtol * Q.cg_rtol;
   DgState st{};
   st.lambda = Q.lambda_init;
-  KMX_HIP(hipMemcpyAsync(d.st, &st, sizeof(st), hipMemcpyHostToDevice, s));
+  KMX_HIP(hipMemcpyAsync(d.st.get(), &st, sizeof(st), hipMemcpyHostToDevice, s));
   KMX_HIP(hipEventRecord(h->ev[4], s));
   KMX_HIP(hipEventRecord(h->ev[0], s));
   if (int rc = dg_pin(h)) return rc;
@@ -897,39 +837,46 @@ extern "C" int kmx_dgraph_solve(kmx_dgraph* h, const kmx_dgraph_params* params, 
     for (int it = 0;; ++it) {
       if (it > 0) KMX_HIP(hipEventRecord(h->ev[0], s));
       if (moved) {
-        KMX_HIP(hipMemcpyAsync(d.R, d.Rt, 9 * (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-        KMX_HIP(hipMemcpyAsync(d.t, d.tt, 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
+        KMX_HIP(hipMemcpyAsync(d.R.get(), d.Rt.get(), 9 * (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
+        KMX_HIP(hipMemcpyAsync(d.t.get(), d.tt.get(), 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
         if (int rc = dg_linearize(h, 0)) return rc;
         moved = false;
       }
-      hipLaunchKernelGGL(k_dg_precond, gn, b256, 0, s, n, d.mode, d.blk, d.st, d.Minv);
+      hipLaunchKernelGGL(k_dg_precond, gn, b256, 0, s, n, d.mode.get(), d.blk.get(), d.st.get(), d.Minv.get());
       KMX_HIP(hipEventRecord(h->ev[1], s));
-      hipLaunchKernelGGL(k_dg_cg_init, gt, wave, 0, s, n, d.b, d.Minv, d.x, d.r, d.z, d.p, d.part);
-      hipLaunchKernelGGL((k_dg_reduce<0>), one, wave, 0, s, d.part, nt, d.st, rtol2, Q.cg_max_iterations, 0);
+      hipLaunchKernelGGL(k_dg_cg_init, gt, wave, 0, s, n, d.b.get(), d.Minv.get(), d.x.get(), d.r.get(), d.z.get(),
+                         d.p.get(), d.part.get());
+      hipLaunchKernelGGL((k_dg_reduce<0>), one, wave, 0, s, d.part.get(), nt, d.st.get(), rtol2, Q.cg_max_iterations,
+                         0);
       KMX_HIP(hipGetLastError());
       for (int done = 0; done < Q.cg_max_iterations;) {
         const int k = std::min(Q.check_every, Q.cg_max_iterations - done);
         for (int c = 0; c < k; ++c) {
-          hipLaunchKernelGGL((k_dg_apply<false>), gt, wave, 0, s, n, I, P, d.p, d.q, d.st, d.part);
-          hipLaunchKernelGGL((k_dg_reduce<1>), one, wave, 0, s, d.part, nt, d.st, rtol2, Q.cg_max_iterations, 0);
-          hipLaunchKernelGGL(k_dg_update, gt, wave, 0, s, n, d.Minv, d.x, d.r, d.z, d.p, d.q, d.st, d.part);
-          hipLaunchKernelGGL((k_dg_reduce<2>), one, wave, 0, s, d.part, nt, d.st, rtol2, Q.cg_max_iterations, 0);
-          hipLaunchKernelGGL(k_dg_dir, gn6, b256, 0, s, 6 * n, d.z, d.p, d.st);
+          hipLaunchKernelGGL((k_dg_apply<false>), gt, wave, 0, s, n, I, P, d.p.get(), d.q.get(), d.st.get(),
+                             d.part.get());
+          hipLaunchKernelGGL((k_dg_reduce<1>), one, wave, 0, s, d.part.get(), nt, d.st.get(), rtol2,
+                             Q.cg_max_iterations, 0);
+          hipLaunchKernelGGL(k_dg_update, gt, wave, 0, s, n, d.Minv.get(), d.x.get(), d.r.get(), d.z.get(), d.p.get(),
+                             d.q.get(), d.st.get(), d.part.get());
+          hipLaunchKernelGGL((k_dg_reduce<2>), one, wave, 0, s, d.part.get(), nt, d.st.get(), rtol2,
+                             Q.cg_max_iterations, 0);
+          hipLaunchKernelGGL(k_dg_dir, gn6, b256, 0, s, 6 * n, d.z.get(), d.p.get(), d.st.get());
         }
         KMX_HIP(hipGetLastError());
         done += k;
         if (done >= Q.cg_max_iterations) break;
         int running = 0;
-        KMX_HIP(hipMemcpyAsync(&running, &d.st->cg_active, sizeof(int), hipMemcpyDeviceToHost, s));
+        KMX_HIP(hipMemcpyAsync(&running, &d.st.get()->cg_active, sizeof(int), hipMemcpyDeviceToHost, s));
         KMX_HIP(hipStreamSynchronize(s));
         if (!running) break;
       }
       KMX_HIP(hipEventRecord(h->ev[2], s));
-      hipLaunchKernelGGL(k_dg_retract, gn, b256, 0, s, n, d.x, d.R, d.t, d.Rt, d.tt);
-      hipLaunchKernelGGL((k_dg_linearize<false>), gt, wave, 0, s, n, I, P, d.Rt, d.tt, d.b, d.blk, d.part);
-      hipLaunchKernelGGL((k_dg_reduce<4>), one, wave, 0, s, d.part, nt, d.st, 0.0, 0, 0);
-      hipLaunchKernelGGL(k_dg_decide, one, one, 0, s, d.st, Q.factor, Q.lambda_min, Q.lambda_max, Q.rel_tol, Q.abs_tol,
-                         Q.max_iterations);
+      hipLaunchKernelGGL(k_dg_retract, gn, b256, 0, s, n, d.x.get(), d.R.get(), d.t.get(), d.Rt.get(), d.tt.get());
+      hipLaunchKernelGGL((k_dg_linearize<false>), gt, wave, 0, s, n, I, P, d.Rt.get(), d.tt.get(), d.b.get(),
+                         d.blk.get(), d.part.get());
+      hipLaunchKernelGGL((k_dg_reduce<4>), one, wave, 0, s, d.part.get(), nt, d.st.get(), 0.0, 0, 0);
+      hipLaunchKernelGGL(k_dg_decide, one, one, 0, s, d.st.get(), Q.factor, Q.lambda_min, Q.lambda_max, Q.rel_tol,
+                         Q.abs_tol, Q.max_iterations);
       KMX_HIP(hipGetLastError());
       KMX_HIP(hipEventRecord(h->ev[3], s));
       const double f_before = st.f;
@@ -950,8 +897,8 @@ extern "C" int kmx_dgraph_solve(kmx_dgraph* h, const kmx_dgraph_params* params, 
       }
     }
     if (moved) {
-      KMX_HIP(hipMemcpyAsync(d.R, d.Rt, 9 * (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-      KMX_HIP(hipMemcpyAsync(d.t, d.tt, 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
+      KMX_HIP(hipMemcpyAsync(d.R.get(), d.Rt.get(), 9 * (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
+      KMX_HIP(hipMemcpyAsync(d.t.get(), d.tt.get(), 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
     }
   }
   KMX_HIP(hipEventRecord(h->ev[5], s));

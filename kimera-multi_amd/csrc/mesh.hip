@@ -15,6 +15,7 @@
 // w[k] fp64, count.
 #include <algorithm>
 #include <climits>
+#include <memory>
 #include <vector>
 
 #include "common.h"
@@ -273,54 +274,33 @@ __global__ __launch_bounds__(64) void k_mesh_stats(const MeshPartial* part, int 
 
 }  // namespace
 
-struct kmx_mesh {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+struct kmx_mesh : kmx::StreamCore {
   kmx_mesh_params P{};
   kmx::MeshNodeIndex index;
-  int64_t n_vertices = 0, ncap = 0, vcap = 0;
+  int64_t n_vertices = 0, ncap = 0, vcap = 0;  // the capacities are of eight buffers each, set once all have grown
   bool nodes_dirty = false;
   // nodes by id, the staging of current poses, and the sorted layout
-  double *d_rrest = nullptr, *d_g = nullptr, *d_rows = nullptr, *d_rcur = nullptr, *d_p = nullptr;
-  long long* d_s_stamp = nullptr;
-  int *d_s_id = nullptr, *d_off = nullptr;
-  double* d_s_g = nullptr;
+  kmx::DevBuf<double> d_rrest, d_g, d_rows, d_rcur, d_p;
+  kmx::DevBuf<long long> d_s_stamp;
+  kmx::DevBuf<int> d_s_id, d_off;
+  kmx::DevBuf<double> d_s_g;
   std::vector<int32_t> h_off, h_s_id;
   std::vector<int64_t> h_s_stamp;
   std::vector<double> h_s_g;
   // vertices and bindings
-  float *d_vxyz = nullptr, *d_out = nullptr;
-  int *d_vrobot = nullptr, *d_bidx = nullptr, *d_bcnt = nullptr;
-  long long* d_vstamp = nullptr;
-  double* d_bw = nullptr;
-  MeshPartial* d_part = nullptr;
-  MeshStatsDev* d_stats = nullptr;
-  int* d_gblocks = nullptr;
+  kmx::DevBuf<float> d_vxyz, d_out;
+  kmx::DevBuf<int> d_vrobot, d_bidx, d_bcnt;
+  kmx::DevBuf<long long> d_vstamp;
+  kmx::DevBuf<double> d_bw;
+  kmx::DevBuf<MeshPartial> d_part;
+  kmx::DevBuf<MeshStatsDev> d_stats;
+  kmx::DevBuf<int> d_gblocks;
   int last_bind_blocks = 0;
   bool timing = false, bind_timed = false, deform_timed = false;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // bind begin/end, deform begin/end
+  kmx::Event ev[4];  // bind begin/end, deform begin/end
 };
 
 namespace {
-
-// Replaces *p (holding `used` elements) by a buffer of `cap` elements with the same contents.
-template <typename T>
-int mesh_grow(kmx_mesh*, T** p, size_t used, size_t cap) {
-  T* q = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&q), sizeof(T) * std::max<size_t>(cap, 1));
-  if (e != hipSuccess) return kmx::fail(KMX_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-  if (*p && used) {
-    e = hipMemcpy(q, *p, sizeof(T) * used, hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) {
-      (void)hipFree(q);
-      return kmx::fail(KMX_EHIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-  }
-  if (*p) (void)hipFree(*p);
-  *p = q;
-  return 0;
-}
 
 int64_t mesh_next_cap(int64_t cap, int64_t need) {
   int64_t c = std::max<int64_t>(cap, 1024);
@@ -335,10 +315,10 @@ int mesh_reserve_nodes(kmx_mesh* h, int64_t need) {
   KMX_HIP(hipStreamSynchronize(h->stream));
   const size_t c = (size_t)mesh_next_cap(h->ncap, need), u = (size_t)h->index.n_nodes;
   int rc;
-  if ((rc = mesh_grow(h, &h->d_rrest, u * 9, c * 9)) || (rc = mesh_grow(h, &h->d_g, u * 3, c * 3)) ||
-      (rc = mesh_grow(h, &h->d_rows, u * MESH_ROW, c * MESH_ROW)) || (rc = mesh_grow(h, &h->d_rcur, 0, c * 9)) ||
-      (rc = mesh_grow(h, &h->d_p, 0, c * 3)) || (rc = mesh_grow(h, &h->d_s_stamp, 0, c)) ||
-      (rc = mesh_grow(h, &h->d_s_id, 0, c)) || (rc = mesh_grow(h, &h->d_s_g, 0, c * 3)))
+  if ((rc = h->d_rrest.grow_keep(u * 9, c * 9)) || (rc = h->d_g.grow_keep(u * 3, c * 3)) ||
+      (rc = h->d_rows.grow_keep(u * MESH_ROW, c * MESH_ROW)) || (rc = h->d_rcur.alloc(c * 9)) ||
+      (rc = h->d_p.alloc(c * 3)) || (rc = h->d_s_stamp.alloc(c)) || (rc = h->d_s_id.alloc(c)) ||
+      (rc = h->d_s_g.alloc(c * 3)))
     return rc;
   h->ncap = (int64_t)c;
   h->nodes_dirty = true;  // the sorted arrays are new
@@ -350,11 +330,10 @@ int mesh_reserve_vertices(kmx_mesh* h, int64_t need) {
   KMX_HIP(hipStreamSynchronize(h->stream));
   const size_t c = (size_t)mesh_next_cap(h->vcap, need), u = (size_t)h->n_vertices, k = (size_t)h->P.k;
   int rc;
-  if ((rc = mesh_grow(h, &h->d_vxyz, u * 3, c * 3)) || (rc = mesh_grow(h, &h->d_vrobot, u, c)) ||
-      (rc = mesh_grow(h, &h->d_vstamp, u, c)) || (rc = mesh_grow(h, &h->d_bidx, u * k, c * k)) ||
-      (rc = mesh_grow(h, &h->d_bw, u * k, c * k)) || (rc = mesh_grow(h, &h->d_bcnt, u, c)) ||
-      (rc = mesh_grow(h, &h->d_out, 0, c * 3)) ||
-      (rc = mesh_grow(h, &h->d_part, 0, (c + MESH_BLOCK - 1) / MESH_BLOCK)))
+  if ((rc = h->d_vxyz.grow_keep(u * 3, c * 3)) || (rc = h->d_vrobot.grow_keep(u, c)) ||
+      (rc = h->d_vstamp.grow_keep(u, c)) || (rc = h->d_bidx.grow_keep(u * k, c * k)) ||
+      (rc = h->d_bw.grow_keep(u * k, c * k)) || (rc = h->d_bcnt.grow_keep(u, c)) || (rc = h->d_out.alloc(c * 3)) ||
+      (rc = h->d_part.alloc((c + MESH_BLOCK - 1) / MESH_BLOCK)))
     return rc;
   h->vcap = (int64_t)c;
   return 0;
@@ -363,7 +342,7 @@ int mesh_reserve_vertices(kmx_mesh* h, int64_t need) {
 int mesh_form_rows(kmx_mesh* h, int64_t first, int64_t n, const double* d_Rcur, const double* d_p) {
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_mesh_node, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (long long)n, d_Rcur, d_p,
-                     h->d_rrest + 9 * first, h->d_g + 3 * first, h->d_rows + MESH_ROW * first);
+                     h->d_rrest.get() + 9 * first, h->d_g.get() + 3 * first, h->d_rows.get() + MESH_ROW * first);
   KMX_HIP(hipGetLastError());
   return 0;
 }
@@ -375,8 +354,8 @@ void mesh_launch_bind(kmx_mesh* h, const MeshBindArgs& a, int blocks) {
 
 template <int K>
 void mesh_launch_deform(kmx_mesh* h, long long first, long long n, float* out, int blocks) {
-  hipLaunchKernelGGL(k_mesh_deform<K>, dim3(blocks), dim3(MESH_BLOCK), 0, h->stream, first, n, h->d_vxyz, h->d_bidx,
-                     h->d_bw, h->d_bcnt, h->d_rows, out, h->d_part);
+  hipLaunchKernelGGL(k_mesh_deform<K>, dim3(blocks), dim3(MESH_BLOCK), 0, h->stream, first, n, h->d_vxyz.get(),
+                     h->d_bidx.get(), h->d_bw.get(), h->d_bcnt.get(), h->d_rows.get(), out, h->d_part.get());
 }
 
 #define MESH_K_SWITCH(k, call)  \
@@ -399,7 +378,8 @@ int mesh_enqueue_deform(kmx_mesh* h, int64_t first, int64_t n, float* out) {
   MESH_K_SWITCH(h->P.k, MESH_CALL)
 #undef MESH_CALL
   KMX_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_mesh_stats, dim3(1), dim3(64), 0, h->stream, (const MeshPartial*)h->d_part, blocks, h->d_stats);
+  hipLaunchKernelGGL(k_mesh_stats, dim3(1), dim3(64), 0, h->stream, (const MeshPartial*)h->d_part.get(), blocks,
+                     h->d_stats.get());
   KMX_HIP(hipGetLastError());
   if (h->timing) {
     KMX_HIP(hipEventRecord(h->ev[3], h->stream));
@@ -415,63 +395,29 @@ extern "C" int kmx_mesh_create(const kmx_mesh_params* params, int device, kmx_me
   KMX_CHECK(out, KMX_EINVAL, "null argument");
   std::string err;
   if (int rc = kmx::mesh_check_params(params, &err)) return kmx::fail(rc, err);
-  int ndev = 0;
-  KMX_HIP(hipGetDeviceCount(&ndev));
-  KMX_CHECK(device >= 0 && device < ndev, KMX_EINVAL, "bad HIP device ordinal");
-  KMX_HIP(hipSetDevice(device));
-  kmx_mesh* h = new kmx_mesh();
-  h->device = device;
+  std::unique_ptr<kmx_mesh> h(new kmx_mesh());  // a failure below unwinds through the members' destructors
+  int rc;
+  if ((rc = h->open(device)) || (rc = kmx::create_events(h->ev))) return rc;
   h->P = *params;
   h->index.init(params->n_robots);
-  auto fail_create = [&](int rc) {
-    kmx_mesh_destroy(h);
+  if ((rc = h->d_off.alloc((size_t)params->n_robots + 1)) || (rc = h->d_stats.alloc(1)) || (rc = h->d_gblocks.alloc(1)))
     return rc;
-  };
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-    h->stream = nullptr;
-    return fail_create(kmx::fail(KMX_EHIP, "hipStreamCreate failed"));
-  }
-  h->own_stream = true;
-  bool ok = true;
-  for (auto& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-  if (!ok) return fail_create(kmx::fail(KMX_EHIP, "hipEventCreate failed"));
-  int rc;
-  if ((rc = mesh_grow(h, &h->d_off, 0, (size_t)params->n_robots + 1)) || (rc = mesh_grow(h, &h->d_stats, 0, 1)) ||
-      (rc = mesh_grow(h, &h->d_gblocks, 0, 1)))
-    return fail_create(rc);
-  if (hipMemset(h->d_off, 0, sizeof(int) * ((size_t)params->n_robots + 1)) != hipSuccess ||
-      hipMemset(h->d_gblocks, 0, sizeof(int)) != hipSuccess)
-    return fail_create(kmx::fail(KMX_EHIP, "hipMemset failed"));
-  if ((rc = mesh_reserve_nodes(h, 1)) || (rc = mesh_reserve_vertices(h, 1))) return fail_create(rc);
-  *out = h;
+  if (hipMemset(h->d_off.get(), 0, sizeof(int) * ((size_t)params->n_robots + 1)) != hipSuccess ||
+      hipMemset(h->d_gblocks.get(), 0, sizeof(int)) != hipSuccess)
+    return kmx::fail(KMX_EHIP, "hipMemset failed");
+  if ((rc = mesh_reserve_nodes(h.get(), 1)) || (rc = mesh_reserve_vertices(h.get(), 1))) return rc;
+  *out = h.release();
   return KMX_OK;
   KMX_GUARD_END
 }
 
 extern "C" int kmx_mesh_destroy(kmx_mesh* h) {
-  if (!h) return KMX_OK;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void* p : {(void*)h->d_rrest, (void*)h->d_g, (void*)h->d_rows, (void*)h->d_rcur, (void*)h->d_p,
-                  (void*)h->d_s_stamp, (void*)h->d_s_id, (void*)h->d_off, (void*)h->d_s_g, (void*)h->d_vxyz,
-                  (void*)h->d_out, (void*)h->d_vrobot, (void*)h->d_bidx, (void*)h->d_bcnt, (void*)h->d_vstamp,
-                  (void*)h->d_bw, (void*)h->d_part, (void*)h->d_stats, (void*)h->d_gblocks})
-    if (p) (void)hipFree(p);
-  for (auto e : h->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-  return KMX_OK;
+  return kmx::destroy(h);
 }
 
 extern "C" int kmx_mesh_set_stream(kmx_mesh* h, void* s) {
   KMX_CHECK(h, KMX_EINVAL, "null handle");
-  KMX_HIP(hipSetDevice(h->device));
-  if (h->stream) KMX_HIP(hipStreamSynchronize(h->stream));
-  if (h->own_stream && h->stream) KMX_HIP(hipStreamDestroy(h->stream));
-  h->own_stream = false;
-  h->stream = reinterpret_cast<hipStream_t>(s);
-  return KMX_OK;
+  return h->adopt(s, true);
 }
 
 extern "C" int kmx_mesh_info(kmx_mesh* h, kmx_mesh_info_t* info, int64_t* per_robot_nodes,
@@ -481,7 +427,7 @@ extern "C" int kmx_mesh_info(kmx_mesh* h, kmx_mesh_info_t* info, int64_t* per_ro
   if (info) {
     KMX_HIP(hipSetDevice(h->device));
     int gb = 0;
-    KMX_HIP(hipMemcpyAsync(&gb, h->d_gblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    KMX_HIP(hipMemcpyAsync(&gb, h->d_gblocks.get(), sizeof(int), hipMemcpyDeviceToHost, h->stream));
     KMX_HIP(hipStreamSynchronize(h->stream));
     info->n_nodes = h->index.n_nodes;
     info->n_vertices = h->n_vertices;
@@ -515,10 +461,10 @@ extern "C" int kmx_mesh_add_nodes(kmx_mesh* h, int64_t n, const int32_t* robot, 
   KMX_HIP(hipSetDevice(h->device));
   const int64_t n0 = h->index.n_nodes;
   if (int rc = mesh_reserve_nodes(h, n0 + n)) return rc;
-  KMX_HIP(hipMemcpyAsync(h->d_rrest + 9 * n0, Rrest, sizeof(double) * 9 * n, hipMemcpyHostToDevice, h->stream));
-  KMX_HIP(hipMemcpyAsync(h->d_g + 3 * n0, g, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->d_rrest.get() + 9 * n0, Rrest, sizeof(double) * 9 * n, hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->d_g.get() + 3 * n0, g, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->stream));
   // current = rest until kmx_mesh_set_node_poses says otherwise
-  if (int rc = mesh_form_rows(h, n0, n, h->d_rrest + 9 * n0, h->d_g + 3 * n0)) return rc;
+  if (int rc = mesh_form_rows(h, n0, n, h->d_rrest.get() + 9 * n0, h->d_g.get() + 3 * n0)) return rc;
   KMX_HIP(hipStreamSynchronize(h->stream));  // the caller's arrays are free again
   h->index.append_nodes(n, robot, stamp_ns, g);
   h->nodes_dirty = true;
@@ -535,9 +481,9 @@ extern "C" int kmx_mesh_set_node_poses(kmx_mesh* h, int64_t first, int64_t n, co
   KMX_CHECK(kmx::mesh_all_finite(Rcur, (size_t)n * 9) && kmx::mesh_all_finite(p, (size_t)n * 3), KMX_EINVAL,
             "node pose is not finite");
   KMX_HIP(hipSetDevice(h->device));
-  KMX_HIP(hipMemcpyAsync(h->d_rcur + 9 * first, Rcur, sizeof(double) * 9 * n, hipMemcpyHostToDevice, h->stream));
-  KMX_HIP(hipMemcpyAsync(h->d_p + 3 * first, p, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->stream));
-  if (int rc = mesh_form_rows(h, first, n, h->d_rcur + 9 * first, h->d_p + 3 * first)) return rc;
+  KMX_HIP(hipMemcpyAsync(h->d_rcur.get() + 9 * first, Rcur, sizeof(double) * 9 * n, hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->d_p.get() + 3 * first, p, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->stream));
+  if (int rc = mesh_form_rows(h, first, n, h->d_rcur.get() + 9 * first, h->d_p.get() + 3 * first)) return rc;
   KMX_HIP(hipStreamSynchronize(h->stream));
   return KMX_OK;
   KMX_GUARD_END
@@ -554,12 +500,12 @@ extern "C" int kmx_mesh_add_vertices(kmx_mesh* h, int64_t n, const int32_t* robo
   KMX_HIP(hipSetDevice(h->device));
   const int64_t v0 = h->n_vertices;
   if (int rc = mesh_reserve_vertices(h, v0 + n)) return rc;
-  KMX_HIP(hipMemcpyAsync(h->d_vxyz + 3 * v0, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, h->stream));
-  KMX_HIP(hipMemcpyAsync(h->d_vrobot + v0, robot, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
-  KMX_HIP(hipMemcpyAsync(h->d_vstamp + v0, stamp_ns, sizeof(long long) * n, hipMemcpyHostToDevice, h->stream));
-  KMX_HIP(hipMemsetAsync(h->d_bcnt + v0, 0, sizeof(int) * n, h->stream));  // unbound
-  KMX_HIP(hipMemsetAsync(h->d_bidx + v0 * h->P.k, 0xff, sizeof(int) * n * h->P.k, h->stream));
-  KMX_HIP(hipMemsetAsync(h->d_bw + v0 * h->P.k, 0, sizeof(double) * n * h->P.k, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->d_vxyz.get() + 3 * v0, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->d_vrobot.get() + v0, robot, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->d_vstamp.get() + v0, stamp_ns, sizeof(long long) * n, hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemsetAsync(h->d_bcnt.get() + v0, 0, sizeof(int) * n, h->stream));  // unbound
+  KMX_HIP(hipMemsetAsync(h->d_bidx.get() + v0 * h->P.k, 0xff, sizeof(int) * n * h->P.k, h->stream));
+  KMX_HIP(hipMemsetAsync(h->d_bw.get() + v0 * h->P.k, 0, sizeof(double) * n * h->P.k, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   h->index.count_vertices(n, robot);
   h->n_vertices = v0 + n;
@@ -577,18 +523,21 @@ extern "C" int kmx_mesh_bind(kmx_mesh* h, int64_t first, int64_t n) {
     KMX_HIP(hipStreamSynchronize(h->stream));
     h->index.sorted_layout(&h->h_off, &h->h_s_stamp, &h->h_s_id, &h->h_s_g);
     const size_t nn = (size_t)h->index.n_nodes;
-    KMX_HIP(hipMemcpyAsync(h->d_off, h->h_off.data(), sizeof(int) * h->h_off.size(), hipMemcpyHostToDevice, h->stream));
+    KMX_HIP(hipMemcpyAsync(h->d_off.get(), h->h_off.data(), sizeof(int) * h->h_off.size(), hipMemcpyHostToDevice,
+                           h->stream));
     if (nn) {
-      KMX_HIP(hipMemcpyAsync(h->d_s_stamp, h->h_s_stamp.data(), sizeof(long long) * nn, hipMemcpyHostToDevice,
+      KMX_HIP(hipMemcpyAsync(h->d_s_stamp.get(), h->h_s_stamp.data(), sizeof(long long) * nn, hipMemcpyHostToDevice,
                              h->stream));
-      KMX_HIP(hipMemcpyAsync(h->d_s_id, h->h_s_id.data(), sizeof(int) * nn, hipMemcpyHostToDevice, h->stream));
-      KMX_HIP(hipMemcpyAsync(h->d_s_g, h->h_s_g.data(), sizeof(double) * 3 * nn, hipMemcpyHostToDevice, h->stream));
+      KMX_HIP(hipMemcpyAsync(h->d_s_id.get(), h->h_s_id.data(), sizeof(int) * nn, hipMemcpyHostToDevice, h->stream));
+      KMX_HIP(hipMemcpyAsync(h->d_s_g.get(), h->h_s_g.data(), sizeof(double) * 3 * nn, hipMemcpyHostToDevice,
+                             h->stream));
     }
     h->nodes_dirty = false;
   }
-  KMX_HIP(hipMemsetAsync(h->d_gblocks, 0, sizeof(int), h->stream));
-  MeshBindArgs a{(long long)first, (long long)n, (long long)h->P.window_ns, h->d_off, h->d_s_stamp, h->d_s_id,
-                 h->d_s_g, h->d_vxyz, h->d_vrobot, h->d_vstamp, h->d_bidx, h->d_bw, h->d_bcnt, h->d_gblocks};
+  KMX_HIP(hipMemsetAsync(h->d_gblocks.get(), 0, sizeof(int), h->stream));
+  MeshBindArgs a{(long long)first, (long long)n, (long long)h->P.window_ns, h->d_off.get(), h->d_s_stamp.get(),
+                 h->d_s_id.get(), h->d_s_g.get(), h->d_vxyz.get(), h->d_vrobot.get(), h->d_vstamp.get(),
+                 h->d_bidx.get(), h->d_bw.get(), h->d_bcnt.get(), h->d_gblocks.get()};
   const int blocks = (int)((n + MESH_BLOCK - 1) / MESH_BLOCK);
   if (h->timing) KMX_HIP(hipEventRecord(h->ev[0], h->stream));
 #define MESH_CALL(K) mesh_launch_bind<K>(h, a, blocks)
@@ -612,9 +561,10 @@ extern "C" int kmx_mesh_get_bindings(kmx_mesh* h, int64_t first, int64_t n, int3
   KMX_HIP(hipSetDevice(h->device));
   const size_t k = (size_t)h->P.k;
   if (idx)
-    KMX_HIP(hipMemcpyAsync(idx, h->d_bidx + first * k, sizeof(int) * n * k, hipMemcpyDeviceToHost, h->stream));
-  if (w) KMX_HIP(hipMemcpyAsync(w, h->d_bw + first * k, sizeof(double) * n * k, hipMemcpyDeviceToHost, h->stream));
-  if (count) KMX_HIP(hipMemcpyAsync(count, h->d_bcnt + first, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
+    KMX_HIP(hipMemcpyAsync(idx, h->d_bidx.get() + first * k, sizeof(int) * n * k, hipMemcpyDeviceToHost, h->stream));
+  if (w) KMX_HIP(hipMemcpyAsync(w, h->d_bw.get() + first * k, sizeof(double) * n * k, hipMemcpyDeviceToHost,
+                                h->stream));
+  if (count) KMX_HIP(hipMemcpyAsync(count, h->d_bcnt.get() + first, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   return KMX_OK;
   KMX_GUARD_END
@@ -639,10 +589,10 @@ extern "C" int kmx_mesh_deform(kmx_mesh* h, int64_t first, int64_t n, float* xyz
   if (n == 0) return KMX_OK;
   KMX_CHECK(xyz_out, KMX_EINVAL, "null output");
   KMX_HIP(hipSetDevice(h->device));
-  if (int rc = mesh_enqueue_deform(h, first, n, h->d_out)) return rc;
+  if (int rc = mesh_enqueue_deform(h, first, n, h->d_out.get())) return rc;
   MeshStatsDev s{};
-  KMX_HIP(hipMemcpyAsync(xyz_out, h->d_out, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, h->stream));
-  KMX_HIP(hipMemcpyAsync(&s, h->d_stats, sizeof(s), hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(xyz_out, h->d_out.get(), sizeof(float) * 3 * n, hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(&s, h->d_stats.get(), sizeof(s), hipMemcpyDeviceToHost, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   if (stats_out) {
     stats_out->n_unbound = s.unbound;

@@ -29,6 +29,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -224,86 +225,70 @@ __global__ __launch_bounds__(RED_BLOCK) void k_voc_reduce(VocDev v, int N, int a
   if (tid == 0) nnz[blockIdx.x] = nh;
 }
 
-template <typename T>
-int voc_alloc(T** p, size_t n) {
-  *p = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * std::max<size_t>(n, 1));
-  if (e != hipSuccess) return kmx::fail(KMX_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-  return 0;
-}
+// The batch buffers (grow-only, replaced as a whole): uploaded descriptors /
+// counts / frame ids, leaves, outputs.
+struct VocBatch {
+  kmx::DevBuf<uint4> in;                 // [dcap()][2]; only the host path has it
+  kmx::DevBuf<int> nfeat, fid, nnz;      // [fcap()]
+  kmx::DevBuf<int> leaf;                 // [scap()]
+  kmx::DevBuf<unsigned> words;           // [scap()]
+  kmx::DevBuf<double> weights;           // [scap()]
+  size_t fcap() const { return nnz.cap(); }      // frames
+  size_t scap() const { return weights.cap(); }  // feature slots
+  size_t dcap() const { return in.cap() / 2; }   // uploaded descriptor slots
+};
 
 }  // namespace
 
-struct kmx_voc {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+struct kmx_voc : kmx::StreamCore {
   int n_nodes = 0, n_words = 0, max_children = 0, max_depth = 0, n_lds = 0, weighting = 0;
   int grid = 0;
-  uint4* d_desc = nullptr;
-  int2* d_child = nullptr;
-  int* d_word_of = nullptr;
-  double* d_weight = nullptr;
-  double* d_word_weight = nullptr;
-  // batch buffers (grow-only): uploaded descriptors / counts / frame ids, leaves, outputs
-  size_t fcap = 0, scap = 0, dcap = 0;  // frames, feature slots, uploaded descriptor slots
-  int last_frames = 0, last_N = 0;      // the batch whose outputs the device holds
-  uint4* d_in = nullptr;
-  int *d_nfeat = nullptr, *d_fid = nullptr, *d_leaf = nullptr, *d_nnz = nullptr;
-  unsigned* d_words = nullptr;
-  double* d_weights = nullptr;
-  hipEvent_t ev_pool = nullptr;  // orders a pool transform after the detector's stream
+  kmx::DevBuf<uint4> d_desc;
+  kmx::DevBuf<int2> d_child;
+  kmx::DevBuf<int> d_word_of;
+  kmx::DevBuf<double> d_weight;
+  kmx::DevBuf<double> d_word_weight;
+  VocBatch b;
+  int last_frames = 0, last_N = 0;  // the batch whose outputs the device holds
+  kmx::Event ev_pool;               // orders a pool transform after the detector's stream
   bool timing = false;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  kmx::Event ev[3];
 };
 
 namespace {
 
-void voc_free_batch(kmx_voc* h) {
-  for (void* p : {(void*)h->d_in, (void*)h->d_nfeat, (void*)h->d_fid, (void*)h->d_leaf, (void*)h->d_nnz,
-                  (void*)h->d_words, (void*)h->d_weights})
-    if (p) (void)hipFree(p);
-  h->d_in = nullptr;
-  h->d_nfeat = h->d_fid = h->d_leaf = h->d_nnz = nullptr;
-  h->d_words = nullptr;
-  h->d_weights = nullptr;
-  h->fcap = h->scap = h->dcap = 0;
-}
-
 // Room for a batch of n frames at stride N (and, for the host path, its descriptors).
 int voc_reserve(kmx_voc* h, size_t n, size_t N, bool upload) {
   const size_t slots = n * N;
-  if (n <= h->fcap && slots <= h->scap && (!upload || slots <= h->dcap)) return 0;
+  if (n <= h->b.fcap() && slots <= h->b.scap() && (!upload || slots <= h->b.dcap())) return 0;
   KMX_HIP(hipStreamSynchronize(h->stream));  // a batch in flight uses the old buffers
-  const size_t fcap = std::max(n, h->fcap), scap = std::max(slots, h->scap);
-  const size_t dcap = upload ? std::max(slots, h->dcap) : h->dcap;
-  voc_free_batch(h);
+  const size_t fcap = std::max(n, h->b.fcap()), scap = std::max(slots, h->b.scap());
+  const size_t dcap = upload ? std::max(slots, h->b.dcap()) : h->b.dcap();
+  h->b = VocBatch();  // the old batch goes first; a failure below leaves the handle without one
+  VocBatch b;
   int rc;
-  if ((rc = voc_alloc(&h->d_nfeat, fcap)) || (rc = voc_alloc(&h->d_fid, fcap)) || (rc = voc_alloc(&h->d_nnz, fcap)) ||
-      (rc = voc_alloc(&h->d_leaf, scap)) || (rc = voc_alloc(&h->d_words, scap)) ||
-      (rc = voc_alloc(&h->d_weights, scap)) || (dcap && (rc = voc_alloc(&h->d_in, dcap * 2)))) {
-    voc_free_batch(h);
+  if ((rc = b.nfeat.alloc(fcap)) || (rc = b.fid.alloc(fcap)) || (rc = b.nnz.alloc(fcap)) ||
+      (rc = b.leaf.alloc(scap)) || (rc = b.words.alloc(scap)) || (rc = b.weights.alloc(scap)) ||
+      (dcap && (rc = b.in.alloc(dcap * 2))))
     return rc;
-  }
-  h->fcap = fcap;
-  h->scap = scap;
-  h->dcap = dcap;
+  h->b = std::move(b);
   return 0;
 }
 
 // Both kernels for n frames at stride N over the descriptor pool `desc`
 // (counts d_nf indexed by pool frame; d_fid: batch frame -> pool frame, or null).
 int voc_launch(kmx_voc* h, int n, int N, const int* d_nf, const int* d_fid, const uint4* desc) {
-  VocDev v{h->d_desc, h->d_child, h->d_word_of, h->d_weight, h->d_word_weight, h->n_nodes, h->n_lds};
+  VocDev v{h->d_desc.get(), h->d_child.get(), h->d_word_of.get(), h->d_weight.get(), h->d_word_weight.get(), h->n_nodes,
+           h->n_lds};
   const long long total = (long long)n * N;
   const int grid = (int)std::min<long long>((total + VOC_BLOCK - 1) / VOC_BLOCK, h->grid);
   if (h->timing) KMX_HIP(hipEventRecord(h->ev[0], h->stream));
   hipLaunchKernelGGL(k_voc_descend, dim3(grid), dim3(VOC_BLOCK), 0, h->stream, v, total, N, d_nf, d_fid, desc,
-                     h->d_leaf);
+                     h->b.leaf.get());
   KMX_HIP(hipGetLastError());
   if (h->timing) KMX_HIP(hipEventRecord(h->ev[1], h->stream));
   hipLaunchKernelGGL(k_voc_reduce, dim3(n), dim3(RED_BLOCK), 0, h->stream, v, N, h->weighting <= 1 ? 1 : 0,
-                     (const int*)h->d_leaf, h->d_nnz, h->d_words, h->d_weights);
+                     (const int*)h->b.leaf.get(), h->b.nnz.get(), h->b.words.get(), h->b.weights.get());
   KMX_HIP(hipGetLastError());
   if (h->timing) KMX_HIP(hipEventRecord(h->ev[2], h->stream));
   h->last_frames = n;
@@ -313,9 +298,9 @@ int voc_launch(kmx_voc* h, int n, int N, const int* d_nf, const int* d_fid, cons
 
 int voc_fetch(kmx_voc* h, int32_t* out_nnz, uint32_t* out_words, double* out_weights) {
   const size_t n = (size_t)h->last_frames, slots = n * h->last_N;
-  KMX_HIP(hipMemcpyAsync(out_nnz, h->d_nnz, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
-  KMX_HIP(hipMemcpyAsync(out_words, h->d_words, sizeof(unsigned) * slots, hipMemcpyDeviceToHost, h->stream));
-  KMX_HIP(hipMemcpyAsync(out_weights, h->d_weights, sizeof(double) * slots, hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(out_nnz, h->b.nnz.get(), sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(out_words, h->b.words.get(), sizeof(unsigned) * slots, hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(out_weights, h->b.weights.get(), sizeof(double) * slots, hipMemcpyDeviceToHost, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -328,9 +313,9 @@ int kmx::voc_batch_view(kmx_voc* h, kmx::VocBatchView* out) {
   out->n_words = h->n_words;
   out->n_frames = h->last_frames;
   out->stride = h->last_N;
-  out->nnz = h->d_nnz;
-  out->words = h->d_words;
-  out->weights = h->d_weights;
+  out->nnz = h->b.nnz.get();
+  out->words = h->b.words.get();
+  out->weights = h->b.weights.get();
   out->stream = h->stream;
   return KMX_OK;
 }
@@ -345,12 +330,9 @@ extern "C" int kmx_voc_create(int device, int32_t n_nodes, const int32_t* parent
   std::string err;
   if (int rc = kmx::voc_prepare(n_nodes, parent, descriptor, weight, n_words, word_node, weighting, &L, &err))
     return kmx::fail(rc, err);
-  int ndev = 0;
-  KMX_HIP(hipGetDeviceCount(&ndev));
-  KMX_CHECK(device >= 0 && device < ndev, KMX_EINVAL, "bad HIP device ordinal");
-  KMX_HIP(hipSetDevice(device));
-  kmx_voc* h = new kmx_voc();
-  h->device = device;
+  std::unique_ptr<kmx_voc> h(new kmx_voc());  // a failure below unwinds through the members' destructors
+  int rc;
+  if ((rc = h->open(device))) return rc;
   h->n_nodes = L.n_nodes;
   h->n_words = L.n_words;
   h->max_children = L.max_children;
@@ -363,64 +345,36 @@ extern "C" int kmx_voc_create(int device, int32_t n_nodes, const int32_t* parent
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_voc_descend, VOC_BLOCK, 0) != hipSuccess || per_cu < 1)
     per_cu = 1;
   h->grid = std::max(1, cus) * per_cu;
-  auto fail_create = [&](int rc) {
-    kmx_voc_destroy(h);
-    return rc;
-  };
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-    h->stream = nullptr;
-    return fail_create(kmx::fail(KMX_EHIP, "hipStreamCreate failed"));
-  }
-  h->own_stream = true;
-  bool ok = hipEventCreateWithFlags(&h->ev_pool, hipEventDisableTiming) == hipSuccess;
-  for (auto& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-  if (!ok) return fail_create(kmx::fail(KMX_EHIP, "hipEventCreate failed"));
+  if ((rc = h->ev_pool.create(hipEventDisableTiming)) || (rc = kmx::create_events(h->ev))) return rc;
   std::vector<int2> child((size_t)L.n_nodes);
   for (int i = 0; i < L.n_nodes; ++i) child[i] = make_int2(L.child_first[i], L.child_count[i]);
-  int rc;
-  if ((rc = voc_alloc(&h->d_desc, (size_t)L.n_nodes * 2)) || (rc = voc_alloc(&h->d_child, child.size())) ||
-      (rc = voc_alloc(&h->d_word_of, L.word_of.size())) || (rc = voc_alloc(&h->d_weight, L.weight.size())) ||
-      (rc = voc_alloc(&h->d_word_weight, L.word_weight.size())))
-    return fail_create(rc);
-  hipError_t e = hipMemcpy(h->d_desc, L.desc.data(), sizeof(uint32_t) * L.desc.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(h->d_child, child.data(), sizeof(int2) * child.size(), hipMemcpyHostToDevice);
+  if ((rc = h->d_desc.alloc((size_t)L.n_nodes * 2)) || (rc = h->d_child.alloc(child.size())) ||
+      (rc = h->d_word_of.alloc(L.word_of.size())) || (rc = h->d_weight.alloc(L.weight.size())) ||
+      (rc = h->d_word_weight.alloc(L.word_weight.size())))
+    return rc;
+  hipError_t e = hipMemcpy(h->d_desc.get(), L.desc.data(), sizeof(uint32_t) * L.desc.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(h->d_child.get(), child.data(), sizeof(int2) * child.size(),
+                                     hipMemcpyHostToDevice);
   if (e == hipSuccess)
-    e = hipMemcpy(h->d_word_of, L.word_of.data(), sizeof(int) * L.word_of.size(), hipMemcpyHostToDevice);
+    e = hipMemcpy(h->d_word_of.get(), L.word_of.data(), sizeof(int) * L.word_of.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess)
-    e = hipMemcpy(h->d_weight, L.weight.data(), sizeof(double) * L.weight.size(), hipMemcpyHostToDevice);
+    e = hipMemcpy(h->d_weight.get(), L.weight.data(), sizeof(double) * L.weight.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess)
-    e = hipMemcpy(h->d_word_weight, L.word_weight.data(), sizeof(double) * L.word_weight.size(),
+    e = hipMemcpy(h->d_word_weight.get(), L.word_weight.data(), sizeof(double) * L.word_weight.size(),
                   hipMemcpyHostToDevice);
-  if (e != hipSuccess) return fail_create(kmx::fail(KMX_EHIP, std::string("hipMemcpy: ") + hipGetErrorString(e)));
-  *out = h;
+  if (e != hipSuccess) return kmx::fail(KMX_EHIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+  *out = h.release();
   return KMX_OK;
   KMX_GUARD_END
 }
 
 extern "C" int kmx_voc_destroy(kmx_voc* h) {
-  if (!h) return KMX_OK;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  voc_free_batch(h);
-  for (void* p : {(void*)h->d_desc, (void*)h->d_child, (void*)h->d_word_of, (void*)h->d_weight,
-                  (void*)h->d_word_weight})
-    if (p) (void)hipFree(p);
-  if (h->ev_pool) (void)hipEventDestroy(h->ev_pool);
-  for (auto e : h->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-  return KMX_OK;
+  return kmx::destroy(h);
 }
 
 extern "C" int kmx_voc_set_stream(kmx_voc* h, void* s) {
   KMX_CHECK(h, KMX_EINVAL, "null handle");
-  KMX_HIP(hipSetDevice(h->device));
-  if (h->stream) KMX_HIP(hipStreamSynchronize(h->stream));
-  if (h->own_stream && h->stream) KMX_HIP(hipStreamDestroy(h->stream));
-  h->own_stream = false;
-  h->stream = reinterpret_cast<hipStream_t>(s);
-  return KMX_OK;
+  return h->adopt(s, true);
 }
 
 extern "C" int kmx_voc_info(kmx_voc* h, int32_t* n_nodes, int32_t* n_words, int32_t* max_children,
@@ -449,9 +403,9 @@ extern "C" int kmx_voc_transform_async(kmx_voc* h, int32_t n_frames, int32_t max
   if (n_frames == 0) return KMX_OK;
   if (int rc = voc_reserve(h, (size_t)n_frames, (size_t)max_feats, true)) return rc;
   const size_t slots = (size_t)n_frames * max_feats;
-  KMX_HIP(hipMemcpyAsync(h->d_in, desc, slots * 32, hipMemcpyHostToDevice, h->stream));
-  KMX_HIP(hipMemcpyAsync(h->d_nfeat, n_feats, sizeof(int) * n_frames, hipMemcpyHostToDevice, h->stream));
-  return voc_launch(h, n_frames, max_feats, h->d_nfeat, nullptr, h->d_in);
+  KMX_HIP(hipMemcpyAsync(h->b.in.get(), desc, slots * 32, hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->b.nfeat.get(), n_feats, sizeof(int) * n_frames, hipMemcpyHostToDevice, h->stream));
+  return voc_launch(h, n_frames, max_feats, h->b.nfeat.get(), nullptr, h->b.in.get());
   KMX_GUARD_END
 }
 
@@ -477,13 +431,14 @@ extern "C" int kmx_voc_transform_pool_async(kmx_voc* h, kmx_lcd* pool, int32_t n
   KMX_HIP(hipSetDevice(h->device));
   h->last_frames = 0;
   if (n == 0) return KMX_OK;
-  KMX_CHECK(pv.desc && pv.n_feats && pv.max_feats >= 1 && pv.max_feats <= RED_MAX, KMX_ESTATE, "the pool has no frames");
+  KMX_CHECK(pv.desc && pv.n_feats && pv.max_feats >= 1 && pv.max_feats <= RED_MAX, KMX_ESTATE,
+            "the pool has no frames");
   if (int rc = voc_reserve(h, (size_t)n, (size_t)pv.max_feats, false)) return rc;
   // after whatever the detector has enqueued on its stream (frame uploads)
   KMX_HIP(hipEventRecord(h->ev_pool, pv.stream));
   KMX_HIP(hipStreamWaitEvent(h->stream, h->ev_pool, 0));
-  KMX_HIP(hipMemcpyAsync(h->d_fid, frame_ids, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
-  return voc_launch(h, n, pv.max_feats, pv.n_feats, h->d_fid, reinterpret_cast<const uint4*>(pv.desc));
+  KMX_HIP(hipMemcpyAsync(h->b.fid.get(), frame_ids, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
+  return voc_launch(h, n, pv.max_feats, pv.n_feats, h->b.fid.get(), reinterpret_cast<const uint4*>(pv.desc));
   KMX_GUARD_END
 }
 
