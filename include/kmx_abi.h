@@ -378,6 +378,10 @@ int kmx_pgo_get_trajectory(kmx_pgo* h, int robot, const double* anchor,
 #define KMX_EVAL_RHESS 3      /* out = Riemannian Hessian at X applied to V      */
 #define KMX_EVAL_PRECON 4     /* out = preconditioner at X applied to V          */
 #define KMX_EVAL_RETRACT 5    /* out = R_X(V)                                    */
+#define KMX_EVAL_PROJECT 6    /* out = Proj(V): the polar factor U V^T of every pose's r x 3
+                               * rotation block, translation column unchanged (the projection
+                               * of the accelerated rounds; any finite V gives orthonormal
+                               * columns, rank-deficient blocks included). Additive to ABI 10. */
 int kmx_pgo_eval(kmx_pgo* h, int robot, int mode, const double* V, double* out,
                  double* scalar);
 

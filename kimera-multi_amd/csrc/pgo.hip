@@ -56,6 +56,7 @@
 
 #include "common.h"
 #include "pgo_host.h"
+#include "so3_project.h"
 
 // KMX_HESS_PROBE (diagnostic builds only, scripts/gpu_hess_probe.sh): bits
 // remove one k_hess stream each so its PMC traffic can be attributed; the
@@ -565,6 +566,178 @@ __device__ __forceinline__ void group_retract(const double x[4], const double v[
   }
   out[0] = A[0]; out[1] = A[1]; out[2] = A[2];
   out[3] = x[3] + v[3];
+}
+
+// Proj of the accelerated rounds (k_accel) and KMX_EVAL_PROJECT: the polar
+// factor U V^T of the pose's r x 3 rotation block (this lane holds row a in
+// m[0..2]); out[3] = m[3]. Every lane of the group fetches the whole block
+// (3 R shuffles, all lanes active) and runs the oracle's proj_stiefel on it in
+// registers, so nothing below exchanges data and a lane may leave its loops
+// alone. One-sided Jacobi, as so3_project.h: plane rotations W turn the
+// columns of A = M W orthogonal and Y = sum_k (A_k / |A_k|) W_k^T. The block is
+// never squared and no vanishing singular value is divided by: a column that
+// is zero, or that one Gram-Schmidt step against the larger columns'
+// directions takes more than half of (its direction is rounding noise), is
+// replaced by a completion of the frame (the e_k the kept directions are least
+// along, made orthogonal in two passes; their squared entries in row k sum to
+// at most 2 / R < 1 there, so what is left never vanishes). The output always
+// has orthonormal columns; the zero block, and a block with a non-finite
+// entry, give e1 e2 e3. `live` is false on the idle tail lanes, whose block
+// would mix two groups: they work on zeros.
+template <int R>
+__device__ __forceinline__ void group_project(const double m[4], int a, int base, bool live, double out[4]) {
+  double A[R][3], W[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+  double amax = 0.0, fin = 0.0;
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double x = __shfl(m[c], base + k, 64);
+      A[k][c] = live ? x : 0.0;
+      amax = fmax(amax, fabs(A[k][c]));
+    }
+    fin += (A[k][0] + A[k][1] + A[k][2]) * 0.0;  // Inf * 0 and NaN * 0 are NaN
+  }
+  const bool ok = fin == 0.0 && amax > 0.0 && amax < INFINITY;
+#pragma unroll
+  for (int k = 0; k < R; ++k)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) A[k][c] = ok ? A[k][c] / amax : 0.0;  // the projection does not depend on the scale
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    bool rotated = false;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = i + 1; j < 3; ++j) {
+        double aii = 0.0, ajj = 0.0, aij = 0.0;
+#pragma unroll
+        for (int k = 0; k < R; ++k) aii += A[k][i] * A[k][i];
+#pragma unroll
+        for (int k = 0; k < R; ++k) ajj += A[k][j] * A[k][j];
+#pragma unroll
+        for (int k = 0; k < R; ++k) aij += A[k][i] * A[k][j];
+        // orthogonal to 4 eps: below it a rotation only moves rounding noise about (the sums'
+        // own rounding is R eps / 2), and the Gram-Schmidt step below takes what is left
+        if (fabs(aij) <= 0x1p-50 * sqrt(aii * ajj) || aij == 0.0 || !(fabs(aij) < INFINITY)) continue;
+        rotated = true;
+        const double zeta = (ajj - aii) / (2.0 * aij);
+        const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+        const double cs = 1.0 / sqrt(1.0 + tt * tt), sn = cs * tt;
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+          const double ai = A[k][i], aj = A[k][j];
+          A[k][i] = cs * ai - sn * aj;
+          A[k][j] = sn * ai + cs * aj;
+        }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          const double vi = W[q][i], vj = W[q][j];
+          W[q][i] = cs * vi - sn * vj;
+          W[q][j] = sn * vi + cs * vj;
+        }
+      }
+    if (!rotated) break;
+  }
+  double s2[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int k = 0; k < R; ++k) s2[c] += A[k][c] * A[k][c];
+  // columns by decreasing norm, as the oracle picks them: the largest (the
+  // first of equals), then the other two in index order unless the later is
+  // larger; moved with selects, so no register is indexed
+  auto swap_cols = [&](int x, int y, bool on) {
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const double p = A[k][x], q = A[k][y];
+      A[k][x] = on ? q : p;
+      A[k][y] = on ? p : q;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const double p = W[k][x], q = W[k][y];
+      W[k][x] = on ? q : p;
+      W[k][y] = on ? p : q;
+    }
+    const double p = s2[x], q = s2[y];
+    s2[x] = on ? q : p;
+    s2[y] = on ? p : q;
+  };
+  const bool first2 = s2[2] > fmax(s2[0], s2[1]), first1 = !first2 && s2[1] > s2[0];
+  swap_cols(0, 1, first1);  // (1, 0, 2)
+  swap_cols(1, 2, first2);  // (0, 2, 1) ...
+  swap_cols(0, 1, first2);  // ... (2, 0, 1)
+  swap_cols(1, 2, s2[2] > s2[1]);
+  // u1: the largest column (zero only for the zero block), in place in A
+  {
+    const double n1 = sqrt(s2[0]);
+#pragma unroll
+    for (int k = 0; k < R; ++k) A[k][0] = s2[0] > 0.0 ? A[k][0] / n1 : (k == 0 ? 1.0 : 0.0);
+  }
+  // u2, u3: one Gram-Schmidt step against the directions before them, or the completion
+#pragma unroll
+  for (int c = 1; c < 3; ++c) {
+    const double s = s2[c], ns = sqrt(s);
+    double t[R];
+#pragma unroll
+    for (int k = 0; k < R; ++k) t[k] = s > 1e-280 ? A[k][c] / ns : 0.0;
+#pragma unroll
+    for (int j = 0; j < c; ++j) {
+      double dot = 0.0;
+#pragma unroll
+      for (int k = 0; k < R; ++k) dot += A[k][j] * t[k];
+#pragma unroll
+      for (int k = 0; k < R; ++k) t[k] -= dot * A[k][j];
+    }
+    double nn = 0.0;
+#pragma unroll
+    for (int k = 0; k < R; ++k) nn += t[k] * t[k];
+    if (nn >= 0.5) {
+      const double nt = sqrt(nn);
+#pragma unroll
+      for (int k = 0; k < R; ++k) A[k][c] = t[k] / nt;
+    } else {
+      int kb = 0;
+      double best = 0.0;
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        double q = 0.0;
+#pragma unroll
+        for (int j = 0; j < c; ++j) q += A[k][j] * A[k][j];
+        if (k == 0 || q < best) {
+          best = q;
+          kb = k;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < R; ++k) t[k] = (k == kb) ? 1.0 : 0.0;
+#pragma unroll
+      for (int pass = 0; pass < 2; ++pass)
+#pragma unroll
+        for (int j = 0; j < c; ++j) {
+          double dot = 0.0;
+#pragma unroll
+          for (int k = 0; k < R; ++k) dot += A[k][j] * t[k];
+#pragma unroll
+          for (int k = 0; k < R; ++k) t[k] -= dot * A[k][j];
+        }
+      double nw = 0.0;
+#pragma unroll
+      for (int k = 0; k < R; ++k) nw += t[k] * t[k];
+      nw = sqrt(nw);
+#pragma unroll
+      for (int k = 0; k < R; ++k) A[k][c] = t[k] / nw;
+    }
+  }
+  // this lane's row of U W^T
+  double ua[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+  for (int k = 0; k < R; ++k)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) ua[c] = (k == a) ? A[k][c] : ua[c];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) out[j] = ua[0] * W[j][0] + ua[1] * W[j][1] + ua[2] * W[j][2];
+  out[3] = m[3];
 }
 
 // ------------------------------------------------------------- lane map ----
@@ -2816,36 +2989,8 @@ __global__ void k_shared_unpack(double* ew, const int* sh_edge, const int* sh_id
 }
 
 // --- rounding to SE(3) in the anchor frame (same algorithm as the oracle) --
-__device__ void jacobi3(double A[9], double V[9]) {
-  for (int i = 0; i < 9; ++i) V[i] = (i % 4 == 0) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 12; ++sweep) {
-    for (int p = 0; p < 2; ++p)
-      for (int q = p + 1; q < 3; ++q) {
-        const double apq = A[p * 3 + q];
-        if (apq == 0.0) continue;
-        const double app = A[p * 3 + p], aqq = A[q * 3 + q];
-        const double theta = (aqq - app) / (2.0 * apq);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
-        for (int k = 0; k < 3; ++k) {
-          const double akp = A[k * 3 + p], akq = A[k * 3 + q];
-          A[k * 3 + p] = cs * akp - sn * akq;
-          A[k * 3 + q] = sn * akp + cs * akq;
-        }
-        for (int k = 0; k < 3; ++k) {
-          const double apk = A[p * 3 + k], aqk = A[q * 3 + k];
-          A[p * 3 + k] = cs * apk - sn * aqk;
-          A[q * 3 + k] = sn * apk + cs * aqk;
-        }
-        for (int k = 0; k < 3; ++k) {
-          const double vkp = V[k * 3 + p], vkq = V[k * 3 + q];
-          V[k * 3 + p] = cs * vkp - sn * vkq;
-          V[k * 3 + q] = sn * vkp + cs * vkq;
-        }
-      }
-  }
-}
-
+// R = the nearest rotation to M = Ya^T Yi (so3_project.h: any singular values,
+// 0 included, give a finite proper rotation), t = Ya^T (pi - pa).
 __global__ void k_traj(const double* X, int n, int R_, const double* anchor, double* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -2861,32 +3006,10 @@ __global__ void k_traj(const double* X, int n, int R_, const double* anchor, dou
     for (int k = 0; k < R_; ++k) s += anchor[4 * k + x] * (Xi[4 * k + 3] - anchor[4 * k + 3]);
     tv[x] = s;
   }
-  double A[9], V[9];
-  for (int a = 0; a < 3; ++a)
-    for (int b = 0; b < 3; ++b) {
-      double s = 0.0;
-      for (int k = 0; k < 3; ++k) s += M[k * 3 + a] * M[k * 3 + b];
-      A[a * 3 + b] = s;
-    }
-  jacobi3(A, V);
-  const double det = M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) +
-                     M[2] * (M[3] * M[7] - M[4] * M[6]);
-  int kmin = 0;
-  for (int k = 1; k < 3; ++k)
-    if (A[k * 4] < A[kmin * 4]) kmin = k;
-  double Rr[9];
-  for (int q = 0; q < 9; ++q) Rr[q] = 0.0;
-  for (int k = 0; k < 3; ++k) {
-    const double sig = sqrt(fmax(A[k * 4], 0.0));
-    double u[3];
-    for (int q = 0; q < 3; ++q)
-      u[q] = (M[q * 3 + 0] * V[0 * 3 + k] + M[q * 3 + 1] * V[1 * 3 + k] + M[q * 3 + 2] * V[2 * 3 + k]) / sig;
-    const double s = (k == kmin && det < 0.0) ? -1.0 : 1.0;
-    for (int a = 0; a < 3; ++a)
-      for (int b = 0; b < 3; ++b) Rr[a * 3 + b] += s * u[a] * V[b * 3 + k];
-  }
+  double Rr[3][3];
+  so3_project_block(M, Rr);
   double* o = out + (size_t)i * 12;
-  for (int q = 0; q < 9; ++q) o[q] = Rr[q];
+  for (int q = 0; q < 9; ++q) o[q] = Rr[q / 3][q % 3];
   o[9] = tv[0]; o[10] = tv[1]; o[11] = tv[2];
 }
 
@@ -2894,9 +3017,8 @@ __global__ void k_traj(const double* X, int n, int R_, const double* anchor, dou
 //   mode 0: Y = Proj((1 - c) X + c V) -> Yb, X and the owned public rows
 //   mode 1: V = Proj(V + c (X - Yb))
 //   mode 2: V = X (restart)
-// Proj: polar factor of the pose's r x 3 rotation block, M (M^T M)^(-1/2) from
-// the group's 3 x 3 Gram matrix (gsum in row order) and jacobi3; translation
-// unchanged. One lane per (pose, row), as k_retract.
+// Proj: polar factor of the pose's r x 3 rotation block (group_project);
+// translation unchanged. One lane per (pose, row), as k_retract.
 template <int R>
 __global__ __launch_bounds__(BLOCK) void k_accel(Dev d, double* V, double* Yb, double c, int mode) {
   const Lane L = lane_map<R>(d);
@@ -2914,25 +3036,8 @@ __global__ __launch_bounds__(BLOCK) void k_accel(Dev d, double* V, double* Yb, d
   double m[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) m[k] = (mode == 0) ? (1.0 - c) * x[k] + c * v[k] : v[k] + c * (x[k] - y[k]);
-  double G[9], W[9];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = i; j < 3; ++j) {
-      const double g = gsum<R>(m[i] * m[j], L.base);
-      G[i * 3 + j] = g;
-      G[j * 3 + i] = g;
-    }
-  jacobi3(G, W);
-  double isq[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) isq[k] = 1.0 / sqrt(G[k * 4]);
-  double cc[3], out[4];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) cc[k] = (m[0] * W[0 * 3 + k] + m[1] * W[1 * 3 + k] + m[2] * W[2 * 3 + k]) * isq[k];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) out[j] = cc[0] * W[j * 3 + 0] + cc[1] * W[j * 3 + 1] + cc[2] * W[j * 3 + 2];
-  out[3] = m[3];
+  double out[4];
+  group_project<R>(m, L.a, L.base, L.pw < 64 / R, out);
   if (!L.valid) return;
   if (mode == 0) {
     store4(Yb + o, out);
@@ -2965,6 +3070,9 @@ __global__ __launch_bounds__(BLOCK, LB<R>::w) void k_eval(Dev d, int robot, int 
   } else if (mode == KMX_EVAL_EHESS) {
     hinc_gather<R, RW>(d, L, V, res, smem);
     if (L.valid) load4(V + o, v);
+  } else if (mode == KMX_EVAL_PROJECT) {
+    if (L.valid) load4(V + o, v);
+    group_project<R>(v, L.a, L.base, L.pw < 64 / R, res);
   } else {
     double y[4] = {0, 0, 0, 0}, G[4], c0 = 0.0;
     hinc_grad<R, RW>(d, L, d.X, d.pub, G, &c0, smem);
@@ -4674,7 +4782,7 @@ extern "C" int kmx_pgo_get_trajectory(kmx_pgo* h, int robot, const double* ancho
 extern "C" int kmx_pgo_eval(kmx_pgo* h, int robot, int mode, const double* V, double* out, double* scalar) {
   KMX_GUARD_BEGIN
   if (int rc = check_robot(h, robot)) return rc;
-  KMX_CHECK(mode >= KMX_EVAL_COST_EGRAD && mode <= KMX_EVAL_RETRACT, KMX_EINVAL, "bad eval mode");
+  KMX_CHECK(mode >= KMX_EVAL_COST_EGRAD && mode <= KMX_EVAL_PROJECT, KMX_EINVAL, "bad eval mode");
   KMX_CHECK(out && (V || mode == KMX_EVAL_RGRAD), KMX_EINVAL, "null argument");
   KMX_HIP(hipSetDevice(h->device));
   const int ps = 4 * h->P.r, l = h->local_of[robot], n = h->npose[robot];

@@ -30,6 +30,7 @@ KMX_EVAL_RGRAD = 2
 KMX_EVAL_RHESS = 3
 KMX_EVAL_PRECON = 4
 KMX_EVAL_RETRACT = 5
+KMX_EVAL_PROJECT = 6
 KMX_NORM_L1 = 0
 KMX_NORM_HAMMING = 1
 KMX_RNG_GCC9 = 0

@@ -778,25 +778,111 @@ static void block_update(orc_pgo* h, int a, kmx_iter_stats* st, int inner) {
  *   X'     = block update from Y
  *   V      = Proj(V + gamma' (X' - Y))
  * and every restart_interval rounds V = X', gamma = 0 (else gamma = gamma').
- * Proj: the rotation block to the Stiefel manifold by its polar factor
- * M (M^T M)^(-1/2) (the SVD's U V^T), translation unchanged. */
-static void jacobi3(double A[9], double V[9]);
-static void proj_stiefel(int r, const double* M, double* out) {
-  double G[9], W[9];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      double s = 0.0;
-      for (int a = 0; a < r; ++a) s += M[4 * a + i] * M[4 * a + j];
-      G[i * 3 + j] = s;
+ * Proj: the rotation block to the Stiefel manifold by its polar factor (the
+ * SVD's U V^T), translation unchanged. One-sided Jacobi: plane rotations W
+ * turn the columns of A = M W orthogonal, Y = sum_k (A_k / |A_k|) W_k^T. The
+ * block is never squared and no vanishing singular value is divided by: a
+ * column that is zero, or that one Gram-Schmidt step against the larger
+ * columns' directions takes more than half of, is replaced by a completion of
+ * the frame, so Y always has orthonormal columns (the zero block: e1 e2 e3). */
+
+/* a unit r-vector orthogonal to the nk orthonormal columns of u (r x 3): the
+ * e_k they are least along (the first such k), two Gram-Schmidt passes */
+static void stiefel_complete(int r, const double* u, int nk, double* w) {
+  int kb = 0;
+  double best = 0.0;
+  for (int k = 0; k < r; ++k) {
+    double q = 0.0;
+    for (int j = 0; j < nk; ++j) q += u[3 * k + j] * u[3 * k + j];
+    if (k == 0 || q < best) {
+      best = q;
+      kb = k;
     }
-  jacobi3(G, W);
-  double isq[3];
-  for (int k = 0; k < 3; ++k) isq[k] = 1.0 / sqrt(G[k * 4]);
+  }
+  for (int k = 0; k < r; ++k) w[k] = (k == kb) ? 1.0 : 0.0;
+  for (int pass = 0; pass < 2; ++pass)
+    for (int j = 0; j < nk; ++j) {
+      double dot = 0.0;
+      for (int k = 0; k < r; ++k) dot += u[3 * k + j] * w[k];
+      for (int k = 0; k < r; ++k) w[k] -= dot * u[3 * k + j];
+    }
+  double nn = 0.0;
+  for (int k = 0; k < r; ++k) nn += w[k] * w[k];
+  nn = sqrt(nn);
+  for (int k = 0; k < r; ++k) w[k] /= nn;
+}
+
+static void proj_stiefel(int r, const double* M, double* out) {
+  double A[8 * 3], W[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, u[8 * 3], t[8], w[8];
+  double amax = 0.0, fin = 0.0;
   for (int a = 0; a < r; ++a) {
-    double c[3];
-    for (int k = 0; k < 3; ++k)
-      c[k] = (M[4 * a + 0] * W[0 * 3 + k] + M[4 * a + 1] * W[1 * 3 + k] + M[4 * a + 2] * W[2 * 3 + k]) * isq[k];
-    for (int j = 0; j < 3; ++j) out[4 * a + j] = c[0] * W[j * 3 + 0] + c[1] * W[j * 3 + 1] + c[2] * W[j * 3 + 2];
+    for (int c = 0; c < 3; ++c) amax = fmax(amax, fabs(M[4 * a + c]));
+    fin += (M[4 * a + 0] + M[4 * a + 1] + M[4 * a + 2]) * 0.0;
+  }
+  const int ok = fin == 0.0 && amax > 0.0 && amax < INFINITY;
+  for (int a = 0; a < r; ++a)
+    for (int c = 0; c < 3; ++c) A[3 * a + c] = ok ? M[4 * a + c] / amax : 0.0;
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    int rotated = 0;
+    for (int i = 0; i < 2; ++i)
+      for (int j = i + 1; j < 3; ++j) {
+        double aii = 0.0, ajj = 0.0, aij = 0.0;
+        for (int a = 0; a < r; ++a) aii += A[3 * a + i] * A[3 * a + i];
+        for (int a = 0; a < r; ++a) ajj += A[3 * a + j] * A[3 * a + j];
+        for (int a = 0; a < r; ++a) aij += A[3 * a + i] * A[3 * a + j];
+        /* orthogonal to 4 eps: below it a rotation only moves rounding noise about */
+        if (fabs(aij) <= 0x1p-50 * sqrt(aii * ajj) || aij == 0.0 || !(fabs(aij) < INFINITY)) continue;
+        rotated = 1;
+        const double zeta = (ajj - aii) / (2.0 * aij);
+        const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+        const double cs = 1.0 / sqrt(1.0 + tt * tt), sn = cs * tt;
+        for (int a = 0; a < r; ++a) {
+          const double ai = A[3 * a + i], aj = A[3 * a + j];
+          A[3 * a + i] = cs * ai - sn * aj;
+          A[3 * a + j] = sn * ai + cs * aj;
+        }
+        for (int q = 0; q < 3; ++q) {
+          const double vi = W[3 * q + i], vj = W[3 * q + j];
+          W[3 * q + i] = cs * vi - sn * vj;
+          W[3 * q + j] = sn * vi + cs * vj;
+        }
+      }
+    if (!rotated) break;
+  }
+  double s2[3] = {0.0, 0.0, 0.0};
+  for (int c = 0; c < 3; ++c)
+    for (int a = 0; a < r; ++a) s2[c] += A[3 * a + c] * A[3 * a + c];
+  int c1 = 0;
+  if (s2[1] > s2[0]) c1 = 1;
+  if (s2[2] > fmax(s2[0], s2[1])) c1 = 2;
+  int c2 = c1 == 0 ? 1 : 0, c3 = c1 == 2 ? 1 : 2;
+  if (s2[c3] > s2[c2]) {
+    const int tmp = c2;
+    c2 = c3;
+    c3 = tmp;
+  }
+  const int col[3] = {c1, c2, c3};
+  for (int a = 0; a < r; ++a) u[3 * a + 0] = s2[c1] > 0.0 ? A[3 * a + c1] / sqrt(s2[c1]) : (a == 0 ? 1.0 : 0.0);
+  for (int k = 1; k < 3; ++k) { /* one Gram-Schmidt step against the directions before it */
+    const double s = s2[col[k]];
+    for (int a = 0; a < r; ++a) t[a] = s > 1e-280 ? A[3 * a + col[k]] / sqrt(s) : 0.0;
+    for (int j = 0; j < k; ++j) {
+      double dot = 0.0;
+      for (int a = 0; a < r; ++a) dot += u[3 * a + j] * t[a];
+      for (int a = 0; a < r; ++a) t[a] -= dot * u[3 * a + j];
+    }
+    double nn = 0.0;
+    for (int a = 0; a < r; ++a) nn += t[a] * t[a];
+    if (nn >= 0.5) {
+      for (int a = 0; a < r; ++a) u[3 * a + k] = t[a] / sqrt(nn);
+    } else {
+      stiefel_complete(r, u, k, w);
+      for (int a = 0; a < r; ++a) u[3 * a + k] = w[a];
+    }
+  }
+  for (int a = 0; a < r; ++a) {
+    for (int j = 0; j < 3; ++j)
+      out[4 * a + j] = u[3 * a + 0] * W[3 * j + c1] + u[3 * a + 1] * W[3 * j + c2] + u[3 * a + 2] * W[3 * j + c3];
     out[4 * a + 3] = M[4 * a + 3];
   }
 }
@@ -1016,59 +1102,116 @@ int orc_pgo_update_weights_local(void* vh, const uint8_t* local, double* mu_used
 }
 
 /* ------------------------------------------------------------ rounding -- */
-/* symmetric 3x3 Jacobi eigen-decomposition (cyclic, fixed sweeps) */
-static void jacobi3(double A[9], double V[9]) {
-  for (int i = 0; i < 9; ++i) V[i] = (i % 4 == 0) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 12; ++sweep) {
-    for (int p = 0; p < 2; ++p)
-      for (int q = p + 1; q < 3; ++q) {
-        const double apq = A[p * 3 + q];
-        if (apq == 0.0) continue;
-        const double app = A[p * 3 + p], aqq = A[q * 3 + q];
-        const double theta = (aqq - app) / (2.0 * apq);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
-        for (int k = 0; k < 3; ++k) { /* A = J^T A J */
-          const double akp = A[k * 3 + p], akq = A[k * 3 + q];
-          A[k * 3 + p] = cs * akp - sn * akq;
-          A[k * 3 + q] = sn * akp + cs * akq;
-        }
-        for (int k = 0; k < 3; ++k) {
-          const double apk = A[p * 3 + k], aqk = A[q * 3 + k];
-          A[p * 3 + k] = cs * apk - sn * aqk;
-          A[q * 3 + k] = sn * apk + cs * aqk;
-        }
-        for (int k = 0; k < 3; ++k) {
-          const double vkp = V[k * 3 + p], vkq = V[k * 3 + q];
-          V[k * 3 + p] = cs * vkp - sn * vkq;
-          V[k * 3 + q] = sn * vkp + cs * vkq;
-        }
-      }
-  }
+static void cross3(const double* a, const double* b, double* c) {
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-/* nearest rotation: R = U diag(1,1,sign det M) V^T via M^T M = V L V^T */
-static void proj_so3(const double M[9], double Rout[9]) {
-  double A[9], V[9];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      double s = 0.0;
-      for (int k = 0; k < 3; ++k) s += M[k * 3 + i] * M[k * 3 + j];
-      A[i * 3 + j] = s;
-    }
-  jacobi3(A, V);
-  const double det = M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
-  int kmin = 0;
-  for (int k = 1; k < 3; ++k) if (A[k * 4] < A[kmin * 4]) kmin = k;
-  for (int i = 0; i < 9; ++i) Rout[i] = 0.0;
+/* a unit vector orthogonal to the unit vector u: the axis u is least along, made orthogonal */
+static void any_orthogonal3(const double* u, double* v) {
+  int e = 0;
+  if (fabs(u[1]) < fabs(u[e])) e = 1;
+  if (fabs(u[2]) < fabs(u[e])) e = 2;
+  double w[3] = {0.0, 0.0, 0.0};
+  w[e] = 1.0;
+  const double dot = u[e];
+  double nn = 0.0;
   for (int k = 0; k < 3; ++k) {
-    const double sig = sqrt(fmax(A[k * 4], 0.0));
-    double u[3];
-    for (int i = 0; i < 3; ++i) u[i] = (M[i * 3 + 0] * V[0 * 3 + k] + M[i * 3 + 1] * V[1 * 3 + k] + M[i * 3 + 2] * V[2 * 3 + k]) / sig;
-    const double s = (k == kmin && det < 0.0) ? -1.0 : 1.0;
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) Rout[i * 3 + j] += s * u[i] * V[j * 3 + k];
+    w[k] -= dot * u[k];
+    nn += w[k] * w[k];
   }
+  nn = sqrt(nn);
+  for (int k = 0; k < 3; ++k) v[k] = w[k] / nn;
+}
+
+/* v orthogonal to the unit vector u, and unit (one Gram-Schmidt step) */
+static void orthonormalize3(const double* u, double* v) {
+  double dot = 0.0, nn = 0.0;
+  for (int k = 0; k < 3; ++k) dot += u[k] * v[k];
+  for (int k = 0; k < 3; ++k) {
+    v[k] -= dot * u[k];
+    nn += v[k] * v[k];
+  }
+  nn = sqrt(nn);
+  for (int k = 0; k < 3; ++k) v[k] /= nn;
+}
+
+/* nearest rotation: R = U diag(1,1,sign det M) V^T. One-sided Jacobi turns the
+ * columns of A = M V orthogonal; with u1, u2 and v1, v2 the directions of the
+ * two largest singular values, R = u1 v1^T + u2 v2^T + (u1 x u2)(v1 x v2)^T:
+ * M is not squared and the smallest singular value is never divided by. A
+ * block of rank < 2 has its missing directions completed to a rotation (the
+ * zero block gives I). */
+static void proj_so3(const double M[9], double Rout[9]) {
+  double A[3][3], Vm[3][3];
+  double amax = 0.0;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) {
+      A[r][c] = M[3 * r + c];
+      Vm[r][c] = r == c ? 1.0 : 0.0;
+      amax = fmax(amax, fabs(A[r][c]));
+      Rout[3 * r + c] = r == c ? 1.0 : 0.0;
+    }
+  if (!(amax > 0.0 && amax < INFINITY)) return;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) A[r][c] /= amax;
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    int rotated = 0;
+    for (int i = 0; i < 2; ++i)
+      for (int j = i + 1; j < 3; ++j) {
+        double aii = 0.0, ajj = 0.0, aij = 0.0;
+        for (int r = 0; r < 3; ++r) {
+          aii += A[r][i] * A[r][i];
+          ajj += A[r][j] * A[r][j];
+          aij += A[r][i] * A[r][j];
+        }
+        if (fabs(aij) <= 1e-17 * sqrt(aii * ajj) || aij == 0.0) continue;
+        rotated = 1;
+        const double zeta = (ajj - aii) / (2.0 * aij);
+        const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+        const double cs = 1.0 / sqrt(1.0 + tt * tt), sn = cs * tt;
+        for (int r = 0; r < 3; ++r) {
+          const double ai = A[r][i], aj = A[r][j];
+          A[r][i] = cs * ai - sn * aj;
+          A[r][j] = sn * ai + cs * aj;
+          const double vi = Vm[r][i], vj = Vm[r][j];
+          Vm[r][i] = cs * vi - sn * vj;
+          Vm[r][j] = sn * vi + cs * vj;
+        }
+      }
+    if (!rotated) break;
+  }
+  double s2[3];
+  for (int c = 0; c < 3; ++c) s2[c] = A[0][c] * A[0][c] + A[1][c] * A[1][c] + A[2][c] * A[2][c];
+  int c1 = 0;
+  if (s2[1] > s2[c1]) c1 = 1;
+  if (s2[2] > s2[c1]) c1 = 2;
+  int c2 = c1 == 0 ? 1 : 0;
+  for (int c = 0; c < 3; ++c)
+    if (c != c1 && s2[c] > s2[c2]) c2 = c;
+  double u1[3], u2[3], u3[3], v1[3], v2[3], v3[3];
+  const double n1 = sqrt(s2[c1]);
+  for (int r = 0; r < 3; ++r) {
+    u1[r] = A[r][c1] / n1;
+    v1[r] = Vm[r][c1];
+  }
+  if (s2[c2] > 1e-280) {
+    const double n2 = sqrt(s2[c2]);
+    for (int r = 0; r < 3; ++r) {
+      u2[r] = A[r][c2] / n2;
+      v2[r] = Vm[r][c2];
+    }
+    orthonormalize3(u1, u2);
+    orthonormalize3(v1, v2);
+  } else {
+    any_orthogonal3(u1, u2);
+    any_orthogonal3(v1, v2);
+  }
+  cross3(u1, u2, u3);
+  cross3(v1, v2, v3);
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) Rout[3 * r + c] = u1[r] * v1[c] + u2[r] * v2[c] + u3[r] * v3[c];
 }
 
 int orc_pgo_get_trajectory(void* vh, int a, const double* anchor, double* out) {
@@ -1109,6 +1252,9 @@ int orc_pgo_eval(void* vh, int a, int mode, const double* V, double* out, double
     s = edge_eval(&b, V, 1, out);
   } else if (mode == KMX_EVAL_EHESS) {
     edge_eval(&b, V, 0, out);
+    s = dot(V, out, N);
+  } else if (mode == KMX_EVAL_PROJECT) {
+    for (int i = 0; i < b.n; ++i) proj_stiefel(b.r, V + (int64_t)i * b.ps, out + (int64_t)i * b.ps);
     s = dot(V, out, N);
   } else {
     edge_eval(&b, c.Xb, 1, c.eg);

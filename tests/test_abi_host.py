@@ -20,6 +20,17 @@ def test_library_exports_every_header_symbol():
     assert L.kmx_abi_version() == abi.ABI_VERSION
 
 
+def test_eval_modes_match_the_header():
+    """kmx_pgo_eval's modes, KMX_EVAL_PROJECT (additive to ABI 10) included."""
+    from kmx import abi
+    hdr = (ROOT / "include" / "kmx_abi.h").read_text()
+    modes = {n: int(v) for n, v in re.findall(r"#define\s+(KMX_EVAL_\w+)\s+(\d+)", hdr)}
+    assert sorted(modes.values()) == list(range(7)) and modes["KMX_EVAL_PROJECT"] == 6
+    for n, v in modes.items():
+        assert getattr(abi, n) == v, n
+    assert int(re.search(r"#define\s+KMX_ABI_VERSION\s+(\d+)", hdr).group(1)) == abi.ABI_VERSION == 10
+
+
 def test_runtime_info_names_the_rccl_serving_kmx():
     """which librccl / libamdhip64 libkmx's own calls resolve
     to (dladdr inside the library), their versions, and every copy mapped into
