@@ -1014,7 +1014,9 @@ int kmx_chordal_get_robust_stats(kmx_chordal* h, double* out /* [8] */);
  * 64 poses, one wave over the tile partials): two calls give the same bits. */
 typedef struct kmx_cert kmx_cert;
 #define KMX_CERT_UNDECIDED 0 /* max_steps reached (a result, not an error)          */
-#define KMX_CERT_CERTIFIED 1 /* rho <= eta and theta_min - rho >= -eta               */
+#define KMX_CERT_CERTIFIED 1 /* rho <= eta / 10 and theta_min - rho >= -eta: an
+                                eigenvalue lies within rho of theta_min, the smallest
+                                the Krylov space shows (no bound of lambda_min)      */
 #define KMX_CERT_NEGATIVE 2  /* theta_min < -eta: S has an eigenvalue below -eta     */
 typedef struct {
   double eta;          /* > 0, required: the tolerance of the decision              */

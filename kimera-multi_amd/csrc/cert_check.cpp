@@ -181,8 +181,9 @@ int check_tridiag(std::mt19937& rng, int k, double shift) {
     if (i != imin) gap = std::min(gap, ev[i] - ev[imin]);
   if (gap > 1e-3) ok = ok && std::fabs(res.residual - rho) <= 1e-11 * scale / gap;
   const int want = res.theta_min < -eta ? KMX_CERT_NEGATIVE
-                   : (res.residual <= eta && res.theta_min - res.residual >= -eta) ? KMX_CERT_CERTIFIED
-                                                                                    : KMX_CERT_UNDECIDED;
+                   : (res.residual <= kmx::CT_RESIDUAL_FACTOR * eta && res.theta_min - res.residual >= -eta)
+                       ? KMX_CERT_CERTIFIED
+                       : KMX_CERT_UNDECIDED;
   ok = ok && res.decision == want;
   if (!ok) {
     std::fprintf(stderr, "tridiagonal k=%d: theta %.17g / %.17g vs %.17g / %.17g, rho %.3e vs %.3e, decision %d\n", k,
@@ -311,6 +312,16 @@ int main() {
         kmx::cert_ritz(0, a, b, 1.0, &r3, nullptr, &err) != KMX_EINVAL ||
         kmx::cert_ritz(1, a, nan_b, 1.0, &r3, nullptr, &err) != KMX_EINVAL) {
       std::fprintf(stderr, "cert_ritz: invariant subspace / bad arguments\n");
+      ++g_fail;
+    }
+    // the residual factor: one step has s = (1) and rho = beta_1, so eta = 1 certifies up to rho = 1/10
+    const double one[1] = {1.0}, b_in[1] = {kmx::CT_RESIDUAL_FACTOR}, b_out[1] = {2.0 * kmx::CT_RESIDUAL_FACTOR};
+    const double low[1] = {-0.95};  // theta_min - rho < -eta at rho = 1/10
+    if (kmx::cert_ritz(1, one, b_in, 1.0, &r1, nullptr, &err) != KMX_OK || r1.decision != KMX_CERT_CERTIFIED ||
+        kmx::cert_ritz(1, one, b_out, 1.0, &r2, nullptr, &err) != KMX_OK || r2.decision != KMX_CERT_UNDECIDED ||
+        r2.residual != b_out[0] || kmx::cert_ritz(1, low, b_in, 1.0, &r3, nullptr, &err) != KMX_OK ||
+        r3.decision != KMX_CERT_UNDECIDED) {
+      std::fprintf(stderr, "cert_ritz: the residual factor\n");
       ++g_fail;
     }
     // the zero matrix (a pose without edges): certified at once

@@ -103,6 +103,21 @@ def test_ritz_reaches_all_three_decisions(tridiagonals):
     assert one["decision"] == "CERTIFIED" and one["residual"] == 0.0
 
 
+def test_ritz_certifies_only_below_a_tenth_of_eta():
+    """One step has s = (1) and rho = beta_1: CERTIFIED needs rho <= CERT_C eta
+    (and theta_min - rho >= -eta as before), in the library, in the restatement
+    and in the header's words."""
+    from kmx.dpgo.certify import ritz
+    assert CR.CERT_C == 0.1
+    for a, b, want in ((1.0, 0.1, "CERTIFIED"), (1.0, 0.1000001, "UNDECIDED"), (1.0, 0.9, "UNDECIDED"),
+                       (-0.95, 0.1, "UNDECIDED"), (-0.5, 0.1, "CERTIFIED"), (-1.01, 0.0, "NEGATIVE")):
+        got, ref = ritz(np.array([a]), np.array([b]), 1.0), CR.ritz(np.array([a]), np.array([b]), 1.0)
+        assert got["decision"] == ref["decision"] == want, (a, b, got, ref)
+        assert got["residual"] == b and got["theta_min"] == a
+    hdr = (ROOT / "include" / "kmx_abi.h").read_text()
+    assert re.search(r"#define\s+KMX_CERT_CERTIFIED\s+1\s*/\*\s*rho <= eta / 10 and theta_min - rho >= -eta", hdr)
+
+
 @pytest.mark.parametrize("eta", [0.0, -1e-5, float("nan"), float("inf")])
 def test_ritz_refuses_bad_eta(eta):
     import ctypes as C
