@@ -105,6 +105,44 @@ struct HipPinned {
 template <class T>
 using PinnedBuf = BasicDevBuf<T, HipPinned>;
 
+// Pinned host memory the device reads and writes in place (mapped, coherent).
+// A failed allocation is KMX_EHIP, as where the handles made these by hand.
+struct HipMapped {
+  using stream_t = hipStream_t;
+  static int alloc(void** p, size_t bytes) {
+    const hipError_t e = hipHostMalloc(p, bytes, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess) return 0;
+    *p = nullptr;
+    return fail(KMX_EHIP, std::string("hipHostMalloc: ") + hipGetErrorString(e));
+  }
+  static void free(void* p) { (void)hipHostFree(p); }
+};
+template <class T>
+using MappedBuf = BasicDevBuf<T, HipMapped>;  // kernels that take the host pointer itself use this alone
+
+// A mapped buffer with its device pointer, looked up once per allocation:
+// host() for the CPU, dev() for kernel arguments, cap() in elements.
+template <class T>
+class Mapped {
+ public:
+  int alloc(size_t count) {
+    MappedBuf<T> q;
+    void* d = nullptr;
+    if (int rc = q.alloc(count)) return rc;
+    KMX_HIP(hipHostGetDevicePointer(&d, q.get(), 0));
+    buf_ = std::move(q);
+    dev_ = static_cast<T*>(d);
+    return 0;
+  }
+  T* host() const { return buf_.get(); }
+  T* dev() const { return buf_.get() ? dev_ : nullptr; }
+  size_t cap() const { return buf_.cap(); }
+
+ private:
+  MappedBuf<T> buf_;
+  T* dev_ = nullptr;
+};
+
 // What every handle begins with. A handle derives from it, so the stream is
 // made before the handle's buffers and events and destroyed after them.
 struct StreamCore {
@@ -157,6 +195,27 @@ int destroy(H* h) {
   return KMX_OK;
 }
 
+// One owned non-blocking side stream (null until create), beside the handle's own in StreamCore.
+class Stream {
+ public:
+  Stream() = default;
+  Stream(Stream&& o) noexcept : s_(o.s_) { o.s_ = nullptr; }
+  Stream& operator=(Stream&&) = delete;
+  ~Stream() {
+    if (s_) (void)hipStreamDestroy(s_);
+  }
+  int create() {
+    const hipError_t e = hipStreamCreateWithFlags(&s_, hipStreamNonBlocking);
+    if (e == hipSuccess) return 0;
+    s_ = nullptr;
+    return fail(KMX_EHIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+  }
+  operator hipStream_t() const { return s_; }
+
+ private:
+  hipStream_t s_ = nullptr;
+};
+
 // One owned event (null until create); arrays and vectors of it replace the create / destroy loops.
 class Event {
  public:
@@ -167,6 +226,7 @@ class Event {
     if (e_) (void)hipEventDestroy(e_);
   }
   int create(unsigned flags = hipEventDefault) {
+    if (e_) return 0;  // (a retry after a create_events that failed part-way)
     if (hipEventCreateWithFlags(&e_, flags) == hipSuccess) return 0;
     e_ = nullptr;
     return fail(KMX_EHIP, "hipEventCreate failed");

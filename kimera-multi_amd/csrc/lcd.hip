@@ -30,6 +30,7 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
+#include <memory>
 #include <random>
 #include <thread>
 #include <string>
@@ -3402,73 +3403,79 @@ __global__ __launch_bounds__(RS_BLOCK) void k_recover(const double* bearings, co
 }  // namespace
 
 // ============================================================== handle ====
-struct kmx_lcd {
+struct kmx_lcd : kmx::StreamCore {
+  template <class T>
+  using DevBuf = kmx::DevBuf<T>;
   kmx_lcd_params P{};
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  // frame pool: F resident frames of N feature slots, device capacity capF frames
-  int F = 0, N = 0, capF = 0;
-  std::vector<int> h_nfeat;  // host copy of the feature counts (argument checks)
-  uint32_t* d_desc = nullptr;
-  double* d_bear = nullptr;
-  double* d_pts = nullptr;
-  int* d_nfeat = nullptr;
-  // sampler tables, built for rows K in [S, table_N] (they depend only on the
-  // parameters and N, so frames can be added without rebuilding them)
-  short* d_table = nullptr;
-  short* d_table_rec = nullptr;  // samples of the recovery RANSAC (6: PnP, 3: Arun), built when used
-  int table_N = 0;
-  int pmax = 0;
+  // Side streams and events stand before the buffers: the buffers are
+  // destroyed first, then these, then the base's stream.
+  kmx::Stream kstream;  // kNN2 of kmx_lcd_verify / _async
+  kmx::Event ev[3];     // kmx_lcd_enable_timing: around the kNN2 and the RANSAC launches (made on first use)
   // candidate buffers: LCD_SLOTS slots, used by successive calls in turn, so
   // a call's kNN2 (on kstream) can run while earlier calls' RANSACs drain.
   // A slot owns its buffers; slot[cur] is the current call's.
   struct SlotBuffers {
-    int *cq = nullptr, *cm = nullptr, *K = nullptr;
-    int *hyps = nullptr, *nrec = nullptr;  // ordered sampler: the passes each problem drew, recovery sizes
-    int* order = nullptr;                  // k_order's queue order (KMX_LCD_ORDER)
-    int2* pairs = nullptr;
-    kmx_lcd_result* res = nullptr;
-    unsigned char* mask = nullptr;
-    double* prior = nullptr;  // T_prior rows (kmx_lcd_verify_matches)
-    double* fbuf = nullptr;   // [waves][6 N + STASH] compact match bearings + Stewenius stash, per k_ransac_coop wave
-    int* next = nullptr;      // k_ransac_coop's work-queue counter
-    int cap = 0;              // candidates the slot's buffers hold (0: not allocated yet)
+    DevBuf<int> cq, cm, K;
+    DevBuf<int> hyps, nrec;  // ordered sampler: the passes each problem drew, recovery sizes
+    DevBuf<int> order;       // k_order's queue order (KMX_LCD_ORDER)
+    DevBuf<int2> pairs;
+    DevBuf<kmx_lcd_result> res;
+    DevBuf<unsigned char> mask;
+    DevBuf<double> prior;  // T_prior rows (kmx_lcd_verify_matches)
+    DevBuf<double> fbuf;   // [waves][6 N + STASH] compact match bearings + Stewenius stash, per k_ransac_coop wave
+    DevBuf<int> next;      // k_ransac_coop's work-queue counter
+    int cap = 0;           // candidates the slot's buffers hold (0: not allocated yet), set once all have grown
   };
   // Each slot's RANSAC can run on its own stream (slot 0: the handle's
   // stream, slot s > 0: its rsx) with its own work-queue counter and per-wave
   // scratch, so the next calls' RANSACs take the CUs the previous call's
   // drain (its last candidates, finishing alone) leaves idle. The stream and
   // the events live as long as the handle; the buffers come and go (slot_free).
-  struct Slot : SlotBuffers {
-    hipStream_t rsx = nullptr;                    // the slot's RANSAC stream (slots > 0)
-    hipEvent_t ev_knn = nullptr, ev_rs = nullptr;  // its kNN2 is done; its last work is done
+  struct SlotSync {
+    kmx::Stream rsx;            // the slot's RANSAC stream (slots > 0)
+    kmx::Event ev_knn, ev_rs;  // its kNN2 is done; its last work is done
     bool ev_rs_set = false;
+  };
+  struct Slot : SlotSync, SlotBuffers {  // (bases go in reverse: the buffers before the stream)
   } slot[LCD_SLOTS];
   int cur = 0;
   bool rs_conc = true;    // KMX_LCD_RSX=0: every slot on the handle's stream (A/B switch)
   bool rs_small = false;  // this call runs its slots' RANSACs concurrently (the size cut)
   bool rs_on = false;     // this call's slot runs on its rsx
   int cus = 0;
-  hipStream_t kstream = nullptr;  // kNN2 of kmx_lcd_verify / _async
+  // frame pool: F resident frames of N feature slots, device capacity capF frames
+  int F = 0, N = 0, capF = 0;
+  std::vector<int> h_nfeat;  // host copy of the feature counts (argument checks)
+  struct Pool {
+    DevBuf<uint32_t> desc;
+    DevBuf<double> bear, pts;
+    DevBuf<int> nfeat;
+  } pool;
+  // sampler tables, built for rows K in [S, table_N] (they depend only on the
+  // parameters and N, so frames can be added without rebuilding them)
+  struct Tables {
+    DevBuf<short> table;
+    DevBuf<short> rec;  // samples of the recovery RANSAC (6: PnP, 3: Arun), built when used
+  } tab;
+  int table_N = 0;
+  int pmax = 0;
   // ordered sampler (rng_stream 1): the verification thread's engine, one
   // candidate's sample row
   std::mt19937 stream_rng;
-  short* d_row = nullptr;
+  DevBuf<short> d_row;
   // spread form (synchronous calls of <= spread_max candidates; lcd.hip k_rs_*)
   int spread_max = 8;
-  int spread_cap = 0;
-  RsState* d_st = nullptr;
-  HypOut* d_hout = nullptr;
-  double* d_sfbuf = nullptr;
-  unsigned* d_more = nullptr;  // [more_cap] one word per range: some candidate needs the next range
-  unsigned* d_hcnt = nullptr;  // [spread_cap] k_rs_hyps' wave arrivals per candidate (zero between ranges)
-  int more_cap = 0;
-  unsigned* h_more = nullptr;  // pinned copy of the word just read
-  unsigned* z_more = nullptr;  // its device pointer (looked up once)
+  int spread_cap = 0;  // candidates the spread set holds, set once all four have grown
+  struct Spread {
+    DevBuf<RsState> st;
+    DevBuf<HypOut> hout;
+    DevBuf<double> sfbuf;
+    DevBuf<unsigned> hcnt;  // [spread_cap] k_rs_hyps' wave arrivals per candidate (zero between ranges)
+  } spread;
+  DevBuf<unsigned> d_more;     // one word per range: some candidate needs the next range
+  kmx::Mapped<unsigned> more;  // pinned copy of the word just read, and its device pointer
   // a one-candidate call's completion word (mapped; wait_done) and its sequence
-  unsigned* h_done = nullptr;
-  unsigned* z_done = nullptr;
+  kmx::Mapped<unsigned> done;
   unsigned done_seq = 0;
   bool spin_wait = true;  // KMX_LCD_SPINWAIT=0: hipStreamSynchronize instead
   // k_knn2s (synchronous calls of <= KS_MAX candidates): per-query results and
@@ -3480,29 +3487,25 @@ struct kmx_lcd {
   // two-wave candidates run five waves per SIMD instead of eight, and the
   // v_sad_u8 chains need them). KMX_LCD_KNNQ=0: k_knn2 for both.
   bool knn_q = true;
-  int* d_kqb = nullptr;
-  unsigned* d_kcnt = nullptr;
-  int kqb_N = 0;
+  struct KnnSplit {
+    DevBuf<int> kqb;
+    DevBuf<unsigned> kcnt;
+  } ks;
+  int kqb_N = 0;  // the N kqb was sized for
   // pinned staging of the synchronous one-candidate calls (kmx_lcd_match,
   // kmx_lcd_verify_matches): every input in one host-to-device copy, every
   // output through pinned memory (a pageable copy is a blocking staged copy
   // each; the call-for-call chain made five to seven of them per call)
-  size_t io_cap = 0;
   // small frame uploads (add_frames: one keyframe per call) are staged here
   // (pinned, mapped) and scattered into the pool by one kernel that reads the
   // mapped pages, instead of four pageable copies
-  char* h_fst = nullptr;
-  char* z_fst = nullptr;
-  size_t fst_cap = 0;
-  char* h_io = nullptr;  // pinned host, coherent and mapped
-  char* z_io = nullptr;  // h_io's device pointer: the small synchronous calls' kernels read their
-                         // inputs and write their outputs there (zero-copy: no blit per copy)
-  char* d_io = nullptr;
+  kmx::Mapped<char> fst;
+  // io.dev(): the small synchronous calls' kernels read their inputs and write
+  // their outputs there (zero-copy: no blit per copy); d_io holds as much
+  kmx::Mapped<char> io;
+  DevBuf<char> d_io;
   int prof = 0;              // KMX_RS_PROF: phase timers in k_ransac_coop
-  // kmx_lcd_enable_timing: events around the kNN2 and the RANSAC launches
   bool timing = false;
-  bool ev_ok = false;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
 };
 
 namespace {
@@ -3525,58 +3528,37 @@ hipError_t sync_all(kmx_lcd* h) {
 }
 void lcd_free_frames(kmx_lcd* h) {
   (void)sync_all(h);  // a verification in flight may read the pool
-  void* p[] = {h->d_desc, h->d_bear, h->d_pts, h->d_nfeat};
-  for (void* x : p)
-    if (x) (void)hipFree(x);
-  h->d_desc = nullptr; h->d_bear = h->d_pts = nullptr; h->d_nfeat = nullptr;
+  h->pool = {};
   h->F = h->capF = 0;
   h->h_nfeat.clear();
-}
-void lcd_free_tables(kmx_lcd* h) {
-  if (h->d_table) (void)hipFree(h->d_table);
-  if (h->d_table_rec) (void)hipFree(h->d_table_rec);
-  h->d_table = h->d_table_rec = nullptr;
-  h->table_N = 0;
 }
 // The slot's buffers (the caller has waited for the work that uses them);
 // its stream and events stay.
 void slot_free(Slot& sl) {
-  void* p[] = {sl.cq, sl.cm, sl.K, sl.hyps, sl.nrec, sl.order, sl.pairs, sl.res, sl.mask, sl.prior, sl.fbuf, sl.next};
-  for (void* x : p)
-    if (x) (void)hipFree(x);
   static_cast<kmx_lcd::SlotBuffers&>(sl) = kmx_lcd::SlotBuffers{};
   sl.ev_rs_set = false;
 }
 void lcd_free_cand(kmx_lcd* h) {
   (void)sync_all(h);  // in-flight calls may still use the buffers
   for (Slot& sl : h->slot) slot_free(sl);
-  void* q[] = {h->d_st, h->d_hout, h->d_sfbuf, h->d_more, h->d_kqb, h->d_kcnt, h->d_hcnt};
-  for (void* x : q)
-    if (x) (void)hipFree(x);
-  if (h->h_more) (void)hipHostFree(h->h_more);
-  h->d_st = nullptr; h->d_hout = nullptr; h->d_sfbuf = nullptr; h->d_more = nullptr; h->h_more = nullptr; h->z_more = nullptr;
-  h->d_kqb = nullptr; h->d_kcnt = nullptr; h->kqb_N = 0; h->d_hcnt = nullptr;
-  h->spread_cap = 0;
-  h->more_cap = 0;
+  h->spread = {};
+  h->d_more = {};
+  h->more = {};
+  h->ks = {};
+  h->spread_cap = h->kqb_N = 0;
 }
+int more_cap(const kmx_lcd* h) { return (int)h->d_more.cap(); }
 // Pinned host + device staging of at least `bytes` (grow-only; the callers
-// are synchronous, so the previous call's copies have completed).
-void io_free(kmx_lcd* h) {
-  if (h->h_io) (void)hipHostFree(h->h_io);
-  if (h->d_io) (void)hipFree(h->d_io);
-  h->h_io = nullptr; h->d_io = nullptr; h->z_io = nullptr;
-  h->io_cap = 0;
-}
+// are synchronous, so the previous call's copies have completed). Released
+// first; d_io before io, so io.cap() never promises more than d_io holds.
 int io_reserve(kmx_lcd* h, size_t bytes) {
-  if (bytes <= h->io_cap) return 0;
+  if (bytes <= h->io.cap()) return 0;
   KMX_HIP(sync_all(h));
-  io_free(h);
+  h->io = {};
+  h->d_io = {};
   const size_t cap = std::max<size_t>(bytes, 256 * 1024);
-  KMX_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->h_io), cap, hipHostMallocMapped | hipHostMallocCoherent));
-  KMX_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->z_io), h->h_io, 0));
-  KMX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_io), cap));
-  h->io_cap = cap;
-  return 0;
+  if (int rc = h->d_io.alloc(cap)) return rc;
+  return h->io.alloc(cap);
 }
 // One-candidate calls (the reference's verifyLoopSpin pattern) end in a kernel
 // that stores a fresh sequence number to a mapped word after its outputs
@@ -3586,28 +3568,24 @@ int io_reserve(kmx_lcd* h, size_t bytes) {
 // kernel). next_done gives the word and the sequence (nullptr: not used).
 unsigned* next_done(kmx_lcd* h, unsigned* seq) {
   if (!h->spin_wait) return nullptr;
-  if (!h->h_done) {
-    if (hipHostMalloc(reinterpret_cast<void**>(&h->h_done), 64, hipHostMallocMapped | hipHostMallocCoherent) !=
-            hipSuccess ||
-        hipHostGetDevicePointer(reinterpret_cast<void**>(&h->z_done), h->h_done, 0) != hipSuccess) {
-      if (h->h_done) (void)hipHostFree(h->h_done);
-      h->h_done = h->z_done = nullptr;
+  if (!h->done.host()) {
+    if (h->done.alloc(16)) {  // (a cache line)
       h->spin_wait = false;
       return nullptr;
     }
-    __atomic_store_n(h->h_done, 0u, __ATOMIC_RELEASE);
+    __atomic_store_n(h->done.host(), 0u, __ATOMIC_RELEASE);
   }
   *seq = ++h->done_seq == 0 ? ++h->done_seq : h->done_seq;  // never 0
-  return h->z_done;
+  return h->done.dev();
 }
 // Wait for `seq` in the completion word; past 2 s of spinning, synchronise
 // the stream (a faulted or hung kernel surfaces there) and require the word.
 int wait_done(kmx_lcd* h, hipStream_t st, unsigned seq) {
   const auto t0 = std::chrono::steady_clock::now();
-  while (__atomic_load_n(h->h_done, __ATOMIC_ACQUIRE) != seq) {
+  while (__atomic_load_n(h->done.host(), __ATOMIC_ACQUIRE) != seq) {
     if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
       KMX_HIP(hipStreamSynchronize(st));
-      KMX_CHECK(__atomic_load_n(h->h_done, __ATOMIC_ACQUIRE) == seq, KMX_EHIP,
+      KMX_CHECK(__atomic_load_n(h->done.host(), __ATOMIC_ACQUIRE) == seq, KMX_EHIP,
                 "a one-candidate call's kernel finished without its completion word");
       return 0;
     }
@@ -3634,18 +3612,6 @@ int rs_wait_slot(kmx_lcd* h) {
   if (cur_slot(h).ev_rs_set) KMX_HIP(hipStreamWaitEvent(rs_stream(h), cur_slot(h).ev_rs, 0));
   return 0;
 }
-// The staging areas of the small calls and the frame uploads, the completion
-// word and the ordered sampler's row.
-void lcd_free_staging(kmx_lcd* h) {
-  if (h->d_row) (void)hipFree(h->d_row);
-  h->d_row = nullptr;
-  io_free(h);
-  if (h->h_fst) (void)hipHostFree(h->h_fst);
-  h->h_fst = h->z_fst = nullptr;
-  h->fst_cap = 0;
-  if (h->h_done) (void)hipHostFree(h->h_done);
-  h->h_done = h->z_done = nullptr;
-}
 
 using kmx::build_table, kmx::rec_S, kmx::rec_sampled, kmx::sample_row, kmx::sampler_draw;  // lcd_host.h
 
@@ -3654,19 +3620,20 @@ using kmx::build_table, kmx::rec_S, kmx::rec_sampled, kmx::sample_row, kmx::samp
 int ensure_tables(kmx_lcd* h) {
   h->pmax = kmx::lcd_pmax(h->P);
   if (h->P.rng_stream) {
-    if (!h->d_row) KMX_HIP(hipMalloc(&h->d_row, sizeof(short) * (size_t)h->pmax * PNP_S));
+    if (!h->d_row.get()) return h->d_row.alloc((size_t)h->pmax * PNP_S);
     return 0;
   }
-  if (h->table_N == h->N && h->d_table) return 0;
-  lcd_free_tables(h);
+  if (h->table_N == h->N && h->tab.table.get()) return 0;
+  h->tab = {};
+  h->table_N = 0;
   std::vector<short> tab;
   build_table(h->P, h->N, h->pmax, tab);
-  KMX_HIP(hipMalloc(&h->d_table, sizeof(short) * tab.size()));
-  KMX_HIP(hipMemcpy(h->d_table, tab.data(), sizeof(short) * tab.size(), hipMemcpyHostToDevice));
+  if (int rc = h->tab.table.alloc(tab.size())) return rc;
+  KMX_HIP(hipMemcpy(h->tab.table.get(), tab.data(), sizeof(short) * tab.size(), hipMemcpyHostToDevice));
   if (rec_sampled(h->P)) {
     build_table(h->P, h->N, h->pmax, tab, rec_S(h->P));
-    KMX_HIP(hipMalloc(&h->d_table_rec, sizeof(short) * tab.size()));
-    KMX_HIP(hipMemcpy(h->d_table_rec, tab.data(), sizeof(short) * tab.size(), hipMemcpyHostToDevice));
+    if (int rc = h->tab.rec.alloc(tab.size())) return rc;
+    KMX_HIP(hipMemcpy(h->tab.rec.get(), tab.data(), sizeof(short) * tab.size(), hipMemcpyHostToDevice));
   }
   h->table_N = h->N;
   return 0;
@@ -3691,21 +3658,14 @@ int ensure_cap(kmx_lcd* h, int n, bool async) {
     KMX_HIP(sync_all(h));  // the slot's last call may still be in flight on any stream
     slot_free(sl);
     const int cap = std::max(n, 1024);
-    bool ok =
-           hipMalloc(&sl.fbuf, sizeof(double) * (6 * (size_t)h->N + STASH) * std::min(cap, RS_MAX_SLOTS)) ==
-               hipSuccess &&
-           hipMalloc(&sl.next, sizeof(int)) == hipSuccess &&
-           hipMalloc(&sl.cq, sizeof(int) * cap) == hipSuccess && hipMalloc(&sl.cm, sizeof(int) * cap) == hipSuccess &&
-           hipMalloc(&sl.K, sizeof(int) * cap) == hipSuccess &&
-           hipMalloc(&sl.pairs, sizeof(int2) * (size_t)cap * h->N) == hipSuccess &&
-           hipMalloc(&sl.res, sizeof(kmx_lcd_result) * cap) == hipSuccess &&
-           hipMalloc(&sl.mask, (size_t)cap * h->N) == hipSuccess && hipMalloc(&sl.hyps, sizeof(int) * cap) == hipSuccess &&
-           hipMalloc(&sl.nrec, sizeof(int) * cap) == hipSuccess &&
-           hipMalloc(&sl.prior, sizeof(double) * 12 * (size_t)cap) == hipSuccess &&
-           hipMalloc(&sl.order, sizeof(int) * cap) == hipSuccess;
-    if (!ok) {
+    const size_t c = (size_t)cap;
+    int rc = 0;
+    if ((rc = sl.fbuf.alloc((6 * (size_t)h->N + STASH) * std::min(cap, RS_MAX_SLOTS))) || (rc = sl.next.alloc(1)) ||
+        (rc = sl.cq.alloc(c)) || (rc = sl.cm.alloc(c)) || (rc = sl.K.alloc(c)) || (rc = sl.pairs.alloc(c * h->N)) ||
+        (rc = sl.res.alloc(c)) || (rc = sl.mask.alloc(c * h->N)) || (rc = sl.hyps.alloc(c)) ||
+        (rc = sl.nrec.alloc(c)) || (rc = sl.prior.alloc(12 * c)) || (rc = sl.order.alloc(c))) {
       lcd_free_cand(h);
-      return kmx::fail(KMX_ENOMEM, "candidate buffers");
+      return rc;
     }
     sl.cap = cap;
   }
@@ -3755,7 +3715,7 @@ RsParams rs_params(const kmx_lcd* h, int stages) {
   rp.algo = h->P.algorithm_2d2d;
   rp.refine = h->P.refine_pose && h->P.pose_recovery_type == 0 ? 1 : 0;
   rp.stages = stages;
-  rp.prior = cur_slot(h).prior;
+  rp.prior = cur_slot(h).prior.get();
   return rp;
 }
 PnpParams pnp_params(const kmx_lcd* h, int stages) {
@@ -3814,7 +3774,7 @@ int launch_ransac(kmx_lcd* h, int n, const RsParams& rp, const short* table, int
   KMX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kc, RS_BLOCK, 0));
   const Slot& sl = cur_slot(h);
   const int waves = std::max(1, std::min({n, std::max(per_cu, 1) * h->cus, RS_MAX_SLOTS, sl.cap}));  // (ensure_cap set cus)
-  KMX_HIP(hipMemsetAsync(sl.next, 0, sizeof(int), rs_stream(h)));
+  KMX_HIP(hipMemsetAsync(sl.next.get(), 0, sizeof(int), rs_stream(h)));
   RsParams p = rp;
   if (p.prior) p.prior += (size_t)c0 * 12;
   if (p.hyps) p.hyps += c0;
@@ -3823,13 +3783,14 @@ int launch_ransac(kmx_lcd* h, int n, const RsParams& rp, const short* table, int
   const bool longest_first = ov && std::atoi(ov) == 1;
   const int* order = nullptr;
   if (longest_first && n > 1 && c0 == 0) {
-    hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, rs_stream(h), (const int*)sl.K, n, h->N, sl.order);
-    order = sl.order;
+    hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, rs_stream(h), (const int*)sl.K.get(), n, h->N, sl.order.get());
+    order = sl.order.get();
   }
-  hipLaunchKernelGGL(kc, dim3(waves), dim3(RS_BLOCK), 0, rs_stream(h), (const double*)h->d_bear,
-                     (const double*)h->d_pts, h->N, (const int*)sl.cq + c0, (const int*)sl.cm + c0,
-                     (const int2*)sl.pairs + (size_t)c0 * h->N, (const int*)sl.K + c0, table, p, sl.res + c0,
-                     masks ? sl.mask + (size_t)c0 * h->N : nullptr, sl.fbuf, n, sl.next, order);
+  hipLaunchKernelGGL(kc, dim3(waves), dim3(RS_BLOCK), 0, rs_stream(h), (const double*)h->pool.bear.get(),
+                     (const double*)h->pool.pts.get(), h->N, (const int*)sl.cq.get() + c0, (const int*)sl.cm.get() + c0,
+                     (const int2*)sl.pairs.get() + (size_t)c0 * h->N, (const int*)sl.K.get() + c0, table, p,
+                     sl.res.get() + c0,
+                     masks ? sl.mask.get() + (size_t)c0 * h->N : nullptr, sl.fbuf.get(), n, sl.next.get(), order);
   return 0;
 }
 int launch_recover(kmx_lcd* h, int n, const PnpParams& pp, const short* table, int c0) {
@@ -3839,9 +3800,11 @@ int launch_recover(kmx_lcd* h, int n, const PnpParams& pp, const short* table, i
   if (p.hyps) p.hyps += c0;
   const Slot& sl = cur_slot(h);
   hipLaunchKernelGGL(pnp ? k_recover<true> : k_recover<false>, dim3(n), dim3(RS_BLOCK), smem, rs_stream(h),
-                     (const double*)h->d_bear, (const double*)h->d_pts, h->N, (const int*)sl.cq + c0,
-                     (const int*)sl.cm + c0, (const int2*)sl.pairs + (size_t)c0 * h->N, (const int*)sl.K + c0,
-                     table, p, sl.res + c0, sl.mask + (size_t)c0 * h->N);
+                     (const double*)h->pool.bear.get(), (const double*)h->pool.pts.get(), h->N,
+                     (const int*)sl.cq.get() + c0,
+                     (const int*)sl.cm.get() + c0, (const int2*)sl.pairs.get() + (size_t)c0 * h->N,
+                     (const int*)sl.K.get() + c0,
+                     table, p, sl.res.get() + c0, sl.mask.get() + (size_t)c0 * h->N);
   return 0;
 }
 
@@ -3855,15 +3818,15 @@ int launch_recover(kmx_lcd* h, int n, const PnpParams& pp, const short* table, i
 int verify_ordered(kmx_lcd* h, int n, int stages, bool masks) {
   const Slot& sl = cur_slot(h);
   std::vector<int> K(n);
-  KMX_HIP(hipMemcpyAsync(K.data(), sl.K, sizeof(int) * n, hipMemcpyDeviceToHost, rs_stream(h)));
+  KMX_HIP(hipMemcpyAsync(K.data(), sl.K.get(), sizeof(int) * n, hipMemcpyDeviceToHost, rs_stream(h)));
   KMX_HIP(hipStreamSynchronize(rs_stream(h)));
   RsParams rp = rs_params(h, stages);
   rp.tab_fixed = 1;
-  rp.hyps = sl.hyps;
-  rp.nrec = rec_sampled(h->P) ? sl.nrec : nullptr;
+  rp.hyps = sl.hyps.get();
+  rp.nrec = rec_sampled(h->P) ? sl.nrec.get() : nullptr;
   PnpParams pp = pnp_params(h, stages);
   pp.tab_fixed = 1;
-  pp.hyps = sl.hyps;
+  pp.hyps = sl.hyps.get();
   const int v = h->P.rng_variant;
   std::vector<short> row((size_t)h->pmax * PNP_S);
   auto advance = [&](int passes, int S) {
@@ -3874,30 +3837,30 @@ int verify_ordered(kmx_lcd* h, int n, int stages, bool masks) {
     if (st2d && K[c] >= 5) {
       std::mt19937 probe = h->stream_rng;
       sample_row(probe, v, K[c], h->pmax, 5, row.data());
-      KMX_HIP(hipMemcpyAsync(h->d_row, row.data(), sizeof(short) * (size_t)h->pmax * 5, hipMemcpyHostToDevice,
+      KMX_HIP(hipMemcpyAsync(h->d_row.get(), row.data(), sizeof(short) * (size_t)h->pmax * 5, hipMemcpyHostToDevice,
                              rs_stream(h)));
     }
-    if (int rc = launch_ransac(h, 1, rp, h->d_row, c, masks || rp.pnp)) return rc;
+    if (int rc = launch_ransac(h, 1, rp, h->d_row.get(), c, masks || rp.pnp)) return rc;
     int got[2] = {0, 0};
-    KMX_HIP(hipMemcpyAsync(&got[0], sl.hyps + c, sizeof(int), hipMemcpyDeviceToHost, rs_stream(h)));
-    if (rp.nrec) KMX_HIP(hipMemcpyAsync(&got[1], sl.nrec + c, sizeof(int), hipMemcpyDeviceToHost, rs_stream(h)));
+    KMX_HIP(hipMemcpyAsync(&got[0], sl.hyps.get() + c, sizeof(int), hipMemcpyDeviceToHost, rs_stream(h)));
+    if (rp.nrec) KMX_HIP(hipMemcpyAsync(&got[1], sl.nrec.get() + c, sizeof(int), hipMemcpyDeviceToHost, rs_stream(h)));
     KMX_HIP(hipStreamSynchronize(rs_stream(h)));
     if (st2d && K[c] >= 5) advance(got[0], 5);
     if (!rp.pnp || !(stages & KMX_LCD_STAGE_RECOVER)) continue;
     kmx_lcd_result r{};
-    KMX_HIP(hipMemcpyAsync(&r, sl.res + c, sizeof(r), hipMemcpyDeviceToHost, rs_stream(h)));
+    KMX_HIP(hipMemcpyAsync(&r, sl.res.get() + c, sizeof(r), hipMemcpyDeviceToHost, rs_stream(h)));
     KMX_HIP(hipStreamSynchronize(rs_stream(h)));
     if (r.mono_inliers < pp.min2d) continue;
     const int S = rec_S(h->P), n2 = got[1];
     if (n2 >= S) {
       std::mt19937 probe = h->stream_rng;
       sample_row(probe, v, n2, h->pmax, S, row.data());
-      KMX_HIP(hipMemcpyAsync(h->d_row, row.data(), sizeof(short) * (size_t)h->pmax * S, hipMemcpyHostToDevice,
+      KMX_HIP(hipMemcpyAsync(h->d_row.get(), row.data(), sizeof(short) * (size_t)h->pmax * S, hipMemcpyHostToDevice,
                              rs_stream(h)));
     }
-    if (int rc = launch_recover(h, 1, pp, h->d_row, c)) return rc;
+    if (int rc = launch_recover(h, 1, pp, h->d_row.get(), c)) return rc;
     int hy = 0;
-    KMX_HIP(hipMemcpyAsync(&hy, sl.hyps + c, sizeof(int), hipMemcpyDeviceToHost, rs_stream(h)));
+    KMX_HIP(hipMemcpyAsync(&hy, sl.hyps.get() + c, sizeof(int), hipMemcpyDeviceToHost, rs_stream(h)));
     KMX_HIP(hipStreamSynchronize(rs_stream(h)));
     if (n2 >= S) advance(hy, S);
   }
@@ -3930,9 +3893,11 @@ struct SmallCall {
 };
 // The slot's results (and masks) of n candidates to the pinned staging block.
 int copy_results(kmx_lcd* h, const Slot& sl, int n, size_t o_res, size_t o_mask) {
-  KMX_HIP(hipMemcpyAsync(h->h_io + o_res, sl.res, sizeof(kmx_lcd_result) * n, hipMemcpyDeviceToHost, rs_stream(h)));
+  KMX_HIP(hipMemcpyAsync(h->io.host() + o_res, sl.res.get(), sizeof(kmx_lcd_result) * n, hipMemcpyDeviceToHost,
+                         rs_stream(h)));
   if (o_mask)
-    KMX_HIP(hipMemcpyAsync(h->h_io + o_mask, sl.mask, (size_t)n * h->N, hipMemcpyDeviceToHost, rs_stream(h)));
+    KMX_HIP(hipMemcpyAsync(h->io.host() + o_mask, sl.mask.get(), (size_t)n * h->N, hipMemcpyDeviceToHost,
+                           rs_stream(h)));
   return 0;
 }
 // The one place that decides the spread form: a synchronous call of at most
@@ -3943,33 +3908,24 @@ bool takes_spread(const kmx_lcd* h, int n, bool sync_call) {
 // The spread form's buffers for n candidates (grow-only).
 int spread_alloc(kmx_lcd* h, int n) {
   hipStream_t st = rs_stream(h);
+  int rc = 0;
   if (n > h->spread_cap) {
-    void* q[] = {h->d_st, h->d_hout, h->d_sfbuf, h->d_hcnt};
     KMX_HIP(hipStreamSynchronize(st));
-    for (void* x : q)
-      if (x) (void)hipFree(x);
-    h->d_st = nullptr; h->d_hout = nullptr; h->d_sfbuf = nullptr; h->d_hcnt = nullptr;
+    h->spread = {};
     h->spread_cap = 0;
     const int cap = std::max(n, h->spread_max);
-    KMX_HIP(hipMalloc(&h->d_st, sizeof(RsState) * cap));
-    KMX_HIP(hipMalloc(&h->d_hcnt, sizeof(unsigned) * cap));
-    KMX_HIP(hipMalloc(&h->d_hout, sizeof(HypOut) * (size_t)cap * h->pmax));
-    KMX_HIP(hipMalloc(&h->d_sfbuf, sizeof(double) * (6 * (size_t)h->N + STASH) * std::max(SPREAD_WAVES, cap)));
+    kmx_lcd::Spread& sp = h->spread;
+    if ((rc = sp.st.alloc(cap)) || (rc = sp.hcnt.alloc(cap)) || (rc = sp.hout.alloc((size_t)cap * h->pmax)) ||
+        (rc = sp.sfbuf.alloc((6 * (size_t)h->N + STASH) * std::max(SPREAD_WAVES, cap))))
+      return rc;
     h->spread_cap = cap;
   }
-  if (h->pmax + 1 > h->more_cap) {  // every range advances by >= 1 pass: at most pmax ranges
+  if (h->pmax + 1 > more_cap(h)) {  // every range advances by >= 1 pass: at most pmax ranges
     KMX_HIP(hipStreamSynchronize(st));
-    if (h->d_more) (void)hipFree(h->d_more);
-    h->d_more = nullptr;
-    h->more_cap = 0;
-    KMX_HIP(hipMalloc(&h->d_more, sizeof(unsigned) * (h->pmax + 1)));
-    h->more_cap = h->pmax + 1;
+    h->d_more = {};
+    if ((rc = h->d_more.alloc(h->pmax + 1))) return rc;
   }
-  if (!h->h_more) {
-    KMX_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->h_more), sizeof(unsigned),
-                          hipHostMallocMapped | hipHostMallocCoherent));
-    KMX_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->z_more), h->h_more, 0));
-  }
+  if (!h->more.host()) return h->more.alloc(1);
   return 0;
 }
 int ransac_spread(kmx_lcd* h, int n, int stages, bool want_masks, SmallCall* sc) {
@@ -3980,8 +3936,9 @@ int ransac_spread(kmx_lcd* h, int n, int stages, bool want_masks, SmallCall* sc)
   if (int rc = spread_alloc(h, n)) return rc;
   const bool stew = rp.algo == KMX_ALGO_STEWENIUS;
   if (!(sc && sc->inited))
-    hipLaunchKernelGGL(k_rs_init, dim3((std::max(n, h->more_cap) + 63) / 64), dim3(64), 0, st, h->d_st, h->d_hcnt, n,
-                       stages, h->d_more, h->more_cap);
+    hipLaunchKernelGGL(k_rs_init, dim3((std::max(n, more_cap(h)) + 63) / 64), dim3(64), 0, st, h->spread.st.get(),
+                       h->spread.hcnt.get(), n,
+                       stages, h->d_more.get(), more_cap(h));
   const size_t tail_bytes = sizeof(double) * tail_lds_doubles(h->N);
   if (tail_bytes > 65536 - 16384)  // (max_feats near 1024: 75 KB, + 8.8 KB static: workspace, counts)
     KMX_HIP(hipFuncSetAttribute((const void*)k_rs_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tail_bytes));
@@ -3992,34 +3949,38 @@ int ransac_spread(kmx_lcd* h, int n, int stages, bool want_masks, SmallCall* sc)
     unsigned* done = one && seq_out ? next_done(h, &seq) : nullptr;
     if (seq_out) *seq_out = done ? seq : 0;
     hipLaunchKernelGGL(k_rs_finish, dim3(n), dim3(RS_BLOCK * RS_FIN), tail_bytes, st,
-                       (const double*)h->d_bear, (const double*)h->d_pts,
-                       h->N, (const int*)sl.cq, (const int*)sl.cm, (const int2*)sl.pairs, (const int*)sl.K, rp,
-                       (const RsState*)h->d_st, zc ? sc->res_dst : sl.res,
-                       masks ? (zc && sc->mask_dst ? sc->mask_dst : sl.mask) : nullptr, h->d_sfbuf, skip,
-                       skip && zc ? h->z_more : nullptr, done, seq);
+                       (const double*)h->pool.bear.get(), (const double*)h->pool.pts.get(),
+                       h->N, (const int*)sl.cq.get(), (const int*)sl.cm.get(), (const int2*)sl.pairs.get(),
+                       (const int*)sl.K.get(), rp,
+                       (const RsState*)h->spread.st.get(), zc ? sc->res_dst : sl.res.get(),
+                       masks ? (zc && sc->mask_dst ? sc->mask_dst : sl.mask.get()) : nullptr, h->spread.sfbuf.get(),
+                       skip,
+                       skip && zc ? h->more.dev() : nullptr, done, seq);
   };
   const bool spec = sc && !rp.pnp;
   int pa = 0, range = kmx::spread_first_range(n);
   for (int it = 0; pa < h->pmax && (stages & KMX_LCD_STAGE_2D2D); ++it) {  // (recovery alone: no hypotheses)
     const kmx::SpreadStep s = kmx::spread_step(n, pa, range, kmx::spread_per_max(rp.algo), h->pmax);
     hipLaunchKernelGGL(stew ? k_rs_hyps<true> : k_rs_hyps<false>, dim3(n * s.G), dim3(RS_BLOCK), 0, st,
-                       (const double*)h->d_bear, h->N, (const int*)sl.cq, (const int*)sl.cm,
-                       (const int2*)sl.pairs, (const int*)sl.K, (const short*)h->d_table, rp,
-                       h->d_st, h->d_hout, pa, s.pb, s.G, s.per, h->d_sfbuf, h->d_hcnt, h->d_more + it);
+                       (const double*)h->pool.bear.get(), h->N, (const int*)sl.cq.get(), (const int*)sl.cm.get(),
+                       (const int2*)sl.pairs.get(), (const int*)sl.K.get(), (const short*)h->tab.table.get(), rp,
+                       h->spread.st.get(), h->spread.hout.get(), pa, s.pb, s.G, s.per, h->spread.sfbuf.get(),
+                       h->spread.hcnt.get(), h->d_more.get() + it);
     const bool zc_more = spec && it == 0 && zc;  // the speculative finish writes the word itself
     unsigned sseq = 0;
     if (spec && it == 0) {
-      finish(h->d_more, zc_more ? &sseq : nullptr);
+      finish(h->d_more.get(), zc_more ? &sseq : nullptr);
       if (!zc)
         if (int rc = copy_results(h, sl, n, sc->o_res, sc->o_mask)) return rc;
     }
-    if (!zc_more) KMX_HIP(hipMemcpyAsync(h->h_more, h->d_more + it, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    if (!zc_more) KMX_HIP(hipMemcpyAsync(h->more.host(), h->d_more.get() + it, sizeof(unsigned),
+        hipMemcpyDeviceToHost, st));
     if (sseq) {  // the finish stored the more word before its completion word
       if (int rc = wait_done(h, st, sseq)) return rc;
     } else {
       KMX_HIP(hipStreamSynchronize(st));
     }
-    if (!*h->h_more) {
+    if (!*h->more.host()) {
       if (spec && it == 0) {
         sc->copied = true;
         sc->fseq = sseq;
@@ -4033,7 +3994,7 @@ int ransac_spread(kmx_lcd* h, int n, int stages, bool want_masks, SmallCall* sc)
   }
   finish(nullptr, sc ? &sc->fseq : nullptr);
   if (rp.pnp && (stages & KMX_LCD_STAGE_RECOVER))
-    if (int rc = launch_recover(h, n, pnp_params(h, stages), h->d_table_rec, 0)) return rc;
+    if (int rc = launch_recover(h, n, pnp_params(h, stages), h->tab.rec.get(), 0)) return rc;
   KMX_HIP(hipGetLastError());
   return 0;
 }
@@ -4046,9 +4007,9 @@ int enqueue_ransac(kmx_lcd* h, int n, int stages, bool want_masks, bool sync_cal
   if (h->P.rng_stream) return verify_ordered(h, n, stages, want_masks);
   if (takes_spread(h, n, sync_call)) return ransac_spread(h, n, stages, want_masks, sc);
   const RsParams rp = rs_params(h, stages);
-  if (int rc = launch_ransac(h, n, rp, h->d_table, 0, want_masks || rp.pnp)) return rc;
+  if (int rc = launch_ransac(h, n, rp, h->tab.table.get(), 0, want_masks || rp.pnp)) return rc;
   if (rp.pnp && (stages & KMX_LCD_STAGE_RECOVER))
-    if (int rc = launch_recover(h, n, pnp_params(h, stages), h->d_table_rec, 0)) return rc;
+    if (int rc = launch_recover(h, n, pnp_params(h, stages), h->tab.rec.get(), 0)) return rc;
   return 0;
 }
 
@@ -4058,8 +4019,8 @@ int slot_upload(kmx_lcd* h, int n, const int32_t* cq, const int32_t* cm) {
   const Slot &sl = cur_slot(h), &sl2 = h->slot[(h->cur + LCD_SLOTS - 2) % LCD_SLOTS];
   if (sl.ev_rs_set) KMX_HIP(hipStreamWaitEvent(h->kstream, sl.ev_rs, 0));
   if (!h->rs_small && sl2.ev_rs_set) KMX_HIP(hipStreamWaitEvent(h->kstream, sl2.ev_rs, 0));
-  KMX_HIP(hipMemcpyAsync(sl.cq, cq, sizeof(int) * n, hipMemcpyHostToDevice, h->kstream));
-  KMX_HIP(hipMemcpyAsync(sl.cm, cm, sizeof(int) * n, hipMemcpyHostToDevice, h->kstream));
+  KMX_HIP(hipMemcpyAsync(sl.cq.get(), cq, sizeof(int) * n, hipMemcpyHostToDevice, h->kstream));
+  KMX_HIP(hipMemcpyAsync(sl.cm.get(), cm, sizeof(int) * n, hipMemcpyHostToDevice, h->kstream));
   return 0;
 }
 // The kNN2 of n candidates on stream st: k_knn2, or for a synchronous call of
@@ -4080,27 +4041,29 @@ int launch_knn2(kmx_lcd* h, int n, const KnnIo& io, hipStream_t st, bool sync_ca
   if (sync_call && h->knn_split && n <= KS_MAX) {
     if (h->kqb_N < h->N) {
       KMX_HIP(hipStreamSynchronize(st));
-      if (h->d_kqb) (void)hipFree(h->d_kqb);
-      h->d_kqb = nullptr;
+      h->ks.kqb = {};
       h->kqb_N = 0;
-      KMX_HIP(hipMalloc(&h->d_kqb, sizeof(int) * (size_t)KS_MAX * h->N));
+      if (int rc = h->ks.kqb.alloc((size_t)KS_MAX * h->N)) return rc;
       h->kqb_N = h->N;
     }
-    if (!h->d_kcnt) {
-      KMX_HIP(hipMalloc(&h->d_kcnt, sizeof(unsigned) * KS_MAX));
-      KMX_HIP(hipMemsetAsync(h->d_kcnt, 0, sizeof(unsigned) * KS_MAX, st));
+    if (!h->ks.kcnt.get()) {
+      if (int rc = h->ks.kcnt.alloc(KS_MAX)) return rc;
+      KMX_HIP(hipMemsetAsync(h->ks.kcnt.get(), 0, sizeof(unsigned) * KS_MAX, st));
     }
     const int S = (h->N + KS_Q - 1) / KS_Q;
     const size_t smem = (size_t)h->N * 32 + sizeof(uint32_t) * 4 * KS_Q * 2 + sizeof(int) * (KNN_BLOCK + 1);
     hipLaunchKernelGGL(h->P.norm == KMX_NORM_HAMMING ? k_knn2s<true> : k_knn2s<false>, dim3(n * S), dim3(KNN_BLOCK),
-                       smem, st, (const uint32_t*)h->d_desc, (const int*)h->d_nfeat, h->N, io.cq, io.cm,
-                       h->P.lowe_ratio, io.pairs, io.K, h->d_kqb, h->d_kcnt, S, done.word, done.seq);
+                       smem, st, (const uint32_t*)h->pool.desc.get(), (const int*)h->pool.nfeat.get(), h->N, io.cq,
+                       io.cm,
+                       h->P.lowe_ratio, io.pairs, io.K, h->ks.kqb.get(), h->ks.kcnt.get(), S, done.word, done.seq);
   } else if (h->knn_q && h->P.norm == KMX_NORM_HAMMING && h->N <= KQ_BLOCK * KQ_Q) {
-    hipLaunchKernelGGL(k_knn2q<true>, dim3(n), dim3(KQ_BLOCK), (size_t)h->N * 32, st, (const uint32_t*)h->d_desc,
-                       (const int*)h->d_nfeat, h->N, io.cq, io.cm, h->P.lowe_ratio, io.pairs, io.K);
+    hipLaunchKernelGGL(k_knn2q<true>, dim3(n), dim3(KQ_BLOCK), (size_t)h->N * 32, st,
+                       (const uint32_t*)h->pool.desc.get(),
+                       (const int*)h->pool.nfeat.get(), h->N, io.cq, io.cm, h->P.lowe_ratio, io.pairs, io.K);
   } else {
     hipLaunchKernelGGL(k_knn2, dim3(n), dim3(KNN_BLOCK), (size_t)h->N * 32 + sizeof(int) * (KNN_BLOCK + 1), st,
-                       (const uint32_t*)h->d_desc, (const int*)h->d_nfeat, h->N, io.cq, io.cm, h->P.norm,
+                       (const uint32_t*)h->pool.desc.get(), (const int*)h->pool.nfeat.get(), h->N, io.cq, io.cm,
+                       h->P.norm,
                        h->P.lowe_ratio, io.pairs, io.K);
   }
   return 0;
@@ -4114,13 +4077,12 @@ int enqueue_verify(kmx_lcd* h, int n, bool want_masks, bool sync_call = false) {
   if (n == 0) return 0;
   Slot& sl = cur_slot(h);
   if (h->timing) {
-    if (!h->ev_ok) {
-      for (auto& e : h->ev) KMX_HIP(hipEventCreate(&e));
-      h->ev_ok = true;
-    }
+    if (!h->ev[2])
+      if (int rc = kmx::create_events(h->ev)) return rc;
     KMX_HIP(hipEventRecord(h->ev[0], h->kstream));
   }
-  if (int rc = launch_knn2(h, n, KnnIo{sl.cq, sl.cm, sl.pairs, sl.K}, h->kstream, sync_call)) return rc;
+  const KnnIo io{sl.cq.get(), sl.cm.get(), sl.pairs.get(), sl.K.get()};
+  if (int rc = launch_knn2(h, n, io, h->kstream, sync_call)) return rc;
   if (h->timing) KMX_HIP(hipEventRecord(h->ev[1], h->kstream));
   KMX_HIP(hipEventRecord(sl.ev_knn, h->kstream));
   KMX_HIP(hipStreamWaitEvent(rs_stream(h), sl.ev_knn, 0));
@@ -4145,29 +4107,21 @@ int grow_pool(kmx_lcd* h, int need) {
   if (need <= h->capF) return 0;
   const int cap = std::max({need, 2 * h->capF, 64});
   const size_t FN = (size_t)cap * h->N, old = (size_t)h->F * h->N;
-  uint32_t* desc = nullptr;
-  double *bear = nullptr, *pts = nullptr;
-  int* nf = nullptr;
-  if (hipMalloc(&desc, FN * 32) != hipSuccess || hipMalloc(&bear, FN * 3 * sizeof(double)) != hipSuccess ||
-      hipMalloc(&pts, FN * 3 * sizeof(double)) != hipSuccess || hipMalloc(&nf, sizeof(int) * cap) != hipSuccess) {
-    for (void* x : {(void*)desc, (void*)bear, (void*)pts, (void*)nf})
-      if (x) (void)hipFree(x);
-    return kmx::fail(KMX_ENOMEM, "frame pool");
-  }
+  kmx_lcd::Pool np;  // built aside: a failure leaves the resident pool as it was
+  int rc = 0;
+  if ((rc = np.desc.alloc(FN * 8)) || (rc = np.bear.alloc(FN * 3)) || (rc = np.pts.alloc(FN * 3)) ||
+      (rc = np.nfeat.alloc(cap)))
+    return rc;
   KMX_HIP(sync_all(h));  // a kNN2 or a RANSAC in flight may read the old pool
   if (h->F) {
-    KMX_HIP(hipMemcpyAsync(desc, h->d_desc, old * 32, hipMemcpyDeviceToDevice, h->stream));
-    KMX_HIP(hipMemcpyAsync(bear, h->d_bear, old * 3 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    KMX_HIP(hipMemcpyAsync(pts, h->d_pts, old * 3 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    KMX_HIP(hipMemcpyAsync(nf, h->d_nfeat, sizeof(int) * h->F, hipMemcpyDeviceToDevice, h->stream));
+    const kmx_lcd::Pool& op = h->pool;
+    KMX_HIP(hipMemcpyAsync(np.desc.get(), op.desc.get(), old * 32, hipMemcpyDeviceToDevice, h->stream));
+    KMX_HIP(hipMemcpyAsync(np.bear.get(), op.bear.get(), old * 3 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    KMX_HIP(hipMemcpyAsync(np.pts.get(), op.pts.get(), old * 3 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    KMX_HIP(hipMemcpyAsync(np.nfeat.get(), op.nfeat.get(), sizeof(int) * h->F, hipMemcpyDeviceToDevice, h->stream));
     KMX_HIP(hipStreamSynchronize(h->stream));
   }
-  for (void* x : {(void*)h->d_desc, (void*)h->d_bear, (void*)h->d_pts, (void*)h->d_nfeat})
-    if (x) (void)hipFree(x);
-  h->d_desc = desc;
-  h->d_bear = bear;
-  h->d_pts = pts;
-  h->d_nfeat = nf;
+  h->pool = std::move(np);
   h->capF = cap;
   return 0;
 }
@@ -4197,38 +4151,35 @@ int upload_frames(kmx_lcd* h, int n, const int32_t* n_feats, const uint8_t* desc
   const size_t b_desc = FN * 32, b_bear = FN * 3 * sizeof(double), b_nf = sizeof(int) * n;
   const size_t b_all = b_desc + 2 * b_bear + b_nf;
   if (b_all <= FRAME_STAGE_MAX) {
-    if (b_all > h->fst_cap) {  // grow-only; the previous upload has completed (synchronised below)
-      if (h->h_fst) (void)hipHostFree(h->h_fst);
-      h->h_fst = h->z_fst = nullptr;
-      h->fst_cap = 0;
-      const size_t cap = std::max<size_t>(b_all, 256 * 1024);
-      KMX_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->h_fst), cap, hipHostMallocMapped | hipHostMallocCoherent));
-      KMX_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->z_fst), h->h_fst, 0));
-      h->fst_cap = cap;
+    if (b_all > h->fst.cap()) {  // grow-only; the previous upload has completed (synchronised below)
+      h->fst = {};
+      if (int rc = h->fst.alloc(std::max<size_t>(b_all, 256 * 1024))) return rc;
     }
-    std::memcpy(h->h_fst, desc, b_desc);
-    std::memcpy(h->h_fst + b_desc, bearings, b_bear);
-    std::memcpy(h->h_fst + b_desc + b_bear, points, b_bear);
-    std::memcpy(h->h_fst + b_desc + 2 * b_bear, n_feats, b_nf);
+    std::memcpy(h->fst.host(), desc, b_desc);
+    std::memcpy(h->fst.host() + b_desc, bearings, b_bear);
+    std::memcpy(h->fst.host() + b_desc + b_bear, points, b_bear);
+    std::memcpy(h->fst.host() + b_desc + 2 * b_bear, n_feats, b_nf);
     const size_t words = (b_desc + 2 * b_bear) / 8;
     const int blocks = (int)std::min<size_t>((words + 255) / 256, 1024);
     hipLaunchKernelGGL(k_put_frames, dim3(std::max(blocks, 1)), dim3(256), 0, h->stream,
-                       reinterpret_cast<const unsigned long long*>(h->z_fst), b_desc / 8, b_bear / 8,
-                       reinterpret_cast<unsigned long long*>(reinterpret_cast<uint8_t*>(h->d_desc) + at * 32),
-                       reinterpret_cast<unsigned long long*>(h->d_bear + at * 3),
-                       reinterpret_cast<unsigned long long*>(h->d_pts + at * 3),
-                       reinterpret_cast<const int*>(h->z_fst + b_desc + 2 * b_bear), h->d_nfeat + h->F, n);
+                       reinterpret_cast<const unsigned long long*>(h->fst.dev()), b_desc / 8, b_bear / 8,
+                       reinterpret_cast<unsigned long long*>(reinterpret_cast<uint8_t*>(h->pool.desc.get()) + at * 32),
+                       reinterpret_cast<unsigned long long*>(h->pool.bear.get() + at * 3),
+                       reinterpret_cast<unsigned long long*>(h->pool.pts.get() + at * 3),
+                       reinterpret_cast<const int*>(h->fst.dev() + b_desc + 2 * b_bear), h->pool.nfeat.get() + h->F, n);
     KMX_HIP(hipGetLastError());
     KMX_HIP(hipStreamSynchronize(h->stream));  // the staging area is reused by the next call
     h->h_nfeat.insert(h->h_nfeat.end(), n_feats, n_feats + n);
     h->F += n;
     return 0;
   }
-  KMX_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(h->d_desc) + at * 32, desc, FN * 32, hipMemcpyHostToDevice,
+  KMX_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(h->pool.desc.get()) + at * 32, desc, FN * 32, hipMemcpyHostToDevice,
                          h->stream));
-  KMX_HIP(hipMemcpyAsync(h->d_bear + at * 3, bearings, FN * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  KMX_HIP(hipMemcpyAsync(h->d_pts + at * 3, points, FN * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  KMX_HIP(hipMemcpyAsync(h->d_nfeat + h->F, n_feats, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->pool.bear.get() + at * 3, bearings, FN * 3 * sizeof(double), hipMemcpyHostToDevice,
+                         h->stream));
+  KMX_HIP(hipMemcpyAsync(h->pool.pts.get() + at * 3, points, FN * 3 * sizeof(double), hipMemcpyHostToDevice,
+                         h->stream));
+  KMX_HIP(hipMemcpyAsync(h->pool.nfeat.get() + h->F, n_feats, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));  // the host arrays may go away after return
   h->h_nfeat.insert(h->h_nfeat.end(), n_feats, n_feats + n);
   h->F += n;
@@ -4242,58 +4193,35 @@ extern "C" int kmx_lcd_create(const kmx_lcd_params* params, int device, kmx_lcd*
   KMX_CHECK(out, KMX_EINVAL, "null argument");
   std::string err;
   if (int rc = kmx::lcd_check_params(params, &err)) return kmx::fail(rc, err);
-  int ndev = 0;
-  KMX_HIP(hipGetDeviceCount(&ndev));
-  KMX_CHECK(device >= 0 && device < ndev, KMX_EINVAL, "bad HIP device ordinal");
-  KMX_HIP(hipSetDevice(device));
-  kmx_lcd* h = new kmx_lcd();
+  auto h = std::make_unique<kmx_lcd>();
+  if (int rc = h->open(device)) return rc;
   h->P = *params;
-  h->device = device;
   h->stream_rng.seed(params->ransac_seed);
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-    delete h;
-    return kmx::fail(KMX_EHIP, "hipStreamCreate");
-  }
-  h->own_stream = true;
   if (const char* e = std::getenv("KMX_LCD_RSX")) h->rs_conc = std::atoi(e) != 0;
   if (const char* e = std::getenv("KMX_LCD_KSPLIT")) h->knn_split = std::atoi(e) != 0;
   if (const char* e = std::getenv("KMX_LCD_KNNQ")) h->knn_q = std::atoi(e) != 0;
   if (const char* e = std::getenv("KMX_LCD_SPINWAIT")) h->spin_wait = std::atoi(e) != 0;
-  bool ok = hipStreamCreateWithFlags(&h->kstream, hipStreamNonBlocking) == hipSuccess;
-  for (int i = 1; i < LCD_SLOTS && ok; ++i)
-    ok = hipStreamCreateWithFlags(&h->slot[i].rsx, hipStreamNonBlocking) == hipSuccess;
-  for (int i = 0; i < LCD_SLOTS && ok; ++i)
-    ok = hipEventCreateWithFlags(&h->slot[i].ev_knn, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&h->slot[i].ev_rs, hipEventDisableTiming) == hipSuccess;
-  if (!ok) {
-    kmx_lcd_destroy(h);
-    return kmx::fail(KMX_EHIP, "hipStreamCreate / hipEventCreate");
+  if (int rc = h->kstream.create()) return rc;
+  for (int i = 0; i < LCD_SLOTS; ++i) {
+    Slot& sl = h->slot[i];
+    if (i > 0)
+      if (int rc = sl.rsx.create()) return rc;
+    if (int rc = sl.ev_knn.create(hipEventDisableTiming)) return rc;
+    if (int rc = sl.ev_rs.create(hipEventDisableTiming)) return rc;
   }
   if (const char* v = std::getenv("KMX_RS_PROF")) h->prof = std::atoi(v);
   // KMX_LCD_SPREAD: the largest synchronous call that takes the spread form (0: never)
   if (const char* v = std::getenv("KMX_LCD_SPREAD")) h->spread_max = std::max(0, std::atoi(v));
-  *out = h;
+  *out = h.release();
   return KMX_OK;
   KMX_GUARD_END
 }
 
+// The device current, every stream's work done, then the members free what they hold.
 extern "C" int kmx_lcd_destroy(kmx_lcd* h) {
   if (!h) return KMX_OK;
   (void)hipSetDevice(h->device);
   (void)sync_all(h);
-  lcd_free_frames(h);
-  lcd_free_tables(h);
-  lcd_free_cand(h);
-  lcd_free_staging(h);
-  if (h->ev_ok)
-    for (auto e : h->ev) (void)hipEventDestroy(e);
-  for (Slot& sl : h->slot) {
-    if (sl.ev_knn) (void)hipEventDestroy(sl.ev_knn);
-    if (sl.ev_rs) (void)hipEventDestroy(sl.ev_rs);
-    if (sl.rsx) (void)hipStreamDestroy(sl.rsx);
-  }
-  if (h->kstream) (void)hipStreamDestroy(h->kstream);
-  if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return KMX_OK;
 }
@@ -4303,10 +4231,7 @@ extern "C" int kmx_lcd_set_stream(kmx_lcd* h, void* s) {
   KMX_CHECK(h, KMX_EINVAL, "null handle");
   KMX_HIP(hipSetDevice(h->device));
   KMX_HIP(sync_all(h));
-  if (h->own_stream && h->stream) KMX_HIP(hipStreamDestroy(h->stream));
-  h->own_stream = false;
-  h->stream = reinterpret_cast<hipStream_t>(s);
-  return KMX_OK;
+  return h->adopt(s, true);
   KMX_GUARD_END
 }
 
@@ -4368,14 +4293,14 @@ int kmx::lcd_pool_view(kmx_lcd* h, kmx::LcdPoolView* out) {
   out->device = h->device;
   out->n_frames = h->F;
   out->max_feats = h->N;
-  out->desc = h->d_desc;
-  out->n_feats = h->d_nfeat;
+  out->desc = h->pool.desc.get();
+  out->n_feats = h->pool.nfeat.get();
   out->stream = h->stream;
   return KMX_OK;
 }
 
 static int check_cands(kmx_lcd* h, int32_t n, const int32_t* cq, const int32_t* cm) {
-  KMX_CHECK(h && h->d_desc && h->F > 0, KMX_ESTATE, "no frames: set_frames or add_frames first");
+  KMX_CHECK(h && h->pool.desc.get() && h->F > 0, KMX_ESTATE, "no frames: set_frames or add_frames first");
   KMX_CHECK(n >= 0 && (n == 0 || (cq && cm)), KMX_EINVAL, "bad candidate arrays");
   std::string err;
   if (int rc = kmx::lcd_check_cands(n, h->F, cq, cm, &err)) return kmx::fail(rc, err);
@@ -4392,9 +4317,10 @@ extern "C" int kmx_lcd_verify(kmx_lcd* h, int32_t n, const int32_t* cq, const in
   if (int rc = slot_upload(h, n, cq, cm)) return rc;
   if (int rc = enqueue_verify(h, n, inlier_masks != nullptr, true)) return rc;
   const Slot& sl = cur_slot(h);
-  if (n) KMX_HIP(hipMemcpyAsync(results, sl.res, sizeof(kmx_lcd_result) * n, hipMemcpyDeviceToHost, rs_stream(h)));
+  if (n) KMX_HIP(hipMemcpyAsync(results, sl.res.get(), sizeof(kmx_lcd_result) * n, hipMemcpyDeviceToHost,
+      rs_stream(h)));
   if (n && inlier_masks)
-    KMX_HIP(hipMemcpyAsync(inlier_masks, sl.mask, (size_t)n * h->N, hipMemcpyDeviceToHost, rs_stream(h)));
+    KMX_HIP(hipMemcpyAsync(inlier_masks, sl.mask.get(), (size_t)n * h->N, hipMemcpyDeviceToHost, rs_stream(h)));
   KMX_HIP(hipStreamSynchronize(rs_stream(h)));
   return KMX_OK;
   KMX_GUARD_END
@@ -4426,22 +4352,23 @@ extern "C" int kmx_lcd_match(kmx_lcd* h, int32_t n, const int32_t* cq, const int
   const kmx::LcdMatchLayout L = kmx::lcd_match_layout(n, h->N);
   const size_t pb = sizeof(int2) * (size_t)n * h->N;
   if (int rc = io_reserve(h, L.total)) return rc;
-  std::memcpy(h->h_io + L.o_cq, cq, sizeof(int) * n);
-  std::memcpy(h->h_io + L.o_cm, cm, sizeof(int) * n);
+  std::memcpy(h->io.host() + L.o_cq, cq, sizeof(int) * n);
+  std::memcpy(h->io.host() + L.o_cm, cm, sizeof(int) * n);
   const Slot& sl = cur_slot(h);
   const bool zc = h->knn_split && n <= KS_MAX;
   Done done;
   if (zc && n == 1) done.word = next_done(h, &done.seq);  // one candidate: spin on the completion word
   if (zc) {
-    char* z = h->z_io;
+    char* z = h->io.dev();
     const KnnIo io{(const int*)(z + L.o_cq), (const int*)(z + L.o_cm), (int2*)(z + L.o_pairs), (int*)(z + L.o_K)};
     if (int rc = launch_knn2(h, n, io, rs_stream(h), true, done)) return rc;
   } else {
-    KMX_HIP(hipMemcpyAsync(h->d_io, h->h_io, L.o_pairs, hipMemcpyHostToDevice, rs_stream(h)));
-    const KnnIo io{(const int*)(h->d_io + L.o_cq), (const int*)(h->d_io + L.o_cm), sl.pairs, sl.K};
+    KMX_HIP(hipMemcpyAsync(h->d_io.get(), h->io.host(), L.o_pairs, hipMemcpyHostToDevice, rs_stream(h)));
+    const KnnIo io{(const int*)(h->d_io.get() + L.o_cq), (const int*)(h->d_io.get() + L.o_cm), sl.pairs.get(),
+                    sl.K.get()};
     if (int rc = launch_knn2(h, n, io, rs_stream(h), true)) return rc;
-    KMX_HIP(hipMemcpyAsync(h->h_io + L.o_pairs, sl.pairs, pb, hipMemcpyDeviceToHost, rs_stream(h)));
-    KMX_HIP(hipMemcpyAsync(h->h_io + L.o_K, sl.K, sizeof(int) * n, hipMemcpyDeviceToHost, rs_stream(h)));
+    KMX_HIP(hipMemcpyAsync(h->io.host() + L.o_pairs, sl.pairs.get(), pb, hipMemcpyDeviceToHost, rs_stream(h)));
+    KMX_HIP(hipMemcpyAsync(h->io.host() + L.o_K, sl.K.get(), sizeof(int) * n, hipMemcpyDeviceToHost, rs_stream(h)));
   }
   KMX_HIP(hipGetLastError());
   if (int rc = mark_slot(h)) return rc;
@@ -4450,8 +4377,8 @@ extern "C" int kmx_lcd_match(kmx_lcd* h, int32_t n, const int32_t* cq, const int
   } else {
     KMX_HIP(hipStreamSynchronize(rs_stream(h)));
   }
-  std::memcpy(pairs_out, h->h_io + L.o_pairs, pb);
-  std::memcpy(k_out, h->h_io + L.o_K, sizeof(int) * n);
+  std::memcpy(pairs_out, h->io.host() + L.o_pairs, pb);
+  std::memcpy(k_out, h->io.host() + L.o_K, sizeof(int) * n);
   return KMX_OK;
   KMX_GUARD_END
 }
@@ -4483,15 +4410,15 @@ extern "C" int kmx_lcd_verify_matches(kmx_lcd* h, int32_t n, const int32_t* cq, 
   const kmx::LcdVerifyLayout L = kmx::lcd_verify_layout(n, h->N, total, T_prior != nullptr, inlier_masks != nullptr);
   if (int rc = io_reserve(h, L.total)) return rc;
   {
-    int64_t* mp = reinterpret_cast<int64_t*>(h->h_io + L.o_mptr);
+    int64_t* mp = reinterpret_cast<int64_t*>(h->io.host() + L.o_mptr);
     for (int i = 0; i <= n; ++i) mp[i] = mptr[i] - base;
-    std::memcpy(h->h_io + L.o_cq, cq, sizeof(int) * n);
-    std::memcpy(h->h_io + L.o_cm, cm, sizeof(int) * n);
+    std::memcpy(h->io.host() + L.o_cq, cq, sizeof(int) * n);
+    std::memcpy(h->io.host() + L.o_cm, cm, sizeof(int) * n);
     if (total) {
-      std::memcpy(h->h_io + L.o_iq, iq + base, sizeof(int) * total);
-      std::memcpy(h->h_io + L.o_im, im + base, sizeof(int) * total);
+      std::memcpy(h->io.host() + L.o_iq, iq + base, sizeof(int) * total);
+      std::memcpy(h->io.host() + L.o_im, im + base, sizeof(int) * total);
     }
-    if (T_prior) std::memcpy(h->h_io + L.o_prior, T_prior, sizeof(double) * 12 * n);
+    if (T_prior) std::memcpy(h->io.host() + L.o_prior, T_prior, sizeof(double) * 12 * n);
   }
   // a spread-form call (small, synchronous) reads its inputs from the mapped
   // staging and, without PnP (k_recover writes through the device buffers),
@@ -4502,21 +4429,21 @@ extern "C" int kmx_lcd_verify_matches(kmx_lcd* h, int32_t n, const int32_t* cq, 
   sc.o_res = L.o_res;
   sc.o_mask = inlier_masks ? L.o_mask : 0;
   if (spread && !rs_params(h, stages).pnp) {
-    sc.res_dst = reinterpret_cast<kmx_lcd_result*>(h->z_io + L.o_res);
-    if (inlier_masks) sc.mask_dst = reinterpret_cast<unsigned char*>(h->z_io + L.o_mask);
+    sc.res_dst = reinterpret_cast<kmx_lcd_result*>(h->io.dev() + L.o_res);
+    if (inlier_masks) sc.mask_dst = reinterpret_cast<unsigned char*>(h->io.dev() + L.o_mask);
   }
-  const char* src = spread ? h->z_io : h->d_io;
+  const char* src = spread ? h->io.dev() : h->d_io.get();
   if (spread) {
     if (int rc = spread_alloc(h, n)) return rc;
   } else {
-    KMX_HIP(hipMemcpyAsync(h->d_io, h->h_io, L.in_bytes, hipMemcpyHostToDevice, rs_stream(h)));
+    KMX_HIP(hipMemcpyAsync(h->d_io.get(), h->io.host(), L.in_bytes, hipMemcpyHostToDevice, rs_stream(h)));
   }
   const Slot& sl = cur_slot(h);
   hipLaunchKernelGGL(k_scatter_pairs, dim3(n), dim3(256), 0, rs_stream(h), (const int64_t*)(src + L.o_mptr),
-                     (const int*)(src + L.o_iq), (const int*)(src + L.o_im), h->N, sl.pairs, sl.K,
+                     (const int*)(src + L.o_iq), (const int*)(src + L.o_im), h->N, sl.pairs.get(), sl.K.get(),
                      (const int*)(src + L.o_cq), (const int*)(src + L.o_cm),
-                     T_prior ? (const double*)(src + L.o_prior) : nullptr, sl.cq, sl.cm, sl.prior,
-                     spread ? h->d_st : nullptr, h->d_hcnt, stages, h->d_more, h->more_cap);
+                     T_prior ? (const double*)(src + L.o_prior) : nullptr, sl.cq.get(), sl.cm.get(), sl.prior.get(),
+                     spread ? h->spread.st.get() : nullptr, h->spread.hcnt.get(), stages, h->d_more.get(), more_cap(h));
   KMX_HIP(hipGetLastError());
   if (int rc = enqueue_ransac(h, n, stages, inlier_masks != nullptr, true, &sc)) return rc;
   KMX_HIP(hipGetLastError());
@@ -4528,8 +4455,8 @@ extern "C" int kmx_lcd_verify_matches(kmx_lcd* h, int32_t n, const int32_t* cq, 
   } else {
     KMX_HIP(hipStreamSynchronize(rs_stream(h)));
   }
-  std::memcpy(results, h->h_io + L.o_res, sizeof(kmx_lcd_result) * n);
-  if (inlier_masks) std::memcpy(inlier_masks, h->h_io + L.o_mask, (size_t)n * h->N);
+  std::memcpy(results, h->io.host() + L.o_res, sizeof(kmx_lcd_result) * n);
+  if (inlier_masks) std::memcpy(inlier_masks, h->io.host() + L.o_mask, (size_t)n * h->N);
   return KMX_OK;
   KMX_GUARD_END
 }
@@ -4542,7 +4469,7 @@ extern "C" int kmx_lcd_enable_timing(kmx_lcd* h, int enable) {
 
 extern "C" int kmx_lcd_read_timing(kmx_lcd* h, double* knn_ms, double* ransac_ms) {
   KMX_CHECK(h && knn_ms && ransac_ms, KMX_EINVAL, "null argument");
-  KMX_CHECK(h->ev_ok, KMX_ESTATE, "no evented verification yet (kmx_lcd_enable_timing)");
+  KMX_CHECK(h->ev[2], KMX_ESTATE, "no evented verification yet (kmx_lcd_enable_timing)");
   KMX_HIP(hipSetDevice(h->device));
   KMX_HIP(sync_all(h));
   float a = 0.f, b = 0.f;
@@ -4574,37 +4501,27 @@ extern "C" int kmx_lcd_knn2(int norm, double lowe_ratio, const uint8_t* q, int32
   if (nq) std::memcpy(pool.data(), q, (size_t)nq * 32);
   if (nm) std::memcpy(pool.data() + (size_t)N * 32, mdesc, (size_t)nm * 32);
   int nf[2] = {nq, nm}, cq = 0, cm = 1;
-  uint32_t* d_desc = nullptr;
-  int *d_nf = nullptr, *d_c = nullptr, *d_K = nullptr;
-  int2* d_pairs = nullptr;
-  auto cleanup = [&]() {
-    if (d_desc) (void)hipFree(d_desc);
-    if (d_nf) (void)hipFree(d_nf);
-    if (d_c) (void)hipFree(d_c);
-    if (d_K) (void)hipFree(d_K);
-    if (d_pairs) (void)hipFree(d_pairs);
-  };
-  if (hipMalloc(&d_desc, pool.size()) != hipSuccess || hipMalloc(&d_nf, sizeof(nf)) != hipSuccess ||
-      hipMalloc(&d_c, 2 * sizeof(int)) != hipSuccess || hipMalloc(&d_K, sizeof(int)) != hipSuccess ||
-      hipMalloc(&d_pairs, sizeof(int2) * N) != hipSuccess) {
-    cleanup();
-    return kmx::fail(KMX_ENOMEM, "hipMalloc");
-  }
+  kmx::DevBuf<uint32_t> d_desc;
+  kmx::DevBuf<int> d_nf, d_c, d_K;
+  kmx::DevBuf<int2> d_pairs;
+  int rc = 0;
+  if ((rc = d_desc.alloc(pool.size() / 4)) || (rc = d_nf.alloc(2)) || (rc = d_c.alloc(2)) || (rc = d_K.alloc(1)) ||
+      (rc = d_pairs.alloc(N)))
+    return rc;
   int cc[2] = {cq, cm};
-  hipError_t e = hipMemcpy(d_desc, pool.data(), pool.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_nf, nf, sizeof(nf), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_c, cc, sizeof(cc), hipMemcpyHostToDevice);
+  hipError_t e = hipMemcpy(d_desc.get(), pool.data(), pool.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_nf.get(), nf, sizeof(nf), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_c.get(), cc, sizeof(cc), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_knn2, dim3(1), dim3(KNN_BLOCK), (size_t)N * 32 + sizeof(int) * (KNN_BLOCK + 1), 0,
-                       (const uint32_t*)d_desc, (const int*)d_nf, N, (const int*)d_c, (const int*)(d_c + 1), norm,
-                       lowe_ratio, d_pairs, d_K);
+                       (const uint32_t*)d_desc.get(), (const int*)d_nf.get(), N, (const int*)d_c.get(),
+                       (const int*)(d_c.get() + 1), norm, lowe_ratio, d_pairs.get(), d_K.get());
     e = hipGetLastError();
   }
   int K = 0;
   std::vector<int2> pr(N);
-  if (e == hipSuccess) e = hipMemcpy(&K, d_K, sizeof(int), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && K > 0) e = hipMemcpy(pr.data(), d_pairs, sizeof(int2) * K, hipMemcpyDeviceToHost);
-  cleanup();
+  if (e == hipSuccess) e = hipMemcpy(&K, d_K.get(), sizeof(int), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && K > 0) e = hipMemcpy(pr.data(), d_pairs.get(), sizeof(int2) * K, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return kmx::fail(KMX_EHIP, hipGetErrorString(e));
   for (int i = 0; i < K; ++i) {
     pairs_out[2 * i] = pr[i].x;

@@ -50,6 +50,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <numeric>
 #include <string>
 #include <vector>
@@ -3110,11 +3111,64 @@ __global__ __launch_bounds__(BLOCK, LB<R>::w) void k_eval(Dev d, int robot, int 
 }  // namespace
 
 // ============================================================ handle =====
-struct kmx_pgo {
+// The graph's device buffers: replaced together by kmx_pgo_set_graph, which
+// builds a fresh set aside and commits it by move once its uploads are done.
+struct PgoDev {
+  template <class T>
+  using DevBuf = kmx::DevBuf<T>;
+  DevBuf<TileDesc> tile;
+  DevBuf<int> rtile0, inc_ptr;
+  DevBuf<double> rec;
+  DevBuf<int> rec_o;
+  DevBuf<double> ekappa, etau, ew;
+  DevBuf<int2> eipos;
+  DevBuf<double> vec;     // X Xt g r z hd eta, then the dhn tCG directions (nvec())
+  DevBuf<double> coefh;   // [L][tcg_max]
+  DevBuf<double> part_f;  // [ntiles][8] one-sync tCG partials (P.tcg_form)
+  DevBuf<double> S, Pinv, hD, hDS, pub, part;
+  DevBuf<Ctl> ctl, ctl2;
+  DevBuf<double> part_h, part_u;
+  DevBuf<Counters> cnt;
+  DevBuf<long long> m_robot;
+  DevBuf<int> n_robot;
+  DevBuf<int> pub_src;    // slot -> local pose (-1 if not local)
+  DevBuf<int> own_src;    // owned slot k -> local pose (index first_owned + k)
+  DevBuf<int> pose_slot;  // local pose -> owned slot or -1
+  DevBuf<int> gnc_edge;
+  DevBuf<int2> gnc_ends;
+  DevBuf<int> sh_edge, sh_idx, osh_edge, osh_idx;
+  DevBuf<double> relc;
+  DevBuf<Gnc> gnc;  // [2]: state, next
+  DevBuf<double> ext;
+  DevBuf<unsigned char> active;
+  DevBuf<double> scratch;  // eval / trajectory in-out, allocated on first use
+  DevBuf<int> hv_launch;   // timing
+  // Nesterov acceleration (P.acceleration): momentum V and this round's Y
+  // (allocated only when enabled)
+  DevBuf<double> accV, accY;
+  // X at the start of the round, kept when a block update runs several RTR
+  // iterations (k_change: its relative change is against this point)
+  DevBuf<double> X0;
+};
+// The native exchange's buffers (kmx_pgo_set_exchange), replaced together.
+struct PgoXchg {
+  kmx::DevBuf<int> xs_slots, xr_slots, xs_seg, xr_seg;
+  kmx::DevBuf<int> xs_rseg, xr_rseg;  // segment index of every row
+  kmx::DevBuf<double> xsbuf, xrbuf;
+};
+
+struct kmx_pgo : kmx::StreamCore {
   kmx_pgo_params P{};
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+  // The group streams and the events stand before the buffers: the buffers
+  // are destroyed first, then these, then the base's stream.
+  static constexpr int MAX_GROUPS = 4;
+  kmx::Stream gstream[MAX_GROUPS - 1];
+  kmx::Event ev_fork, ev_join[MAX_GROUPS - 1];
+  std::vector<kmx::Event> ev_pool;  // timing
+  size_t ev_used = 0;
+  ~kmx_pgo() {
+    if (comm) (void)ncclCommAbort(comm);  // non-blocking communicator: no finalize handshake at teardown
+  }
   // team
   int n_robots = 0;
   std::vector<int> npose;
@@ -3140,42 +3194,11 @@ struct kmx_pgo {
   int gnc_on = 0, gnc_inner_iters = 20, gnc_max_updates = 0x7fffffff, n_ext = 0;
   double gnc_rel_tol = 1e-3;
   // device
-  Dev dv{};
-  TileDesc* d_tile = nullptr;
-  int* d_rtile0 = nullptr;
-  int* d_inc_ptr = nullptr;
-  double* d_rec = nullptr;
-  int* d_rec_o = nullptr;
-  double *d_ekappa = nullptr, *d_etau = nullptr, *d_ew = nullptr;
-  int2* d_eipos = nullptr;
-  double* d_vec = nullptr;  // X Xt g r z hd eta, then the dhn tCG directions (nvec())
-  double* d_coefh = nullptr;  // [L][tcg_max]
-  double* d_part_f = nullptr;  // [ntiles][8] one-sync tCG partials (P.tcg_form)
-  int ctl_par = 0;             // one-sync tCG: the state after the last tCG loop is in ctl2 (odd step count)
-  double *d_S = nullptr, *d_Pinv = nullptr, *d_hD = nullptr, *d_hDS = nullptr, *d_pub = nullptr, *d_part = nullptr;
-  Ctl* d_ctl = nullptr;
-  Ctl* d_ctl2 = nullptr;
-  double *d_part_h = nullptr, *d_part_u = nullptr;
-  Counters* d_cnt = nullptr;
-  long long* d_m_robot = nullptr;
-  int* d_n_robot = nullptr;
-  int* d_pub_src = nullptr;    // slot -> local pose (-1 if not local)
-  int* d_own_src = nullptr;    // owned slot k -> local pose (index first_owned + k)
-  int* d_pose_slot = nullptr;  // local pose -> owned slot or -1
-  int* d_gnc_edge = nullptr;
-  int2* d_gnc_ends = nullptr;
-  int *d_sh_edge = nullptr, *d_sh_idx = nullptr;
-  int *d_osh_edge = nullptr, *d_osh_idx = nullptr;
-  double* d_relc = nullptr;
-  Gnc* d_gnc = nullptr;  // [2]: state, next
-  double* d_ext = nullptr;
-  int ext_cap = 0;
-  unsigned char* d_active = nullptr;
-  double* d_scratch = nullptr;  // eval / trajectory in-out, allocated on first use
-  size_t scratch_cap = 0;
-  // tCG progress polling (see HostStatus)
-  HostStatus* hstat = nullptr;
-  int hstat_cap = 0;
+  Dev dv{};    // what the kernels take: gd's pointers (filled by set_graph alone)
+  PgoDev gd;   // gd.vec null: no graph (ready())
+  int ctl_par = 0;  // one-sync tCG: the state after the last tCG loop is in ctl2 (odd step count)
+  // tCG progress polling (see HostStatus): mapped, coherent; the kernels take the host pointer itself
+  kmx::MappedBuf<HostStatus> hstat;
   unsigned long long seq = 0;
   bool poll = true;          // kmx_pgo_set_tcg_poll(0): enqueue every tCG step (finished robots exit at once)
   // kmx_pgo_set_tcg_poll(-1) (the default): adaptive. A polled tCG loop
@@ -3195,9 +3218,7 @@ struct kmx_pgo {
   ncclComm_t comm = nullptr;
   int world = 1, rank = 0;
   bool xchg = false, xchg_self_p2p = false;
-  int *d_xs_slots = nullptr, *d_xr_slots = nullptr, *d_xs_seg = nullptr, *d_xr_seg = nullptr;
-  int *d_xs_rseg = nullptr, *d_xr_rseg = nullptr;  // segment index of every row
-  double *d_xsbuf = nullptr, *d_xrbuf = nullptr;
+  PgoXchg xd;
   long long xn_send = 0, xn_recv = 0;
   std::vector<long long> xs_cnt, xr_cnt, xs_off, xr_off;  // per peer, in doubles (rows * 4r + 1 status)
   static constexpr int BLIND_SLACK = 2, BLIND_WINDOW = 8;  // the window's state: Group::blind_left
@@ -3215,7 +3236,6 @@ struct kmx_pgo {
   // the grouping (its tiles and the order of its tile partials are the same).
   // In effect for RM_LAUNCH and RTR only, and not while timing is on (the
   // evented replay wants launches that do not overlap).
-  static constexpr int MAX_GROUPS = 4;
   struct Group {
     int l0 = 0, l1 = 0;  // local robots [l0, l1)
     int t0 = 0, nt = 0;  // their tiles [t0, t0 + nt)
@@ -3233,8 +3253,6 @@ struct kmx_pgo {
   // GROUP_CONSUMER_MAX_TILES tiles (pgo_host.h, with the measurements).
   int grm = 2;
   int grm_forced = -1;
-  hipStream_t gstream[MAX_GROUPS - 1] = {nullptr, nullptr, nullptr};
-  hipEvent_t ev_fork = nullptr, ev_join[MAX_GROUPS - 1] = {nullptr, nullptr, nullptr};
   // Gated k_hess launches (KMX_HESS_GATE=0: off): every k_hess launch after a
   // tCG's first tests its robot's phase before its first record chunk is
   // fetched. Ungated, a launch enqueued before the host knows whether any robot
@@ -3265,15 +3283,7 @@ struct kmx_pgo {
   bool poll_timeout = false;
   // timing
   bool timing = false;
-  int* d_hv_launch = nullptr;
-  std::vector<hipEvent_t> ev_pool;
-  size_t ev_used = 0;
-  // Nesterov acceleration (P.acceleration): momentum V and this round's Y
-  // (allocated only when enabled), gamma and the restart counter on the host
-  double *d_accV = nullptr, *d_accY = nullptr;
-  // X at the start of the round, kept when a block update runs several RTR
-  // iterations (k_change: its relative change is against this point)
-  double* d_X0 = nullptr;
+  // Nesterov acceleration (P.acceleration): gamma and the restart counter on the host
   double acc_gamma = 0.0;
   int acc_k = 0;
   bool acc_ready = false, acc_started = false;
@@ -3281,37 +3291,9 @@ struct kmx_pgo {
 
 namespace {
 
-template <typename T>
-int dalloc(T** p, size_t count) {
-  *p = nullptr;
-  if (count == 0) count = 1;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * count);
-  if (e != hipSuccess) return kmx::fail(KMX_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-  return 0;
-}
-
-// hipFree and null every buffer of a list: a buffer is named once here
-// besides its allocation.
-template <typename... T>
-void free_all(T*&... p) {
-  (((p ? (void)hipFree(p) : (void)0), p = nullptr), ...);
-}
-
-void free_xchg(kmx_pgo* h) {
-  free_all(h->d_xs_slots, h->d_xr_slots, h->d_xs_seg, h->d_xr_seg, h->d_xs_rseg, h->d_xr_rseg, h->d_xsbuf,
-           h->d_xrbuf);
+void drop_xchg(kmx_pgo* h) {
+  h->xd = {};
   h->xchg = false;
-}
-
-void free_dev(kmx_pgo* h) {
-  free_all(h->d_tile, h->d_rtile0, h->d_inc_ptr, h->d_rec, h->d_rec_o, h->d_ekappa, h->d_etau, h->d_ew, h->d_eipos,
-           h->d_vec, h->d_S, h->d_Pinv, h->d_hD, h->d_hDS, h->d_pub, h->d_part, h->d_ctl, h->d_cnt, h->d_m_robot,
-           h->d_n_robot, h->d_pub_src, h->d_own_src, h->d_pose_slot, h->d_gnc_edge, h->d_gnc_ends, h->d_sh_edge,
-           h->d_sh_idx, h->d_osh_edge, h->d_osh_idx, h->d_relc, h->d_gnc, h->d_ext, h->d_active, h->d_scratch,
-           h->d_hv_launch, h->d_accV, h->d_accY, h->d_ctl2, h->d_part_h, h->d_part_u, h->d_coefh, h->d_part_f,
-           h->d_X0);
-  h->ext_cap = 0;
-  h->scratch_cap = 0;
 }
 
 // The kernels' compile-time sizes from the handle's run-time ones: f is
@@ -3336,14 +3318,13 @@ void with_rw(int rw, F&& f) {
 
 hipEvent_t next_event(kmx_pgo* h) {
   if (h->ev_used == h->ev_pool.size()) {
-    hipEvent_t e;
-    (void)hipEventCreate(&e);
-    h->ev_pool.push_back(e);
+    h->ev_pool.emplace_back();
+    (void)h->ev_pool.back().create();
   }
   return h->ev_pool[h->ev_used++];
 }
 
-bool ready(kmx_pgo* h) { return h && h->d_vec != nullptr; }
+bool ready(kmx_pgo* h) { return h && h->gd.vec.get() != nullptr; }
 
 // Vectors of d_vec: X Xt g r z hd eta + the tCG directions kept for k_retract
 // (+ Hz, w_0, w_1 for the one-sync tCG, which needs two directions).
@@ -3359,17 +3340,12 @@ size_t nvec(const kmx_pgo* h) { return 7 + (size_t)dh_count(h) + (onesync(h) ? 3
 
 // Scratch of the diagnostic / output entry points (not resident with the graph).
 int ensure_scratch(kmx_pgo* h, size_t doubles) {
-  if (doubles <= h->scratch_cap) return 0;
-  if (h->d_scratch) {
-    KMX_HIP(hipStreamSynchronize(h->stream));
-    (void)hipFree(h->d_scratch);
-  }
-  h->d_scratch = nullptr;
-  h->scratch_cap = 0;
-  if (int rc = dalloc(&h->d_scratch, doubles)) return rc;
-  h->scratch_cap = doubles;
-  return 0;
+  if (doubles <= h->gd.scratch.cap()) return 0;
+  if (h->gd.scratch.get()) KMX_HIP(hipStreamSynchronize(h->stream));
+  h->gd.scratch = {};
+  return h->gd.scratch.alloc(doubles);
 }
+
 
 void sync_params(kmx_pgo* h) {
   Params& p = h->dv.p;
@@ -3393,7 +3369,17 @@ void sync_params(kmx_pgo* h) {
   p.n_ext = h->n_ext;
   p.rgd = h->P.method == KMX_METHOD_RGD ? 1 : 0;
   p.rgd_step = h->P.rgd_stepsize;
-  h->dv.ext = h->d_ext;
+  h->dv.ext = h->gd.ext.get();
+}
+
+// Room for n peers' status words. The stream's work is done before the old
+// words go; a failure changes nothing, and the kernels' copy of the pointer follows.
+int ensure_ext(kmx_pgo* h, size_t n) {
+  if (n <= h->gd.ext.cap()) return 0;
+  KMX_HIP(hipStreamSynchronize(h->stream));
+  if (int rc = h->gd.ext.alloc(n)) return rc;
+  sync_params(h);
+  return 0;
 }
 
 // Owned public rows into the table (the single-device exchange).
@@ -3401,8 +3387,9 @@ void enqueue_publish(kmx_pgo* h) {
   const int ps = 4 * h->P.r;
   const long long tot = h->n_owned * ps;
   if (tot == 0) return;
-  hipLaunchKernelGGL(k_publish, dim3((unsigned)((tot / 2 + 255) / 256)), dim3(256), 0, h->stream, h->d_vec,
-                     h->d_pub + (size_t)h->first_owned * ps, h->d_pub_src + h->first_owned, (int)h->n_owned, ps);
+  hipLaunchKernelGGL(k_publish, dim3((unsigned)((tot / 2 + 255) / 256)), dim3(256), 0, h->stream, h->gd.vec.get(),
+                     h->gd.pub.get() + (size_t)h->first_owned * ps, h->gd.pub_src.get() + h->first_owned,
+                     (int)h->n_owned, ps);
 }
 
 void enqueue_precond(kmx_pgo* h, int gated) {
@@ -3439,7 +3426,7 @@ bool enqueue_begin(kmx_pgo* h, const unsigned char* d_active, int mode, bool def
 // returns whether any of them is still in tCG. A device that stops reporting
 // for 30 s switches the handle to blind enqueueing (every tCG step launched).
 bool wait_running(kmx_pgo* h, unsigned long long seq, int l0, int l1) {
-  volatile HostStatus* hs = h->hstat;
+  volatile HostStatus* hs = h->hstat.get();
   const auto t0 = std::chrono::steady_clock::now();
   bool running = false;
   for (int l = l0; l < l1; ++l) {
@@ -3514,7 +3501,7 @@ Timed next_timed(kmx_pgo* h) {
 // Whether a chain's next tCG loop polls or goes blind, and what a loop that
 // enqueued `steps` steps means for the next ones (see kmx_pgo::poll_auto).
 bool tcg_polls(kmx_pgo* h, kmx_pgo::Group& st) {
-  if (!(h->poll && h->hstat)) return false;
+  if (!(h->poll && h->hstat.get())) return false;
   if (h->poll_auto && st.blind_left > 0) {
     --st.blind_left;
     return false;
@@ -3611,7 +3598,7 @@ void enqueue_tcg_t(kmx_pgo* h, const Chain* q, int G, bool* stopped) {
       const Timed t = next_timed(h);  // timing runs one chain (groups_in_effect)
       poll[g] = poll[g] && h->poll;   // a poll timeout inside wait_running switches to blind
       seq[g] = poll[g] ? ++h->seq : 0;
-      HostStatus* hs = poll[g] ? h->hstat : nullptr;
+      HostStatus* hs = poll[g] ? h->hstat.get() : nullptr;
       const int fl = (j == 0 ? 1 : 0) | (j > 0 && h->hess_gate ? 2 : 0);
       const dim3 grid(q[g].d.gnt);
       if constexpr (cons) {
@@ -3665,9 +3652,9 @@ void enqueue_tcg_onesync_t(kmx_pgo* h, const Chain& q) {
     const Timed t = next_timed(h);
     poll = poll && h->poll;
     const unsigned long long seq = poll ? ++h->seq : 0;
-    HostStatus* hs = poll ? h->hstat : nullptr;
-    const Ctl* cin = (j & 1) ? h->d_ctl2 : h->d_ctl;
-    Ctl* cout = (j & 1) ? h->d_ctl : h->d_ctl2;
+    HostStatus* hs = poll ? h->hstat.get() : nullptr;
+    const Ctl* cin = (j & 1) ? h->gd.ctl2.get() : h->gd.ctl.get();
+    Ctl* cout = (j & 1) ? h->gd.ctl.get() : h->gd.ctl2.get();
     if (t.e0)
       hipExtLaunchKernelGGL((k_step<R, RW>), grid, blk, SmemF<R>::bytes, q.s, t.e0, t.e1, 0u, q.d, cin, cout, j,
                             t.slot, hs, seq);
@@ -3708,7 +3695,8 @@ void enqueue_round_t(kmx_pgo* h, const unsigned char* d_active, int G) {
   // the round's start for k_change (on the handle's stream, ahead of the begin
   // launch the side streams wait for)
   if (multi_rtr(h))
-    (void)hipMemcpyAsync(h->d_X0, h->dv.X, sizeof(double) * (size_t)h->dv.vec, hipMemcpyDeviceToDevice, h->stream);
+    (void)hipMemcpyAsync(h->gd.X0.get(), h->dv.X, sizeof(double) * (size_t)h->dv.vec, hipMemcpyDeviceToDevice,
+     h->stream);
   // the round's first k_grad runs the gated preconditioner rebuild (there is
   // one: set_graph refuses a graph without tiles)
   const bool pend = enqueue_begin(h, d_active, BEGIN_ROUND, true, G > 1 ? h->ev_fork : nullptr);
@@ -3734,7 +3722,7 @@ void enqueue_round_t(kmx_pgo* h, const unsigned char* d_active, int G) {
     // one-sync: each k_step that ended a robot's tCG also formed its trial
     // point, so there is no k_retract; k_cost takes the state from where the
     // tCG left it
-    const Ctl* src = os && h->ctl_par ? h->d_ctl2 : h->d_ctl;
+    const Ctl* src = os && h->ctl_par ? h->gd.ctl2.get() : h->gd.ctl.get();
     for (int g = 0; g < G; ++g) {
       const dim3 grid(q[g].d.gnt);
       const bool last = it + 1 == iters;
@@ -3747,7 +3735,7 @@ void enqueue_round_t(kmx_pgo* h, const unsigned char* d_active, int G) {
       // loop saw the chain's robots stop
       if (!os && !(cons && stopped[g]) && !tail_fused<RM>(h))
         hipLaunchKernelGGL((k_retract<R>), grid, blk, SmemU::bytes, q[g].s, q[g].d, cons && !rgd ? 2 : 0,
-                           (const Ctl*)h->d_ctl);
+                           (const Ctl*)h->gd.ctl.get());
       if (fcost && join)  // the side stream's last dispatch: the join event completes with it
         hipExtLaunchKernelGGL((k_cost<R, RW, RM>), grid, blk, SmemC<R>::bytes, q[g].s, nullptr, join, 0u, q[g].d, src);
       else
@@ -3760,7 +3748,7 @@ void enqueue_round_t(kmx_pgo* h, const unsigned char* d_active, int G) {
   for (int g = 1; g < G; ++g) (void)hipStreamWaitEvent(h->stream, h->ev_join[g - 1], 0);
   hipLaunchKernelGGL((k_commit<R>), dim3(h->ntiles), blk, 0, h->stream, h->dv, fcost ? 1 : 0, 1);
   if (multi_rtr(h))
-    hipLaunchKernelGGL(k_change, dim3(h->dv.L), blk, 0, h->stream, h->dv, (const double*)h->d_X0, 4 * R);
+    hipLaunchKernelGGL(k_change, dim3(h->dv.L), blk, 0, h->stream, h->dv, (const double*)h->gd.X0.get(), 4 * R);
 }
 
 // One RBCD round for the robots whose d_active flag is set; it starts with
@@ -3788,7 +3776,8 @@ double accel_gamma_next(const kmx_pgo* h) {
 }
 void launch_accel(kmx_pgo* h, double c, int mode) {
   with_r(h->P.r, [&](auto R) {
-    hipLaunchKernelGGL(k_accel<R()>, dim3(h->ntiles), dim3(BLOCK), 0, h->stream, h->dv, h->d_accV, h->d_accY, c, mode);
+    hipLaunchKernelGGL(k_accel<R()>, dim3(h->ntiles), dim3(BLOCK), 0, h->stream, h->dv, h->gd.accV.get(),
+                       h->gd.accY.get(), c, mode);
   });
 }
 // Y for the upcoming round (X := Y, owned public rows := Y); once per round.
@@ -3846,19 +3835,9 @@ extern "C" int kmx_pgo_create(const kmx_pgo_params* params, int device, kmx_pgo*
             "tcg_form must be KMX_TCG_FORM_STANDARD or KMX_TCG_FORM_ONESYNC");
   KMX_CHECK(params->method != KMX_METHOD_RGD || params->rgd_stepsize > 0.0, KMX_EINVAL, "rgd_stepsize must be > 0");
   KMX_CHECK(params->tile_incidences >= 0, KMX_EINVAL, "tile_incidences must be >= 0 (0: automatic)");
-  int ndev = 0;
-  KMX_HIP(hipGetDeviceCount(&ndev));
-  KMX_CHECK(device >= 0 && device < ndev, KMX_EINVAL, "bad HIP device ordinal");
-  KMX_HIP(hipSetDevice(device));
-  kmx_pgo* h = new kmx_pgo();
+  auto h = std::make_unique<kmx_pgo>();
+  if (int rc = h->open(device)) return rc;
   h->P = *params;
-  h->device = device;
-  hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    delete h;
-    return kmx::fail(KMX_EHIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
-  }
-  h->own_stream = true;
   if (const char* v = std::getenv("KMX_RED")) {
     const int m = std::atoi(v);
     h->rm_forced = m == 0 ? RM_LAUNCH : m == 2 ? RM_CONSUMER : -1;  // 1 and 3 (tickets, half) were removed
@@ -3872,16 +3851,13 @@ extern "C" int kmx_pgo_create(const kmx_pgo_params* params, int device, kmx_pgo*
   }
   if (const char* v = std::getenv("KMX_GROUP_RED")) h->grm_forced = std::atoi(v) == 2 ? RM_CONSUMER : RM_LAUNCH;
   // the side streams of the robot groups (group 0 runs on the handle's stream)
-  for (int g = 1; g < h->groups_req && e == hipSuccess; ++g) {
-    e = hipStreamCreateWithFlags(&h->gstream[g - 1], hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreate(&h->ev_join[g - 1]);
+  for (int g = 1; g < h->groups_req; ++g) {
+    if (int rc = h->gstream[g - 1].create()) return rc;
+    if (int rc = h->ev_join[g - 1].create()) return rc;
   }
-  if (e == hipSuccess && h->groups_req > 1) e = hipEventCreate(&h->ev_fork);
-  if (e != hipSuccess) {
-    (void)kmx_pgo_destroy(h);
-    return kmx::fail(KMX_EHIP, std::string("robot group streams: ") + hipGetErrorString(e));
-  }
-  *out = h;
+  if (h->groups_req > 1)
+    if (int rc = h->ev_fork.create()) return rc;
+  *out = h.release();
   return KMX_OK;
   KMX_GUARD_END
 }
@@ -3892,31 +3868,13 @@ extern "C" int kmx_pgo_destroy(kmx_pgo* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (hipStream_t s : h->gstream)
     if (s) (void)hipStreamSynchronize(s);
-  free_dev(h);
-  free_xchg(h);
-  if (h->comm) (void)ncclCommAbort(h->comm);  // non-blocking communicator: no finalize handshake at teardown
-  for (auto e : h->ev_pool) (void)hipEventDestroy(e);
-  if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-  if (h->hstat) (void)hipHostFree(h->hstat);
-  for (hipStream_t s : h->gstream)
-    if (s) (void)hipStreamDestroy(s);
-  for (hipEvent_t ev : h->ev_join)
-    if (ev) (void)hipEventDestroy(ev);
-  if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-  delete h;
+  delete h;  // ~kmx_pgo aborts the communicator before any buffer or stream goes
   return KMX_OK;
 }
 
 extern "C" int kmx_pgo_set_stream(kmx_pgo* h, void* s) {
   KMX_CHECK(h, KMX_EINVAL, "null handle");
-  KMX_HIP(hipSetDevice(h->device));
-  if (h->own_stream && h->stream) {
-    KMX_HIP(hipStreamSynchronize(h->stream));
-    KMX_HIP(hipStreamDestroy(h->stream));
-  }
-  h->own_stream = false;
-  h->stream = reinterpret_cast<hipStream_t>(s);
-  return KMX_OK;
+  return h->adopt(s, false);
 }
 
 extern "C" int kmx_pgo_set_tcg_poll(kmx_pgo* h, int mode) {
@@ -3989,8 +3947,8 @@ extern "C" int kmx_pgo_set_graph(kmx_pgo* h, int n_robots, const int32_t* n_pose
     return kmx::fail(rc, err);
   KMX_HIP(hipSetDevice(h->device));
   KMX_HIP(hipStreamSynchronize(h->stream));
-  free_dev(h);
-  free_xchg(h);  // the exchange slot lists index this graph's public table
+  h->gd = {};  // dropped before the new set is allocated: the peak matters at 1M poses
+  drop_xchg(h);  // the exchange slot lists index this graph's public table
   accel_reset(h);
   // the plan's host fields
   const int r = h->P.r, ps = 4 * r;
@@ -4029,107 +3987,101 @@ extern "C" int kmx_pgo_set_graph(kmx_pgo* h, int n_robots, const int32_t* n_pose
   // the single chain (its polling state outlives the graph, as the handle's poll mode)
   h->all.l0 = 0; h->all.l1 = L;
   h->all.t0 = 0; h->all.nt = h->ntiles;
-  // device
-  int rc;
-  const size_t vec = (size_t)std::max(nloc, 1) * ps;
-  if ((rc = dalloc(&h->d_tile, h->ntiles)) || (rc = dalloc(&h->d_rtile0, L + 1)) ||
-      (rc = dalloc(&h->d_inc_ptr, nloc + 1)) || (rc = dalloc(&h->d_rec, plan.rec.size())) ||
-      (rc = dalloc(&h->d_rec_o, plan.rec_o.size())) || (rc = dalloc(&h->d_ekappa, plan.ek.size())) ||
-      (rc = dalloc(&h->d_etau, plan.et.size())) || (rc = dalloc(&h->d_ew, plan.ew.size())) ||
-      (rc = dalloc(&h->d_eipos, plan.eipos.size())) ||
-      (rc = dalloc(&h->d_vec, vec * nvec(h))) || (rc = dalloc(&h->d_S, (size_t)std::max(nloc, 1) * 6)) ||
-      (rc = dalloc(&h->d_Pinv, (size_t)std::max(nloc, 1) * SYM4)) ||
-      (rc = dalloc(&h->d_hD, (size_t)std::max(nloc, 1) * SYM4)) ||
-      (rc = dalloc(&h->d_hDS, (size_t)std::max(nloc, 1) * SYM4)) ||
-      (rc = dalloc(&h->d_pub, (size_t)std::max<int64_t>(h->npub, 1) * ps)) ||
-      (h->P.acceleration && ((rc = dalloc(&h->d_accV, vec)) || (rc = dalloc(&h->d_accY, vec)))) ||
-      (multi_rtr(h) && (rc = dalloc(&h->d_X0, vec))) ||
-      (rc = dalloc(&h->d_part, (size_t)h->ntiles * NPART)) || (rc = dalloc(&h->d_ctl, L)) ||
-      (rc = dalloc(&h->d_ctl2, L)) || (rc = dalloc(&h->d_part_h, (size_t)h->ntiles * 2)) ||
-      (rc = dalloc(&h->d_part_u, (size_t)h->ntiles * 2)) ||
-      (rc = dalloc(&h->d_cnt, 1)) || (rc = dalloc(&h->d_m_robot, L)) ||
-      (rc = dalloc(&h->d_n_robot, L)) || (rc = dalloc(&h->d_pub_src, plan.pub_src.size())) ||
-      (rc = dalloc(&h->d_own_src, plan.own_src.size())) || (rc = dalloc(&h->d_pose_slot, plan.pose_slot.size())) ||
-      (rc = dalloc(&h->d_gnc_edge, std::max(h->n_gnc, 1))) || (rc = dalloc(&h->d_gnc_ends, std::max(h->n_gnc, 1))) ||
-      (rc = dalloc(&h->d_sh_edge, std::max(h->n_sh_local, 1))) ||
-      (rc = dalloc(&h->d_sh_idx, std::max(h->n_sh_local, 1))) || (rc = dalloc(&h->d_active, L)) ||
-      (rc = dalloc(&h->d_osh_edge, std::max(h->n_osh, 1))) || (rc = dalloc(&h->d_osh_idx, std::max(h->n_osh, 1))) ||
-      (rc = dalloc(&h->d_relc, L)) || (rc = dalloc(&h->d_gnc, 2)) || (rc = dalloc(&h->d_ext, 64)) ||
-      (rc = dalloc(&h->d_hv_launch, HV_SLOTS)) ||
-      (rc = dalloc(&h->d_coefh, (size_t)L * std::max(h->P.tcg_max_iterations, 1))) ||
-      (onesync(h) && (rc = dalloc(&h->d_part_f, (size_t)h->ntiles * 16)))) {
-    free_dev(h);
-    return rc;
-  }
-  h->ext_cap = 64;
-  KMX_HIP(upload(h, h->d_tile, plan.tile));
-  KMX_HIP(upload(h, h->d_rtile0, plan.rt0));
-  KMX_HIP(upload(h, h->d_inc_ptr, plan.inc_ptr));
-  KMX_HIP(upload(h, h->d_rec, plan.rec));
-  KMX_HIP(upload(h, h->d_rec_o, plan.rec_o));
-  KMX_HIP(upload(h, h->d_ekappa, plan.ek));
-  KMX_HIP(upload(h, h->d_etau, plan.et));
-  KMX_HIP(upload(h, h->d_ew, plan.ew));
-  KMX_HIP(upload(h, h->d_eipos, plan.eipos));
-  KMX_HIP(hipMemsetAsync(h->d_vec, 0, sizeof(double) * vec * nvec(h), h->stream));
-  KMX_HIP(hipMemsetAsync(h->d_coefh, 0, sizeof(double) * L * std::max(h->P.tcg_max_iterations, 1), h->stream));
-  KMX_HIP(hipMemsetAsync(h->d_pub, 0, sizeof(double) * std::max<int64_t>(h->npub, 1) * ps, h->stream));
-  KMX_HIP(hipMemsetAsync(h->d_ctl, 0, sizeof(Ctl) * L, h->stream));
-  KMX_HIP(hipMemsetAsync(h->d_cnt, 0, sizeof(Counters), h->stream));
-  KMX_HIP(hipMemsetAsync(h->d_ext, 0, sizeof(double) * 64, h->stream));
-  KMX_HIP(hipMemsetAsync(h->d_hv_launch, 0, sizeof(int) * HV_SLOTS, h->stream));
-  if (L > h->hstat_cap) {  // host-mapped per-robot tCG progress
-    if (h->hstat) (void)hipHostFree(h->hstat);
-    h->hstat = nullptr;
-    h->hstat_cap = 0;
-    KMX_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->hstat), sizeof(HostStatus) * L,
-                          hipHostMallocMapped | hipHostMallocCoherent));
-    h->hstat_cap = L;
-  }
-  for (int l = 0; l < L; ++l) h->hstat[l].word = 0;
-  h->seq = 0;
+  // device: the new set is built aside. A failure from here on leaves the
+  // handle with no graph (ready() false); the host vectors the uploads read
+  // are declared before the set, so a set that goes early goes before them
+  // (releasing a device buffer waits for the copies)
+  const size_t vec = (size_t)std::max(nloc, 1) * ps, n1 = (size_t)std::max(nloc, 1);
   std::vector<double> relc(L);  // no block update yet: not converged (an empty block is)
   for (int l = 0; l < L; ++l) relc[l] = plan.nrob[l] > 0 ? std::numeric_limits<double>::infinity() : 0.0;
-  KMX_HIP(upload(h, h->d_relc, relc));
   std::vector<Gnc> g0(2, Gnc{});
   g0[0].mu = g0[1].mu = h->P.gnc_mu_init;
-  KMX_HIP(upload(h, h->d_gnc, g0));
-  KMX_HIP(upload(h, h->d_m_robot, h->m_robot));
-  KMX_HIP(upload(h, h->d_n_robot, plan.nrob));
-  KMX_HIP(upload(h, h->d_pub_src, plan.pub_src));
-  KMX_HIP(upload(h, h->d_own_src, plan.own_src));
-  KMX_HIP(upload(h, h->d_pose_slot, plan.pose_slot));
-  KMX_HIP(upload(h, h->d_gnc_edge, plan.gnc_edge));
-  KMX_HIP(upload(h, h->d_gnc_ends, plan.gnc_ends));
-  KMX_HIP(upload(h, h->d_sh_edge, plan.sh_edge));
-  KMX_HIP(upload(h, h->d_sh_idx, plan.sh_idx));
-  KMX_HIP(upload(h, h->d_osh_edge, plan.osh_edge));
-  KMX_HIP(upload(h, h->d_osh_idx, plan.osh_idx));
   const std::vector<unsigned char> ones(L, 1);
-  KMX_HIP(upload(h, h->d_active, ones));
+  PgoDev nd;
+  int rc;
+  if ((rc = nd.tile.alloc(h->ntiles)) || (rc = nd.rtile0.alloc(L + 1)) || (rc = nd.inc_ptr.alloc(nloc + 1)) ||
+      (rc = nd.rec.alloc(plan.rec.size())) || (rc = nd.rec_o.alloc(plan.rec_o.size())) ||
+      (rc = nd.ekappa.alloc(plan.ek.size())) || (rc = nd.etau.alloc(plan.et.size())) ||
+      (rc = nd.ew.alloc(plan.ew.size())) || (rc = nd.eipos.alloc(plan.eipos.size())) ||
+      (rc = nd.vec.alloc(vec * nvec(h))) || (rc = nd.S.alloc(n1 * 6)) || (rc = nd.Pinv.alloc(n1 * SYM4)) ||
+      (rc = nd.hD.alloc(n1 * SYM4)) || (rc = nd.hDS.alloc(n1 * SYM4)) ||
+      (rc = nd.pub.alloc((size_t)std::max<int64_t>(h->npub, 1) * ps)) ||
+      (h->P.acceleration && ((rc = nd.accV.alloc(vec)) || (rc = nd.accY.alloc(vec)))) ||
+      (multi_rtr(h) && (rc = nd.X0.alloc(vec))) || (rc = nd.part.alloc((size_t)h->ntiles * NPART)) ||
+      (rc = nd.ctl.alloc(L)) || (rc = nd.ctl2.alloc(L)) || (rc = nd.part_h.alloc((size_t)h->ntiles * 2)) ||
+      (rc = nd.part_u.alloc((size_t)h->ntiles * 2)) || (rc = nd.cnt.alloc(1)) || (rc = nd.m_robot.alloc(L)) ||
+      (rc = nd.n_robot.alloc(L)) || (rc = nd.pub_src.alloc(plan.pub_src.size())) ||
+      (rc = nd.own_src.alloc(plan.own_src.size())) || (rc = nd.pose_slot.alloc(plan.pose_slot.size())) ||
+      (rc = nd.gnc_edge.alloc(h->n_gnc)) || (rc = nd.gnc_ends.alloc(h->n_gnc)) ||
+      (rc = nd.sh_edge.alloc(h->n_sh_local)) || (rc = nd.sh_idx.alloc(h->n_sh_local)) || (rc = nd.active.alloc(L)) ||
+      (rc = nd.osh_edge.alloc(h->n_osh)) || (rc = nd.osh_idx.alloc(h->n_osh)) || (rc = nd.relc.alloc(L)) ||
+      (rc = nd.gnc.alloc(2)) || (rc = nd.ext.alloc(64)) || (rc = nd.hv_launch.alloc(HV_SLOTS)) ||
+      (rc = nd.coefh.alloc((size_t)L * std::max(h->P.tcg_max_iterations, 1))) ||
+      (onesync(h) && (rc = nd.part_f.alloc((size_t)h->ntiles * 16))))
+    return rc;
+  KMX_HIP(upload(h, nd.tile.get(), plan.tile));
+  KMX_HIP(upload(h, nd.rtile0.get(), plan.rt0));
+  KMX_HIP(upload(h, nd.inc_ptr.get(), plan.inc_ptr));
+  KMX_HIP(upload(h, nd.rec.get(), plan.rec));
+  KMX_HIP(upload(h, nd.rec_o.get(), plan.rec_o));
+  KMX_HIP(upload(h, nd.ekappa.get(), plan.ek));
+  KMX_HIP(upload(h, nd.etau.get(), plan.et));
+  KMX_HIP(upload(h, nd.ew.get(), plan.ew));
+  KMX_HIP(upload(h, nd.eipos.get(), plan.eipos));
+  KMX_HIP(hipMemsetAsync(nd.vec.get(), 0, sizeof(double) * vec * nvec(h), h->stream));
+  KMX_HIP(hipMemsetAsync(nd.coefh.get(), 0, sizeof(double) * L * std::max(h->P.tcg_max_iterations, 1), h->stream));
+  KMX_HIP(hipMemsetAsync(nd.pub.get(), 0, sizeof(double) * std::max<int64_t>(h->npub, 1) * ps, h->stream));
+  KMX_HIP(hipMemsetAsync(nd.ctl.get(), 0, sizeof(Ctl) * L, h->stream));
+  KMX_HIP(hipMemsetAsync(nd.cnt.get(), 0, sizeof(Counters), h->stream));
+  KMX_HIP(hipMemsetAsync(nd.ext.get(), 0, sizeof(double) * 64, h->stream));
+  KMX_HIP(hipMemsetAsync(nd.hv_launch.get(), 0, sizeof(int) * HV_SLOTS, h->stream));
+  if ((size_t)L > h->hstat.cap()) {  // host-mapped per-robot tCG progress
+    h->hstat = {};
+    if ((rc = h->hstat.alloc(L))) return rc;
+  }
+  for (int l = 0; l < L; ++l) h->hstat.get()[l].word = 0;
+  h->seq = 0;
+  KMX_HIP(upload(h, nd.relc.get(), relc));
+  KMX_HIP(upload(h, nd.gnc.get(), g0));
+  KMX_HIP(upload(h, nd.m_robot.get(), h->m_robot));
+  KMX_HIP(upload(h, nd.n_robot.get(), plan.nrob));
+  KMX_HIP(upload(h, nd.pub_src.get(), plan.pub_src));
+  KMX_HIP(upload(h, nd.own_src.get(), plan.own_src));
+  KMX_HIP(upload(h, nd.pose_slot.get(), plan.pose_slot));
+  KMX_HIP(upload(h, nd.gnc_edge.get(), plan.gnc_edge));
+  KMX_HIP(upload(h, nd.gnc_ends.get(), plan.gnc_ends));
+  KMX_HIP(upload(h, nd.sh_edge.get(), plan.sh_edge));
+  KMX_HIP(upload(h, nd.sh_idx.get(), plan.sh_idx));
+  KMX_HIP(upload(h, nd.osh_edge.get(), plan.osh_edge));
+  KMX_HIP(upload(h, nd.osh_idx.get(), plan.osh_idx));
+  KMX_HIP(upload(h, nd.active.get(), ones));
   // host vectors must outlive the async copies
   KMX_HIP(hipStreamSynchronize(h->stream));
+  h->gd = std::move(nd);  // the uploads are done: commit
+  const PgoDev& gd = h->gd;
   Dev& d = h->dv;
   d = Dev{};
   d.ntiles = h->ntiles; d.L = L; d.nloc = nloc; d.npub = (int)h->npub;
   d.gt0 = 0; d.gnt = h->ntiles;
-  d.tile = h->d_tile; d.rtile0 = h->d_rtile0;
-  d.inc_ptr = h->d_inc_ptr; d.rec = h->d_rec; d.rec_o = h->d_rec_o;
-  d.ekappa = h->d_ekappa; d.etau = h->d_etau; d.ew = h->d_ew; d.eipos = h->d_eipos;
-  d.X = h->d_vec; d.Xt = h->d_vec + vec; d.g = h->d_vec + 2 * vec; d.r = h->d_vec + 3 * vec;
-  d.z = h->d_vec + 4 * vec; d.hd = h->d_vec + 5 * vec; d.eta = h->d_vec + 6 * vec; d.dh = h->d_vec + 7 * vec;
-  d.coefh = h->d_coefh; d.vec = (long long)vec; d.dhn = dh_count(h);
-  d.S = h->d_S; d.Pinv = h->d_Pinv; d.hD = h->d_hD; d.hDS = h->d_hDS; d.pub = h->d_pub; d.part = h->d_part;
-  d.ctl = h->d_ctl; d.cnt = h->d_cnt;
-  d.ctl2 = h->d_ctl2; d.part_h = h->d_part_h; d.part_u = h->d_part_u;
-  d.m_robot = h->d_m_robot; d.n_robot = h->d_n_robot; d.pose_slot = h->d_pose_slot;
-  d.relc = h->d_relc; d.gnc = h->d_gnc; d.gnc_next = h->d_gnc + 1;
-  d.gnc_edge = h->d_gnc_edge; d.gnc_ends = h->d_gnc_ends; d.n_gnc = h->n_gnc;
-  d.hv_launch = h->d_hv_launch;
+  d.tile = gd.tile.get(); d.rtile0 = gd.rtile0.get();
+  d.inc_ptr = gd.inc_ptr.get(); d.rec = gd.rec.get(); d.rec_o = gd.rec_o.get();
+  d.ekappa = gd.ekappa.get(); d.etau = gd.etau.get(); d.ew = gd.ew.get(); d.eipos = gd.eipos.get();
+  double* const v = gd.vec.get();
+  d.X = v; d.Xt = v + vec; d.g = v + 2 * vec; d.r = v + 3 * vec;
+  d.z = v + 4 * vec; d.hd = v + 5 * vec; d.eta = v + 6 * vec; d.dh = v + 7 * vec;
+  d.coefh = gd.coefh.get(); d.vec = (long long)vec; d.dhn = dh_count(h);
+  d.S = gd.S.get(); d.Pinv = gd.Pinv.get(); d.hD = gd.hD.get(); d.hDS = gd.hDS.get();
+  d.pub = gd.pub.get(); d.part = gd.part.get();
+  d.ctl = gd.ctl.get(); d.cnt = gd.cnt.get();
+  d.ctl2 = gd.ctl2.get(); d.part_h = gd.part_h.get(); d.part_u = gd.part_u.get();
+  d.m_robot = gd.m_robot.get(); d.n_robot = gd.n_robot.get(); d.pose_slot = gd.pose_slot.get();
+  d.relc = gd.relc.get(); d.gnc = gd.gnc.get(); d.gnc_next = gd.gnc.get() + 1;
+  d.gnc_edge = gd.gnc_edge.get(); d.gnc_ends = gd.gnc_ends.get(); d.n_gnc = h->n_gnc;
+  d.hv_launch = gd.hv_launch.get();
   if (onesync(h)) {
     const size_t v0 = 7 + (size_t)dh_count(h);
-    d.hz = h->d_vec + v0 * vec; d.w0 = h->d_vec + (v0 + 1) * vec; d.w1 = h->d_vec + (v0 + 2) * vec;
-    d.part_f = h->d_part_f;
+    d.hz = v + v0 * vec; d.w0 = v + (v0 + 1) * vec; d.w1 = v + (v0 + 2) * vec;
+    d.part_f = gd.part_f.get();
   }
   h->n_ext = 0;
   sync_params(h);
@@ -4151,7 +4103,7 @@ extern "C" int kmx_pgo_set_iterate(kmx_pgo* h, int robot, const double* X) {
   KMX_CHECK(X, KMX_EINVAL, "null X");
   KMX_HIP(hipSetDevice(h->device));
   const int ps = 4 * h->P.r, l = h->local_of[robot];
-  KMX_HIP(hipMemcpyAsync(h->d_vec + (size_t)h->loff[l] * ps, X, sizeof(double) * h->npose[robot] * ps,
+  KMX_HIP(hipMemcpyAsync(h->gd.vec.get() + (size_t)h->loff[l] * ps, X, sizeof(double) * h->npose[robot] * ps,
                          hipMemcpyHostToDevice, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   accel_reset(h);  // a new initial iterate restarts the acceleration (V = X at the next round)
@@ -4163,7 +4115,7 @@ extern "C" int kmx_pgo_get_iterate(kmx_pgo* h, int robot, double* X) {
   KMX_CHECK(X, KMX_EINVAL, "null X");
   KMX_HIP(hipSetDevice(h->device));
   const int ps = 4 * h->P.r, l = h->local_of[robot];
-  KMX_HIP(hipMemcpyAsync(X, h->d_vec + (size_t)h->loff[l] * ps, sizeof(double) * h->npose[robot] * ps,
+  KMX_HIP(hipMemcpyAsync(X, h->gd.vec.get() + (size_t)h->loff[l] * ps, sizeof(double) * h->npose[robot] * ps,
                          hipMemcpyDeviceToHost, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   return KMX_OK;
@@ -4184,8 +4136,8 @@ extern "C" int kmx_pgo_pack_public(kmx_pgo* h, void* dev_out) {
   const int ps = 4 * h->P.r;
   const long long tot = h->n_owned * ps;
   if (tot)
-    hipLaunchKernelGGL(k_pack, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->d_vec,
-                       (double*)dev_out, h->d_own_src, 0, (int)h->n_owned, ps);
+    hipLaunchKernelGGL(k_pack, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->gd.vec.get(),
+                       (double*)dev_out, h->gd.own_src.get(), 0, (int)h->n_owned, ps);
   KMX_HIP(hipGetLastError());
   return KMX_OK;
 }
@@ -4195,7 +4147,7 @@ extern "C" int kmx_pgo_unpack_public(kmx_pgo* h, const void* dev_table) {
   KMX_CHECK(dev_table || h->npub == 0, KMX_EINVAL, "null device buffer");
   KMX_HIP(hipSetDevice(h->device));
   if (h->npub)
-    KMX_HIP(hipMemcpyAsync(h->d_pub, dev_table, sizeof(double) * h->npub * 4 * h->P.r, hipMemcpyDeviceToDevice,
+    KMX_HIP(hipMemcpyAsync(h->gd.pub.get(), dev_table, sizeof(double) * h->npub * 4 * h->P.r, hipMemcpyDeviceToDevice,
                            h->stream));
   return KMX_OK;
 }
@@ -4219,9 +4171,9 @@ extern "C" int kmx_pgo_exchange_pack(kmx_pgo* h, const int32_t* dev_slots, int64
   const int ps = 4 * h->P.r;
   const long long tot = (long long)n * ps + n_seg;  // rows, then the status words
   if (tot)
-    hipLaunchKernelGGL(k_gather_slots, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->d_vec,
-                       h->d_pub_src, (const int*)dev_slots, (long long)n, (int)h->npub, (double*)dev_out, ps,
-                       (const int*)dev_seg, n_seg, (const double*)h->d_relc, h->dv.L);
+    hipLaunchKernelGGL(k_gather_slots, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->gd.vec.get(),
+                       h->gd.pub_src.get(), (const int*)dev_slots, (long long)n, (int)h->npub, (double*)dev_out, ps,
+                       (const int*)dev_seg, n_seg, (const double*)h->gd.relc.get(), h->dv.L);
   KMX_HIP(hipGetLastError());
   return KMX_OK;
 }
@@ -4234,19 +4186,12 @@ extern "C" int kmx_pgo_exchange_unpack(kmx_pgo* h, const int32_t* dev_slots, int
             KMX_EINVAL, "bad argument");
   KMX_HIP(hipSetDevice(h->device));
   const int ps = 4 * h->P.r;
-  if (n_seg > h->ext_cap) {
-    KMX_HIP(hipStreamSynchronize(h->stream));
-    if (h->d_ext) (void)hipFree(h->d_ext);
-    h->d_ext = nullptr;
-    h->ext_cap = 0;
-    if (int rc = dalloc(&h->d_ext, n_seg)) return rc;
-    h->ext_cap = n_seg;
-  }
+  if (int rc = ensure_ext(h, n_seg)) return rc;
   const long long tot = (long long)n * ps + n_seg;  // rows, then the status words
   if (tot)
-    hipLaunchKernelGGL(k_scatter_slots, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->d_pub,
+    hipLaunchKernelGGL(k_scatter_slots, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->gd.pub.get(),
                        (const int*)dev_slots, (long long)n, (int)h->npub, (const double*)dev_in, ps,
-                       (const int*)dev_seg, n_seg, h->d_ext);
+                       (const int*)dev_seg, n_seg, h->gd.ext.get());
   h->n_ext = n_seg;
   sync_params(h);
   KMX_HIP(hipGetLastError());
@@ -4283,23 +4228,25 @@ int enqueue_exchange(kmx_pgo* h) {
   if (!h->xchg) return KMX_OK;
   const int ps = 4 * h->P.r, W = h->world;
   const long long ts = h->xn_send * ps + W, tr = h->xn_recv * ps + W;
-  hipLaunchKernelGGL(k_xgather, dim3((unsigned)((ts + 255) / 256)), dim3(256), 0, h->stream, h->d_vec,
-                     h->d_pub_src, h->d_xs_slots, h->d_xs_rseg, h->xn_send, h->d_xsbuf, ps, h->d_xs_seg, W,
-                     (const double*)h->d_relc, h->dv.L);
+  hipLaunchKernelGGL(k_xgather, dim3((unsigned)((ts + 255) / 256)), dim3(256), 0, h->stream, h->gd.vec.get(),
+                     h->gd.pub_src.get(), h->xd.xs_slots.get(), h->xd.xs_rseg.get(), h->xn_send, h->xd.xsbuf.get(),
+                     ps, h->xd.xs_seg.get(), W,
+                     (const double*)h->gd.relc.get(), h->dv.L);
   KMX_NCCL(ncclGroupStart());
   for (int q = 0; q < W; ++q) {
     if (q == h->rank && !h->xchg_self_p2p) continue;
-    KMX_NCCL(ncclSend(h->d_xsbuf + h->xs_off[q], (size_t)h->xs_cnt[q], ncclDouble, q, h->comm, h->stream));
-    KMX_NCCL(ncclRecv(h->d_xrbuf + h->xr_off[q], (size_t)h->xr_cnt[q], ncclDouble, q, h->comm, h->stream));
+    KMX_NCCL(ncclSend(h->xd.xsbuf.get() + h->xs_off[q], (size_t)h->xs_cnt[q], ncclDouble, q, h->comm, h->stream));
+    KMX_NCCL(ncclRecv(h->xd.xrbuf.get() + h->xr_off[q], (size_t)h->xr_cnt[q], ncclDouble, q, h->comm, h->stream));
   }
   // the communicator is non-blocking (kmx_pgo_comm_init): the group may still
   // be enqueueing when ncclGroupEnd returns
   if (int rc = nccl_settle(h, ncclGroupEnd(), "ncclGroupEnd")) return rc;
   if (!h->xchg_self_p2p)  // this handle's own segment (its status word)
-    KMX_HIP(hipMemcpyAsync(h->d_xrbuf + h->xr_off[h->rank], h->d_xsbuf + h->xs_off[h->rank],
+    KMX_HIP(hipMemcpyAsync(h->xd.xrbuf.get() + h->xr_off[h->rank], h->xd.xsbuf.get() + h->xs_off[h->rank],
                            sizeof(double) * h->xs_cnt[h->rank], hipMemcpyDeviceToDevice, h->stream));
-  hipLaunchKernelGGL(k_xscatter, dim3((unsigned)((tr + 255) / 256)), dim3(256), 0, h->stream, h->d_pub,
-                     h->d_xr_slots, h->d_xr_rseg, h->xn_recv, (const double*)h->d_xrbuf, ps, h->d_xr_seg, W, h->d_ext);
+  hipLaunchKernelGGL(k_xscatter, dim3((unsigned)((tr + 255) / 256)), dim3(256), 0, h->stream, h->gd.pub.get(),
+                     h->xd.xr_slots.get(), h->xd.xr_rseg.get(), h->xn_recv, (const double*)h->xd.xrbuf.get(), ps,
+                     h->xd.xr_seg.get(), W, h->gd.ext.get());
   if (h->n_ext != W) {
     h->n_ext = W;
     sync_params(h);
@@ -4388,7 +4335,7 @@ extern "C" int kmx_pgo_comm_destroy(kmx_pgo* h) {
   if (h->comm) (void)ncclCommAbort(h->comm);
   h->comm = nullptr;
   KMX_HIP(hipStreamSynchronize(h->stream));
-  free_xchg(h);
+  drop_xchg(h);
   h->world = 1;
   h->rank = 0;
   if (h->n_ext) {  // the peers' statuses came with the exchange
@@ -4422,9 +4369,10 @@ extern "C" int kmx_pgo_get_public(kmx_pgo* h, double* table, double* ext) {
   KMX_CHECK(table || h->npub == 0, KMX_EINVAL, "null table");
   KMX_HIP(hipSetDevice(h->device));
   if (h->npub)
-    KMX_HIP(hipMemcpyAsync(table, h->d_pub, sizeof(double) * h->npub * 4 * h->P.r, hipMemcpyDeviceToHost, h->stream));
+    KMX_HIP(hipMemcpyAsync(table, h->gd.pub.get(), sizeof(double) * h->npub * 4 * h->P.r, hipMemcpyDeviceToHost,
+                           h->stream));
   if (ext && h->n_ext)
-    KMX_HIP(hipMemcpyAsync(ext, h->d_ext, sizeof(double) * h->n_ext, hipMemcpyDeviceToHost, h->stream));
+    KMX_HIP(hipMemcpyAsync(ext, h->gd.ext.get(), sizeof(double) * h->n_ext, hipMemcpyDeviceToHost, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   return KMX_OK;
   KMX_GUARD_END
@@ -4449,7 +4397,7 @@ extern "C" int kmx_pgo_set_exchange(kmx_pgo* h, const int32_t* send_slots, const
   for (long long i = 0; i < nr; ++i) KMX_CHECK(recv_slots[i] >= 0 && recv_slots[i] < h->npub, KMX_EINVAL, "recv slot out of range");
   KMX_HIP(hipSetDevice(h->device));
   KMX_HIP(hipStreamSynchronize(h->stream));
-  free_xchg(h);
+  drop_xchg(h);  // a failure from here on leaves the handle without an exchange
   std::vector<int> sseg(W + 1, 0), rseg(W + 1, 0);
   h->xs_cnt.assign(W, 0); h->xr_cnt.assign(W, 0); h->xs_off.assign(W, 0); h->xr_off.assign(W, 0);
   for (int q = 0; q < W; ++q) {
@@ -4460,34 +4408,27 @@ extern "C" int kmx_pgo_set_exchange(kmx_pgo* h, const int32_t* send_slots, const
     h->xs_off[q] = (long long)sseg[q] * ps + q;
     h->xr_off[q] = (long long)rseg[q] * ps + q;
   }
+  PgoXchg nx;  // built aside, committed once its copies are done
   int rc = 0;
-  if ((rc = dalloc(&h->d_xs_slots, ns)) || (rc = dalloc(&h->d_xr_slots, nr)) || (rc = dalloc(&h->d_xs_seg, W + 1)) ||
-      (rc = dalloc(&h->d_xs_rseg, ns)) || (rc = dalloc(&h->d_xr_rseg, nr)) ||
-      (rc = dalloc(&h->d_xr_seg, W + 1)) || (rc = dalloc(&h->d_xsbuf, ns * ps + W)) ||
-      (rc = dalloc(&h->d_xrbuf, nr * ps + W))) {
-    free_xchg(h);
+  if ((rc = nx.xs_slots.alloc(ns)) || (rc = nx.xr_slots.alloc(nr)) || (rc = nx.xs_seg.alloc(W + 1)) ||
+      (rc = nx.xs_rseg.alloc(ns)) || (rc = nx.xr_rseg.alloc(nr)) || (rc = nx.xr_seg.alloc(W + 1)) ||
+      (rc = nx.xsbuf.alloc(ns * ps + W)) || (rc = nx.xrbuf.alloc(nr * ps + W)))
     return rc;
-  }
-  if (W > h->ext_cap) {
-    if (h->d_ext) (void)hipFree(h->d_ext);
-    h->d_ext = nullptr;
-    h->ext_cap = 0;
-    if ((rc = dalloc(&h->d_ext, W))) return rc;
-    h->ext_cap = W;
-  }
-  if (ns) KMX_HIP(hipMemcpy(h->d_xs_slots, send_slots, sizeof(int) * ns, hipMemcpyHostToDevice));
-  if (nr) KMX_HIP(hipMemcpy(h->d_xr_slots, recv_slots, sizeof(int) * nr, hipMemcpyHostToDevice));
+  if ((rc = ensure_ext(h, W))) return rc;
+  if (ns) KMX_HIP(hipMemcpy(nx.xs_slots.get(), send_slots, sizeof(int) * ns, hipMemcpyHostToDevice));
+  if (nr) KMX_HIP(hipMemcpy(nx.xr_slots.get(), recv_slots, sizeof(int) * nr, hipMemcpyHostToDevice));
   {
     std::vector<int> srs(std::max<long long>(ns, 1)), rrs(std::max<long long>(nr, 1));
     for (int q = 0; q < W; ++q) {
       for (int k = sseg[q]; k < sseg[q + 1]; ++k) srs[k] = q;
       for (int k = rseg[q]; k < rseg[q + 1]; ++k) rrs[k] = q;
     }
-    if (ns) KMX_HIP(hipMemcpy(h->d_xs_rseg, srs.data(), sizeof(int) * ns, hipMemcpyHostToDevice));
-    if (nr) KMX_HIP(hipMemcpy(h->d_xr_rseg, rrs.data(), sizeof(int) * nr, hipMemcpyHostToDevice));
+    if (ns) KMX_HIP(hipMemcpy(nx.xs_rseg.get(), srs.data(), sizeof(int) * ns, hipMemcpyHostToDevice));
+    if (nr) KMX_HIP(hipMemcpy(nx.xr_rseg.get(), rrs.data(), sizeof(int) * nr, hipMemcpyHostToDevice));
   }
-  KMX_HIP(hipMemcpy(h->d_xs_seg, sseg.data(), sizeof(int) * (W + 1), hipMemcpyHostToDevice));
-  KMX_HIP(hipMemcpy(h->d_xr_seg, rseg.data(), sizeof(int) * (W + 1), hipMemcpyHostToDevice));
+  KMX_HIP(hipMemcpy(nx.xs_seg.get(), sseg.data(), sizeof(int) * (W + 1), hipMemcpyHostToDevice));
+  KMX_HIP(hipMemcpy(nx.xr_seg.get(), rseg.data(), sizeof(int) * (W + 1), hipMemcpyHostToDevice));
+  h->xd = std::move(nx);
   h->xn_send = ns;
   h->xn_recv = nr;
   h->xchg = true;
@@ -4522,7 +4463,7 @@ extern "C" int kmx_pgo_set_neighbor_poses(kmx_pgo* h, int64_t count, const int32
   KMX_HIP(hipSetDevice(h->device));
   const int ps = 4 * h->P.r;
   std::vector<double> tab((size_t)std::max<int64_t>(h->npub, 1) * ps);
-  KMX_HIP(hipMemcpyAsync(tab.data(), h->d_pub, sizeof(double) * h->npub * ps, hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(tab.data(), h->gd.pub.get(), sizeof(double) * h->npub * ps, hipMemcpyDeviceToHost, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   for (int64_t i = 0; i < count; ++i) {
     const int64_t k = ((int64_t)robot[i] << 32) | (uint32_t)pose[i];
@@ -4530,7 +4471,7 @@ extern "C" int kmx_pgo_set_neighbor_poses(kmx_pgo* h, int64_t count, const int32
     KMX_CHECK(it != h->pub_key.end() && *it == k, KMX_EINVAL, "pose is not public (no shared edge)");
     std::memcpy(&tab[(size_t)(it - h->pub_key.begin()) * ps], X + (size_t)i * ps, sizeof(double) * ps);
   }
-  KMX_HIP(hipMemcpyAsync(h->d_pub, tab.data(), sizeof(double) * h->npub * ps, hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->gd.pub.get(), tab.data(), sizeof(double) * h->npub * ps, hipMemcpyHostToDevice, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   return KMX_OK;
   KMX_GUARD_END
@@ -4547,18 +4488,18 @@ extern "C" int kmx_pgo_iterate(kmx_pgo* h, const uint8_t* active, kmx_iter_stats
   if (h->P.acceleration)
     for (int l = 0; l < L; ++l)
       KMX_CHECK(act[l], KMX_EUNSUP, "acceleration needs every local robot active (concurrent schedule)");
-  KMX_HIP(hipMemcpyAsync(h->d_active, act.data(), L, hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->gd.active.get(), act.data(), L, hipMemcpyHostToDevice, h->stream));
   enqueue_accel_pre(h);
   if (int rc = enqueue_exchange(h)) return rc;
-  enqueue_round(h, h->d_active);
+  enqueue_round(h, h->gd.active.get());
   enqueue_accel_post(h);
   KMX_HIP(hipGetLastError());
   std::vector<Ctl> ctl(L);
-  KMX_HIP(hipMemcpyAsync(ctl.data(), h->d_ctl, sizeof(Ctl) * L, hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(ctl.data(), h->gd.ctl.get(), sizeof(Ctl) * L, hipMemcpyDeviceToHost, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   // restore the all-active mask used by iterate_async
   std::vector<unsigned char> ones(L, 1);
-  KMX_HIP(hipMemcpyAsync(h->d_active, ones.data(), L, hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->gd.active.get(), ones.data(), L, hipMemcpyHostToDevice, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   if (stats) {
     for (int a = 0; a < h->n_robots; ++a) std::memset(&stats[a], 0, sizeof(kmx_iter_stats));
@@ -4593,7 +4534,7 @@ extern "C" int kmx_pgo_iterate_async(kmx_pgo* h, int rounds, int refresh_local) 
   for (int i = 0; i < rounds; ++i) {
     enqueue_accel_pre(h);  // publishes Y itself
     if (int rc = enqueue_exchange(h)) return rc;
-    enqueue_round(h, h->d_active);
+    enqueue_round(h, h->gd.active.get());
     enqueue_accel_post(h);
   }
   KMX_HIP(hipGetLastError());
@@ -4623,7 +4564,7 @@ extern "C" int kmx_pgo_get_gnc_state(kmx_pgo* h, kmx_gnc_state* out) {
   KMX_CHECK(ready(h) && out, KMX_EINVAL, "null argument / no graph");
   KMX_HIP(hipSetDevice(h->device));
   Gnc g;
-  KMX_HIP(hipMemcpyAsync(&g, h->d_gnc, sizeof(Gnc), hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(&g, h->gd.gnc.get(), sizeof(Gnc), hipMemcpyDeviceToHost, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   std::memset(out, 0, sizeof(*out));
   out->inner_iter = g.inner;
@@ -4644,7 +4585,7 @@ extern "C" int kmx_pgo_set_gnc_state(kmx_pgo* h, const kmx_gnc_state* in) {
   g[0].rounds = in->rounds;
   g[0].mu = in->mu;
   g[1] = g[0];
-  KMX_HIP(hipMemcpyAsync(h->d_gnc, g, sizeof(g), hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->gd.gnc.get(), g, sizeof(g), hipMemcpyHostToDevice, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   return KMX_OK;
 }
@@ -4654,7 +4595,7 @@ extern "C" int kmx_pgo_get_status(kmx_pgo* h, double* rel_change) {
   KMX_CHECK(ready(h) && rel_change, KMX_EINVAL, "null argument / no graph");
   KMX_HIP(hipSetDevice(h->device));
   std::vector<double> v(h->robots.size());
-  KMX_HIP(hipMemcpyAsync(v.data(), h->d_relc, sizeof(double) * v.size(), hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(v.data(), h->gd.relc.get(), sizeof(double) * v.size(), hipMemcpyDeviceToHost, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   for (size_t l = 0; l < v.size(); ++l) rel_change[h->robots[l]] = v[l];
   return KMX_OK;
@@ -4667,7 +4608,7 @@ extern "C" int kmx_pgo_set_status(kmx_pgo* h, const double* rel_change) {
   KMX_HIP(hipSetDevice(h->device));
   std::vector<double> v(h->robots.size());
   for (size_t l = 0; l < v.size(); ++l) v[l] = rel_change[h->robots[l]];
-  KMX_HIP(hipMemcpyAsync(h->d_relc, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->gd.relc.get(), v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   return KMX_OK;
   KMX_GUARD_END
@@ -4677,11 +4618,11 @@ extern "C" int kmx_pgo_update_weights(kmx_pgo* h, double* mu_out) {
   KMX_CHECK(ready(h), KMX_ESTATE, "set_graph first");
   KMX_HIP(hipSetDevice(h->device));
   Gnc g;
-  KMX_HIP(hipMemcpyAsync(&g, h->d_gnc, sizeof(Gnc), hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(&g, h->gd.gnc.get(), sizeof(Gnc), hipMemcpyDeviceToHost, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   if (mu_out) *mu_out = g.mu;
   if (h->P.robust_cost != KMX_COST_GNC_TLS) return KMX_OK;
-  enqueue_begin(h, h->d_active, BEGIN_FORCE_GNC);
+  enqueue_begin(h, h->gd.active.get(), BEGIN_FORCE_GNC);
   KMX_HIP(hipGetLastError());
   KMX_HIP(hipStreamSynchronize(h->stream));
   return KMX_OK;
@@ -4707,7 +4648,7 @@ extern "C" int kmx_pgo_get_weights(kmx_pgo* h, double* w) {
   KMX_CHECK(ready(h) && w, KMX_EINVAL, "null argument / no graph");
   KMX_HIP(hipSetDevice(h->device));
   std::vector<double> ew(std::max(h->mloc, 1));
-  KMX_HIP(hipMemcpyAsync(ew.data(), h->d_ew, sizeof(double) * h->mloc, hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(ew.data(), h->gd.ew.get(), sizeof(double) * h->mloc, hipMemcpyDeviceToHost, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   for (int k = 0; k < h->mloc; ++k) w[h->loc_edge_gid[k]] = ew[k];
   return KMX_OK;
@@ -4720,7 +4661,7 @@ extern "C" int kmx_pgo_set_weights(kmx_pgo* h, const double* w) {
   KMX_HIP(hipSetDevice(h->device));
   std::vector<double> ew(std::max(h->mloc, 1));
   for (int k = 0; k < h->mloc; ++k) ew[k] = w[h->loc_edge_gid[k]];
-  KMX_HIP(hipMemcpyAsync(h->d_ew, ew.data(), sizeof(double) * h->mloc, hipMemcpyHostToDevice, h->stream));
+  KMX_HIP(hipMemcpyAsync(h->gd.ew.get(), ew.data(), sizeof(double) * h->mloc, hipMemcpyHostToDevice, h->stream));
   enqueue_apply_weights(h);
   KMX_HIP(hipGetLastError());
   KMX_HIP(hipStreamSynchronize(h->stream));
@@ -4742,7 +4683,8 @@ extern "C" int kmx_pgo_pack_shared_weights(kmx_pgo* h, void* dev_out) {
   KMX_HIP(hipMemsetAsync(dev_out, 0, sizeof(double) * h->nshared, h->stream));
   if (h->n_osh)
     hipLaunchKernelGGL(k_shared_pack, dim3((h->n_osh + 255) / 256), dim3(256), 0, h->stream,
-                       (const double*)h->d_ew, h->d_osh_edge, h->d_osh_idx, h->n_osh, (double*)dev_out);
+                       (const double*)h->gd.ew.get(), h->gd.osh_edge.get(), h->gd.osh_idx.get(), h->n_osh,
+                       (double*)dev_out);
   KMX_HIP(hipGetLastError());
   return KMX_OK;
 }
@@ -4752,8 +4694,8 @@ extern "C" int kmx_pgo_unpack_shared_weights(kmx_pgo* h, const void* dev_table) 
   KMX_CHECK(dev_table || h->nshared == 0, KMX_EINVAL, "null device buffer");
   KMX_HIP(hipSetDevice(h->device));
   if (h->n_sh_local)
-    hipLaunchKernelGGL(k_shared_unpack, dim3((h->n_sh_local + 255) / 256), dim3(256), 0, h->stream, h->d_ew,
-                       h->d_sh_edge, h->d_sh_idx, h->n_sh_local, (const double*)dev_table);
+    hipLaunchKernelGGL(k_shared_unpack, dim3((h->n_sh_local + 255) / 256), dim3(256), 0, h->stream, h->gd.ew.get(),
+                       h->gd.sh_edge.get(), h->gd.sh_idx.get(), h->n_sh_local, (const double*)dev_table);
   enqueue_apply_weights(h);
   KMX_HIP(hipGetLastError());
   return KMX_OK;
@@ -4766,12 +4708,13 @@ extern "C" int kmx_pgo_get_trajectory(kmx_pgo* h, int robot, const double* ancho
   KMX_HIP(hipSetDevice(h->device));
   const int ps = 4 * h->P.r, l = h->local_of[robot], n = h->npose[robot];
   if (int rc = ensure_scratch(h, (size_t)ps + (size_t)std::max(n, 1) * 12)) return rc;
-  double* d_anchor = h->d_scratch;
-  double* d_out = h->d_scratch + ps;
+  double* d_anchor = h->gd.scratch.get();
+  double* d_out = h->gd.scratch.get() + ps;
   KMX_HIP(hipMemcpyAsync(d_anchor, anchor, sizeof(double) * ps, hipMemcpyHostToDevice, h->stream));
   if (n)
     hipLaunchKernelGGL(k_traj, dim3((n + 127) / 128), dim3(128), 0, h->stream,
-                       (const double*)(h->d_vec + (size_t)h->loff[l] * ps), n, h->P.r, (const double*)d_anchor, d_out);
+                       (const double*)(h->gd.vec.get() + (size_t)h->loff[l] * ps), n, h->P.r,
+                       (const double*)d_anchor, d_out);
   KMX_HIP(hipGetLastError());
   KMX_HIP(hipMemcpyAsync(out, d_out, sizeof(double) * n * 12, hipMemcpyDeviceToHost, h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
@@ -4788,10 +4731,10 @@ extern "C" int kmx_pgo_eval(kmx_pgo* h, int robot, int mode, const double* V, do
   const int ps = 4 * h->P.r, l = h->local_of[robot], n = h->npose[robot];
   const size_t vec = (size_t)std::max(h->nloc, 1) * ps;
   if (int rc = ensure_scratch(h, vec * 2)) return rc;
-  double* dV = h->d_scratch;
-  double* dO = h->d_scratch + vec;
+  double* dV = h->gd.scratch.get();
+  double* dO = h->gd.scratch.get() + vec;
   const size_t o = (size_t)h->loff[l] * ps;
-  KMX_HIP(hipMemsetAsync(h->d_scratch, 0, sizeof(double) * vec * 2, h->stream));
+  KMX_HIP(hipMemsetAsync(h->gd.scratch.get(), 0, sizeof(double) * vec * 2, h->stream));
   if (V) KMX_HIP(hipMemcpyAsync(dV + o, V, sizeof(double) * n * ps, hipMemcpyHostToDevice, h->stream));
   with_r(h->P.r, [&](auto R) {
     with_rw(h->rw, [&](auto RW) {
@@ -4803,7 +4746,8 @@ extern "C" int kmx_pgo_eval(kmx_pgo* h, int robot, int mode, const double* V, do
   KMX_HIP(hipGetLastError());
   KMX_HIP(hipMemcpyAsync(out, dO + o, sizeof(double) * n * ps, hipMemcpyDeviceToHost, h->stream));
   std::vector<double> part((size_t)h->ntiles * NPART);
-  KMX_HIP(hipMemcpyAsync(part.data(), h->d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, h->stream));
+  KMX_HIP(hipMemcpyAsync(part.data(), h->gd.part.get(), sizeof(double) * part.size(), hipMemcpyDeviceToHost,
+                         h->stream));
   KMX_HIP(hipStreamSynchronize(h->stream));
   // tiles of robot l are contiguous
   const int t0 = h->rt0_h[l], nt = h->rt0_h[l + 1] - h->rt0_h[l];
@@ -4832,7 +4776,7 @@ extern "C" int kmx_pgo_memory(kmx_pgo* h, int64_t* device_bytes, int* record_byt
   b += L * 8 * (int64_t)std::max(h->P.tcg_max_iterations, 1);            // tCG coefficients
   b += std::max<int64_t>(h->npub, 1) * (ps * 8 + 4) + n * 4;             // public table + maps
   b += (int64_t)h->ntiles * (NPART * 8 + 12 + (onesync(h) ? 64 : 0)) + L * (int64_t)(sizeof(Ctl) + 32);
-  b += (int64_t)std::max(h->n_gnc, 1) * 12 + (int64_t)h->scratch_cap * 8;  // GNC lists, scratch in use
+  b += (int64_t)std::max(h->n_gnc, 1) * 12 + (int64_t)h->gd.scratch.cap() * 8;  // GNC lists, scratch in use
   if (h->P.acceleration) b += 2 * n * ps * 8;                              // V, Y
   if (device_bytes) *device_bytes = b;
   if (record_bytes) *record_bytes = rb;
@@ -4850,11 +4794,11 @@ extern "C" int kmx_pgo_read_counters(kmx_pgo* h, kmx_pgo_counters* out) {
   KMX_HIP(hipSetDevice(h->device));
   KMX_HIP(hipStreamSynchronize(h->stream));
   Counters c;
-  KMX_HIP(hipMemcpy(&c, h->d_cnt, sizeof(Counters), hipMemcpyDeviceToHost));
+  KMX_HIP(hipMemcpy(&c, h->gd.cnt.get(), sizeof(Counters), hipMemcpyDeviceToHost));
   // event pairs of k_hess launches in which at least one robot ran a Hess-vec
   const size_t nl = std::min(h->ev_used / 2, (size_t)HV_SLOTS);
   std::vector<int> hv(std::max<size_t>(nl, 1), 0);
-  if (nl) KMX_HIP(hipMemcpy(hv.data(), h->d_hv_launch, sizeof(int) * nl, hipMemcpyDeviceToHost));
+  if (nl) KMX_HIP(hipMemcpy(hv.data(), h->gd.hv_launch.get(), sizeof(int) * nl, hipMemcpyDeviceToHost));
   double ms_total = 0.0;
   int64_t launches = 0;
   for (size_t i = 0; i < nl; ++i) {
@@ -4864,7 +4808,7 @@ extern "C" int kmx_pgo_read_counters(kmx_pgo* h, kmx_pgo_counters* out) {
     ms_total += ms;
     ++launches;
   }
-  if (nl) KMX_HIP(hipMemset(h->d_hv_launch, 0, sizeof(int) * nl));
+  if (nl) KMX_HIP(hipMemset(h->gd.hv_launch.get(), 0, sizeof(int) * nl));
   std::memset(out, 0, sizeof(*out));
   out->hessvec_ms_total = ms_total;
   out->hessvec_launches = launches;
@@ -4874,7 +4818,7 @@ extern "C" int kmx_pgo_read_counters(kmx_pgo* h, kmx_pgo_counters* out) {
   out->hessvecs = (int64_t)c.hessvecs;
   out->gnc_updates = (int64_t)c.gnc_updates;
   h->ev_used = 0;
-  KMX_HIP(hipMemset(h->d_cnt, 0, sizeof(Counters)));
+  KMX_HIP(hipMemset(h->gd.cnt.get(), 0, sizeof(Counters)));
   return KMX_OK;
 }
 

@@ -279,3 +279,215 @@ def test_voc_batches_grow_and_shrink_on_one_handle(gpu):
     for k, (nf, desc) in enumerate(batches):
         _same(gv.transform(nf, desc), want[k], f"batch {k}")
     gv.close()
+
+
+# ------------------------------------------------------- with torch tensors
+_TORCH_CHILD = """
+import sys
+sys.path[:0] = [{root!r} + "/kimera-multi_amd", {root!r}]
+import torch
+torch.cuda.set_device(0)
+torch.cuda.init()  # torch takes the device before the first kmx handle, as in kmx.dpgo.driver
+from tests import test_handle_buffers_gpu as T
+T.{body}()
+print("child ok")
+"""
+
+
+def _in_torch_child(body):
+    """Runs this module's `body` in a process of its own: torch has to take the
+    device before the first kmx handle of a process does, and this session's
+    earlier tests already hold it."""
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = str(Path(__file__).resolve().parents[1])
+    r = subprocess.run([sys.executable, "-c", _TORCH_CHILD.format(root=root, body=body)], capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0 and "child ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+
+
+# ----------------------------------------------------------------------- lcd
+def _lcd_fresh(pool, call):
+    from kmx.lcd import LcdParams, LoopClosureDetector
+    det = LoopClosureDetector(LcdParams())
+    det.set_pool(pool)
+    out = call(det)
+    det.close()
+    return out
+
+
+def test_lcd_slot_grows_past_its_floor_while_slots_are_warm(gpu):
+    """A synchronous call of 1500 candidates lands on a slot whose buffers hold
+    the floor of 1024, after async calls have warmed the other slots; the
+    small calls before and after it use what it left."""
+    from kmx.lcd import LcdParams, LoopClosureDetector
+    from kmx.synth.lcd import make_lcd_pool
+    pool = make_lcd_pool(16, 64, seed=41)
+    small = (pool.cand_query, pool.cand_match)
+    big = (np.tile(pool.cand_query, 94)[:1500], np.tile(pool.cand_match, 94)[:1500])
+    want_small = _lcd_fresh(pool, lambda d: d.verify(*small, with_masks=True))
+    want_big = _lcd_fresh(pool, lambda d: d.verify(*big, with_masks=True))
+    assert sum(r["accepted"] for r in want_small[0]) > 0
+    det = LoopClosureDetector(LcdParams())
+    det.set_pool(pool)
+    _same(det.verify(*small, with_masks=True), want_small, "small")
+    for _ in range(3):
+        det.verify_async(*small)
+    _same(det.verify(*big, with_masks=True), want_big, "1500 candidates")
+    _same(det.verify(*small, with_masks=True), want_small, "small again")
+    det.close()
+
+
+def test_lcd_frame_staging_grows(gpu):
+    """add_frames of one frame, then of four, at max_feats = 1024: 81 KB, then
+    327 KB, past the staging area's 256 KiB floor."""
+    from kmx.lcd import LcdParams, LoopClosureDetector
+    from kmx.synth.lcd import make_lcd_pool
+    pool = make_lcd_pool(6, 1024, seed=43)
+    F = 5
+    cq, cm = np.array([0, 2, 4, 1], np.int32), np.array([1, 3, 0, 2], np.int32)
+    fr = lambda a, b: (pool.n_feats[a:b], pool.desc[a:b], pool.bearings[a:b], pool.points[a:b])  # noqa: E731
+
+    ref = LoopClosureDetector(LcdParams())
+    ref.set_frames(*fr(0, F))
+    want = ref.verify(cq, cm, with_masks=True)
+    ref.close()
+    assert sum(r["accepted"] for r in want[0]) > 0
+    det = LoopClosureDetector(LcdParams())
+    assert det.add_frames(*fr(0, 1)) == 0
+    assert det.add_frames(*fr(1, F)) == 1
+    _same(det.verify(cq, cm, with_masks=True), want, "verify")
+    det.close()
+
+
+def test_lcd_borrowed_stream_is_used_and_left_alive(gpu):
+    _in_torch_child("_lcd_borrowed_stream")
+
+
+def _lcd_borrowed_stream():
+    import torch
+    from kmx.lcd import LcdParams, LoopClosureDetector
+    from kmx.synth.lcd import make_lcd_pool
+    pool = make_lcd_pool(16, 64, seed=47)
+    cq, cm = pool.cand_query, pool.cand_match
+
+    def run(det):
+        v = det.verify(cq, cm, with_masks=True)
+        pairs, k = det.match(cq, cm)
+        corr = [(pairs[i, :k[i], 0], pairs[i, :k[i], 1]) for i in range(len(k))]
+        return v, [pairs[i, :k[i]] for i in range(len(k))], k, det.verify_matches(cq, cm, corr, with_masks=True)
+
+    want = _lcd_fresh(pool, run)
+    st = torch.cuda.Stream()
+    det = LoopClosureDetector(LcdParams())
+    det.set_pool(pool)
+    _same(det.verify(cq, cm, with_masks=True), want[0], "own stream")
+    det.set_stream(st.cuda_stream)
+    _same(run(det), want, "borrowed stream")
+    det.close()
+    with torch.cuda.stream(st):  # the stream was not the detector's to destroy
+        x = torch.arange(8, device="cuda") * 2
+    st.synchronize()
+    assert x.sum().item() == 56
+
+
+def test_lcd_timing_events_made_on_first_use(gpu):
+    from kmx.lcd import LcdParams, LoopClosureDetector
+    from kmx.synth.lcd import make_lcd_pool
+    pool = make_lcd_pool(16, 64, seed=53)
+    det = LoopClosureDetector(LcdParams())
+    det.set_pool(pool)
+    det.enable_timing(True)
+    det.verify(pool.cand_query, pool.cand_match)
+    t = det.read_timing()
+    assert np.isfinite(t["knn_ms"]) and t["knn_ms"] >= 0 and np.isfinite(t["ransac_ms"]) and t["ransac_ms"] >= 0
+    det.close()
+    det = LoopClosureDetector(LcdParams())  # closed with its events never made
+    det.set_pool(pool)
+    det.enable_timing(True)
+    det.close()
+
+
+# ----------------------------------------------------------------------- pgo
+def _pgo_params(kind):
+    from kmx.dpgo.params import PGOAgentParameters, ROptParameters
+    if kind == "accelerated":
+        return PGOAgentParameters(r=5, acceleration=True)
+    if kind == "two_rtr":
+        return PGOAgentParameters(r=5, localOptimizationParams=ROptParameters(RTR_iterations=2))
+    return PGOAgentParameters(r=5)
+
+
+def _pgo_load(s, g):
+    from kmx.synth import lift, lifting_matrix
+    s.set_graph_data(g)
+    Y = lifting_matrix(5, seed=1)
+    for a in range(g.n_robots):
+        s.set_iterate(a, lift(g.init_R[a], g.init_t[a], Y))
+
+
+def _pgo_rounds(s, g):
+    for _ in range(2):
+        s.refresh_local()
+        s.iterate()
+    return [s.get_iterate(a) for a in range(g.n_robots)], s.get_public()[0], s.get_weights(), s.memory()
+
+
+@pytest.mark.parametrize("kind", ["plain", "accelerated", "two_rtr"])
+def test_pgo_set_graph_larger_smaller_and_again(gpu, kind):
+    """accelerated and two_rtr hold the optional buffers (momentum V and Y; X at the round's start)."""
+    from kmx.dpgo.solver import BlockSolver
+    from kmx.synth import make_pose_graph
+    P = _pgo_params(kind)
+    A, B = make_pose_graph(2, 100, 300, seed=3), make_pose_graph(3, 150, 450, seed=4)
+    want = []
+    for g in (A, B):
+        f = BlockSolver(P, 0)
+        _pgo_load(f, g)
+        want.append(_pgo_rounds(f, g))
+        f.close()
+    assert want[0][3] != want[1][3]  # two sizes
+    s = BlockSolver(P, 0)
+    for g, w, what in ((A, want[0], "A"), (B, want[1], "B"), (A, want[0], "A again")):
+        _pgo_load(s, g)
+        _same(_pgo_rounds(s, g), w, what)
+    s.close()
+
+
+def test_pgo_scratch_and_status_words_grow(gpu):
+    """The scratch grows from a trajectory's (620 doubles) to an eval's (4000)
+    and the peers' status words from 8 to 100 (past the first 64). The status
+    words are zero: a peer whose last block update changed nothing."""
+    _in_torch_child("_pgo_scratch_and_status_words")
+
+
+def _pgo_scratch_and_status_words():
+    import torch
+    from kmx.dpgo.solver import BlockSolver
+    from kmx.synth import make_pose_graph
+    g = make_pose_graph(2, 100, 300, seed=3)
+    P = _pgo_params("plain")
+    seg = torch.zeros(101, dtype=torch.int32, device="cuda")
+    rows = torch.zeros(100, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+
+    def unpack_and_round(s, sizes):
+        for n_seg in sizes:
+            s.exchange_unpack(0, 0, seg.data_ptr(), n_seg, rows.data_ptr())
+        out = _pgo_rounds(s, g)
+        return out[:3], s.get_public(100)[1]
+
+    ref = BlockSolver(P, 0)
+    _pgo_load(ref, g)
+    want = unpack_and_round(ref, [100])
+    ref.close()
+    s = BlockSolver(P, 0)
+    _pgo_load(s, g)
+    anchor = s.get_iterate(0)[0]
+    t0 = s.trajectory(0, anchor)
+    grad, _ = s.eval(0, abi.KMX_EVAL_RGRAD)
+    assert np.abs(grad).max() > 0
+    _same(s.trajectory(0, anchor), t0, "trajectory after the scratch grew")
+    _same(unpack_and_round(s, [8, 100]), want, "round after the status words grew")
+    s.close()
