@@ -1345,6 +1345,87 @@ int kmx_dgraph_get_log(kmx_dgraph* h, int32_t cap, kmx_dgraph_log_entry* log, in
  * the matrix-free product kernel alone of the last KMX_DGRAPH_EVAL_JTJ. */
 int kmx_dgraph_get_timing(kmx_dgraph* h, double* ms /* [5] */);
 
+/* ------------------------------------------------------------------------- */
+/* Voxel simplification and deformation-graph build (Kimera-PGMO's stage       */
+/* between the mesh and the deformation graph), csrc/simplify.hip.             */
+/* ------------------------------------------------------------------------- */
+/* Additive to ABI 10. An append-only handle: after any sequence of
+ * kmx_simplify_add calls its arrays are those of one call with the
+ * concatenated input. Every output is an integer, a copied input or a given
+ * constant, so there is no tolerance.
+ *  - The key of a vertex is (robot, ix, iy, iz, win): i* = floor(double(x*) /
+ *    resolution), an fp64 division; win = stamp_ns / horizon_ns rounded toward
+ *    minus infinity, 0 when horizon_ns is 0.
+ *  - The representative of a key is the lowest vertex id that has it. Control
+ *    vertices are numbered in the order of their representatives, so an append
+ *    adds control ids at the end and vertex_to_control of an older vertex never
+ *    changes. A control vertex carries its representative's xyz (widened to
+ *    fp64), stamp and robot.
+ *  - A face is mapped through vertex_to_control, dropped when two corners are
+ *    equal, and of the faces with one unordered triple the one lowest in the
+ *    input is kept, corner order unchanged; the kept list is append-only.
+ *  - The mesh edges are the unique pairs (lo < hi) over the kept faces' sides
+ *    in lexicographic order, formed on request.
+ *  - The graph: nodes are the nk keyframes, then the control vertices (node
+ *    nk + c). For every mesh edge in order (lo+nk -> hi+nk), (hi+nk -> lo+nk)
+ *    at w_mesh; then for every control vertex c (c+nk -> link), (link -> c+nk)
+ *    at w_link, link = kf_offset[a] + the first position in robot a's
+ *    non-decreasing keyframe stamps whose stamp equals c's.
+ * A call that returns KMX_EINVAL or KMX_EUNSUP leaves the handle as it was. */
+typedef struct kmx_simplify kmx_simplify;
+typedef struct {
+  double resolution;     /* metres; finite and > 0 */
+  int64_t horizon_ns;    /* 0: off; >= 0 */
+  int32_t n_robots;      /* 1..65536 */
+  int32_t initial_slots; /* of both hash tables; 0: the default (1024), a power of two otherwise */
+} kmx_simplify_params;
+typedef struct {
+  int64_t n_vertices, n_faces_in, n_control, n_faces_kept;
+  int64_t vertex_slots, face_slots; /* of the two open-addressing tables */
+  int64_t device_bytes;
+  int32_t vertex_rehashes, face_rehashes; /* times a table was enlarged and filled again */
+  int32_t scan_span;                      /* elements one scan workgroup owns */
+  int32_t scan_span2;                     /* elements one pass of the scan's second level covers */
+} kmx_simplify_info_t;
+
+int kmx_simplify_create(const kmx_simplify_params* params, int device, kmx_simplify** out);
+int kmx_simplify_destroy(kmx_simplify* h);
+int kmx_simplify_set_stream(kmx_simplify* h, void* hip_stream);
+int kmx_simplify_sync(kmx_simplify* h);
+int kmx_simplify_info(kmx_simplify* h, kmx_simplify_info_t* info);
+/* Appends n_vertices vertices (robot[n], stamp_ns[n], xyz[n][3] fp32) and
+ * n_faces faces (faces[n_faces][3]: vertex ids, any vertex added so far, this
+ * call's included). first_vertex_out (or NULL): the id of the first new vertex;
+ * counts_out (or NULL) [2]: new control vertices, new kept faces. KMX_EINVAL
+ * for a null array with n > 0, a robot id out of range, a position that is not
+ * finite or whose voxel index exceeds int32, a face index out of range;
+ * KMX_EUNSUP for totals at or above 2^31 - 1. Returns when the result is formed. */
+int kmx_simplify_add(kmx_simplify* h, int64_t n_vertices, const int32_t* robot, const int64_t* stamp_ns,
+                     const float* xyz, int64_t n_faces, const int32_t* faces, int64_t* first_vertex_out,
+                     int64_t* counts_out);
+/* Control vertices [first, first + n): any output may be NULL. */
+int kmx_simplify_get_control(kmx_simplify* h, int64_t first, int64_t n, double* xyz, int64_t* stamp_ns,
+                             int32_t* robot, int32_t* representative);
+int kmx_simplify_get_vertex_map(kmx_simplify* h, int64_t first, int64_t n, int32_t* vertex_to_control);
+int kmx_simplify_get_faces(kmx_simplify* h, int64_t first, int64_t n, int32_t* faces /* [n][3] */);
+/* Forms the unique sorted pairs on the device (once per state of the handle). */
+int kmx_simplify_edges(kmx_simplify* h, int64_t* n_edges_out);
+int kmx_simplify_get_edges(kmx_simplify* h, int32_t* pairs /* [n_edges][2] */);
+/* kf_offset[n_robots + 1] from 0, kf_stamp[nk] robot by robot, non-decreasing
+ * within a robot. *n_directed_out = 2 n_edges + 2 n_control; src, dst, w of
+ * that length and link[n_control] are written when not NULL (all NULL: sizes
+ * only). KMX_EINVAL for n_robots other than the handle's, a kf_offset that
+ * does not start at 0 or decreases, keyframe stamps that decrease within a
+ * robot, or a control vertex without a keyframe at its stamp: kmx_last_error
+ * then names the lowest such robot, its count and its first such vertex. */
+int kmx_simplify_graph(kmx_simplify* h, int32_t n_robots, const int64_t* kf_offset, const int64_t* kf_stamp,
+                       double w_mesh, double w_link, int32_t* src, int32_t* dst, double* w, int64_t* link,
+                       int64_t* n_directed_out);
+/* Device times by HIP events of the last add, the last edge formation and the
+ * last graph (links and emit), 0 for one that has not run; waits. */
+int kmx_simplify_enable_timing(kmx_simplify* h, int enable);
+int kmx_simplify_read_timing(kmx_simplify* h, double* add_ms, double* edges_ms, double* graph_ms);
+
 #ifdef __cplusplus
 }
 #endif

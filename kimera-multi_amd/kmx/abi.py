@@ -211,6 +211,20 @@ class MeshStats(C.Structure):
                 ("max_displacement", C.c_double), ("sum_sq_displacement", C.c_double)]
 
 
+class SimplifyParams(C.Structure):
+    """kmx_simplify_params."""
+    _fields_ = [("resolution", C.c_double), ("horizon_ns", C.c_int64), ("n_robots", C.c_int32),
+                ("initial_slots", C.c_int32)]
+
+
+class SimplifyInfo(C.Structure):
+    """kmx_simplify_info_t."""
+    _fields_ = [("n_vertices", C.c_int64), ("n_faces_in", C.c_int64), ("n_control", C.c_int64),
+                ("n_faces_kept", C.c_int64), ("vertex_slots", C.c_int64), ("face_slots", C.c_int64),
+                ("device_bytes", C.c_int64), ("vertex_rehashes", C.c_int32), ("face_rehashes", C.c_int32),
+                ("scan_span", C.c_int32), ("scan_span2", C.c_int32)]
+
+
 class DgraphParams(C.Structure):
     """kmx_dgraph_params (0 in a field: the library's default; rel_tol < 0: its default)."""
     _fields_ = [("lambda_init", C.c_double), ("lambda_factor", C.c_double), ("lambda_min", C.c_double),
@@ -420,6 +434,20 @@ def lib() -> C.CDLL:
         "kmx_dgraph_solve": ([P, C.POINTER(DgraphParams), C.POINTER(DgraphResult)], C.c_int),
         "kmx_dgraph_get_log": ([P, i32, C.POINTER(DgraphLogEntry), pi32], C.c_int),
         "kmx_dgraph_get_timing": ([P, pf64], C.c_int),
+        "kmx_simplify_create": ([C.POINTER(SimplifyParams), C.c_int, C.POINTER(P)], C.c_int),
+        "kmx_simplify_destroy": ([P], C.c_int),
+        "kmx_simplify_set_stream": ([P, P], C.c_int),
+        "kmx_simplify_sync": ([P], C.c_int),
+        "kmx_simplify_info": ([P, C.POINTER(SimplifyInfo)], C.c_int),
+        "kmx_simplify_add": ([P, i64, pi32, pi64, C.POINTER(C.c_float), i64, pi32, pi64, pi64], C.c_int),
+        "kmx_simplify_get_control": ([P, i64, i64, pf64, pi64, pi32, pi32], C.c_int),
+        "kmx_simplify_get_vertex_map": ([P, i64, i64, pi32], C.c_int),
+        "kmx_simplify_get_faces": ([P, i64, i64, pi32], C.c_int),
+        "kmx_simplify_edges": ([P, pi64], C.c_int),
+        "kmx_simplify_get_edges": ([P, pi32], C.c_int),
+        "kmx_simplify_graph": ([P, i32, pi64, pi64, f64, f64, pi32, pi32, pf64, pi64, pi64], C.c_int),
+        "kmx_simplify_enable_timing": ([P, C.c_int], C.c_int),
+        "kmx_simplify_read_timing": ([P, pf64, pf64, pf64], C.c_int),
     })
     for name, (argt, rest) in sig.items():
         if not hasattr(L, name):

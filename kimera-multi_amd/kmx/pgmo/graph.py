@@ -3,8 +3,9 @@ csrc/dgraph.hip), and the host helpers that build a deformation graph from a
 mesh: simplify_voxel (the control vertices) and graph_from_mesh (mesh edges
 and keyframe links).
 
-The solve runs on the device. The simplification runs on the host in numpy; a
-device version is out of scope here.
+The solve runs on the device. The two helpers here run on the host in numpy
+and are the reference of the device version, simplify.MeshSimplifier
+(csrc/simplify.hip), which returns the same arrays append by append.
 """
 from __future__ import annotations
 

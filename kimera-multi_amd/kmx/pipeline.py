@@ -250,7 +250,7 @@ def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, ran
                  device: int = 0, rounds: int = 100, verifier=None, solver=None, exchange_device=None,
                  return_trajectory: bool = False, local_init: str = "odometry", certify_eta=None,
                  staircase_rmax=None, staircase_kw=None, mesh=None, mesh_k: int = 4,
-                 mesh_window_s: float = 1.0, mesh_graph=None) -> dict:
+                 mesh_window_s: float = 1.0, mesh_graph=None, mesh_graph_simplify: str = "host") -> dict:
     """One team run: LCD verification of this rank's candidates (query robot
     in the rank's robot range) -> all_gather of the accepted loop closures ->
     team graph -> global initialisation -> `rounds` concurrent RBCD rounds
@@ -291,7 +291,8 @@ def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, ran
     device with soft priors on the keyframes at the rounded RBCD trajectory
     (kmx.pgmo.DeformationGraph), and the vertices are bound to and moved by
     the graph's nodes; the "mesh" entry gains "graph" (see deform_mesh).
-    Returns stage timings and metrics (identical on every rank)."""
+    mesh_graph_simplify: deform_mesh's graph_simplify ("host", the default, or
+    "gpu"). Returns stage timings and metrics (identical on every rank)."""
     import time
 
     if certify_eta is not None and world > 1:
@@ -406,7 +407,8 @@ def run_pipeline(g0: PoseGraphData, stream: LcStream, params, lcd_params, *, ran
                 out["staircase"]["trajectory"] = traj
     if mesh is not None:
         out["mesh"] = deform_mesh(g, mesh, odometry_init(g), mine, k=mesh_k, window_s=mesh_window_s, device=device,
-                                  return_xyz=return_trajectory, graph_resolution=mesh_graph)
+                                  return_xyz=return_trajectory, graph_resolution=mesh_graph,
+                                  graph_simplify=mesh_graph_simplify)
     if hasattr(drv.solver, "close"):
         drv.solver.close()
     return out
@@ -425,7 +427,8 @@ def mesh_rmse(g: PoseGraphData, xyz, gt_xyz, traj: dict, *, anchor_robot: int = 
 
 def deform_mesh(g: PoseGraphData, mesh, rest: dict, current: dict, *, k: int = 4, window_s: float = 1.0,
                 device: int = 0, return_xyz: bool = False, graph_resolution=None, graph_kappa: float = 100.0,
-                graph_tau: float = 100.0, graph_solve=None, graph_horizon_s=None) -> dict:
+                graph_tau: float = 100.0, graph_solve=None, graph_horizon_s=None,
+                graph_simplify: str = "host") -> dict:
     """The mesh stage of run_pipeline: keyframes of every robot as control
     nodes (rest[a] -> current[a]), one bind and one deformation on the device.
     graph_resolution (metres; default None: off): the mesh is simplified on a
@@ -437,16 +440,26 @@ def deform_mesh(g: PoseGraphData, mesh, rest: dict, current: dict, *, k: int = 4
     starting from every control vertex moved by its keyframe's correction, and
     the vertices are bound to and moved by the graph's nodes. The result
     then has "graph": nodes, edges, control_vertices, iterations, accepted,
-    stop, cost_before, cost_after and solve_ms (device time)."""
+    stop, cost_before, cost_after and solve_ms (device time). graph_simplify:
+    where the simplification and the graph's edge arrays are formed: "host"
+    (numpy, the default) or "gpu" (kmx.pgmo.MeshSimplifier); the arrays are
+    equal, and so is everything after them."""
     from .pgmo import MeshDeformer
+    if graph_simplify not in ("host", "gpu"):
+        raise ValueError(f"unknown graph_simplify {graph_simplify!r}")
     graph = None
     if graph_resolution is None:
         md = MeshDeformer(k=k, window_s=window_s, n_robots=g.n_robots, device=device)
     else:
-        from .pgmo import DeformationGraph, graph_from_mesh, simplify_voxel
-        cx, cs, cr, cf, _ = simplify_voxel(mesh.xyz, mesh.faces, mesh.stamp, mesh.robot, graph_resolution,
-                                           horizon_s=graph_horizon_s)
-        G = graph_from_mesh(cx, cs, cr, cf, mesh.kf_stamp, [rest[a] for a in range(g.n_robots)])
+        from .pgmo import DeformationGraph, MeshSimplifier, graph_from_mesh, simplify_voxel
+        if graph_simplify == "gpu":
+            with MeshSimplifier(graph_resolution, graph_horizon_s, g.n_robots, device) as ms:
+                ms.add(mesh.xyz, mesh.faces, mesh.stamp, mesh.robot)
+                G = ms.graph(mesh.kf_stamp, [rest[a] for a in range(g.n_robots)])
+        else:
+            cx, cs, cr, cf, _ = simplify_voxel(mesh.xyz, mesh.faces, mesh.stamp, mesh.robot, graph_resolution,
+                                               horizon_s=graph_horizon_s)
+            G = graph_from_mesh(cx, cs, cr, cf, mesh.kf_stamp, [rest[a] for a in range(g.n_robots)])
         nk, n = G["n_keyframes"], G["g"].shape[0]
         mode = np.zeros(n, np.uint8)
         mode[:nk] = 1

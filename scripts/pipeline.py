@@ -45,6 +45,9 @@ def main():
     ap.add_argument("--mesh-graph", type=float, default=None, metavar="RES",
                     help="with --mesh: simplify the mesh on a voxel grid of RES metres, solve the deformation graph "
                          "over keyframes and control vertices on the device and deform through its nodes")
+    ap.add_argument("--mesh-graph-simplify", choices=("host", "gpu"), default="host",
+                    help="with --mesh-graph: where the mesh is simplified and the graph's edges are formed: numpy on "
+                         "the host (default) or kmx.pgmo.MeshSimplifier on the device; the arrays are equal")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -72,7 +75,8 @@ def main():
     gen = time.perf_counter() - t0
     out = PL.run_pipeline(g0, stream, bench.params(), LcdParams(), rank=rank, world=world, device=local_rank,
                           rounds=a.rounds, local_init=a.local_init, certify_eta=a.certify,
-                          staircase_rmax=a.staircase, mesh=mesh, mesh_graph=a.mesh_graph)
+                          staircase_rmax=a.staircase, mesh=mesh, mesh_graph=a.mesh_graph,
+                          mesh_graph_simplify=a.mesh_graph_simplify)
     out["config"] = {"workload": f"configs[4]: {a.robots} robots x {a.poses} poses, {g0.m} base edges "
                                  f"(intra-robot loop closures, 20% intra outliers, odometry noise "
                                  f"{a.sigma_r} rad / {a.sigma_t} m), LC stream "
